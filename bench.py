@@ -17,7 +17,10 @@ of that, from an idle GPU and without the preload, and reported next to it as `m
 behind it (`ms_per_step_repeats`, `ms_per_step_min`: the spread of the very protocol the headline ran, same W and K);
 `lattice_kernel` names the lattice kernel the headline's steps launched.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--preload-ms P]
+`--dump-outputs DIR` writes what the last timed step computed -- the arrays a caller of the timed path receives -- as
+DIR/<name>.npy (float32 / float64, see dump_outputs), so that two builds can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--preload-ms P] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -91,6 +94,10 @@ def parse():
     p.add_argument("--global-batch", type=int, default=0,
                    help="strong scaling: fix the GLOBAL number of utterances and shard it over the ranks "
                         "(default 0 = weak scaling, the config's per-GPU batch on every rank)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (its costs and a fixed, seeded "
+                        "sample of its log-probabilities) as DIR/<name>.npy; the inputs are seeded, so runs with the "
+                        "same arguments can be compared output for output")
     return p.parse_args()
 
 
@@ -122,6 +129,35 @@ def make_batch(cfg, rank, dev):
     xn = torch.full((N,), T, dtype=torch.int32, device=dev)
     yn = torch.full((N,), U - 1, dtype=torch.int32, device=dev)
     return xs, ys, xn, yn
+
+
+DUMP_SAMPLE = 1 << 21        # log-prob elements --dump-outputs writes at most (8 MiB of float32 + 16 MiB of indices)
+
+
+def dump_outputs(out_dir, outputs, rank, world):
+    """--dump-outputs: what the last timed step (of the last timed run) handed its caller, as .npy files of 24 MiB at
+    most in all: `costs` (N,) float32, whole; `log_probs` (N,T,U,V) float32, whole when it has at most DUMP_SAMPLE
+    elements, else the elements at up to DUMP_SAMPLE distinct sorted flat indices drawn from a CPU generator seeded 0
+    (the same for every run of the same shape), written beside it as float64 `log_probs_index`.  With --gpus N > 1
+    every rank writes its own slice, the names suffixed `_rank<r>`, with a sample of DUMP_SAMPLE / N per rank."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    costs, lp = outputs["costs"], outputs["log_probs"]
+    arrays = {"costs": costs.detach().float().cpu().numpy()}
+    flat = lp.detach().reshape(-1)
+    k = DUMP_SAMPLE // world
+    if flat.numel() <= k:
+        arrays["log_probs"] = flat.float().cpu().numpy().reshape(tuple(lp.shape))
+    else:
+        g = torch.Generator()
+        g.manual_seed(0)
+        idx = torch.unique(torch.randint(0, flat.numel(), (k,), generator=g, dtype=torch.int64))   # (sorted)
+        arrays["log_probs"] = flat[idx.to(flat.device)].float().cpu().numpy()
+        arrays["log_probs_index"] = idx.numpy().astype(np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), arr)
+    return sorted(name + sfx for name in arrays)
 
 
 def cpu_baseline(cfg, utts):
@@ -453,6 +489,7 @@ def main():
         cfg = (hi - lo,) + cfg[1:]
     N, T, U, V, gather, lam, inplace = cfg
     xs, ys, xn, yn = make_batch(cfg, rank, dev)
+    dump = a.dump_outputs is not None
     cells = N * T * U
 
     # HIP events around the two halves of a step, inside the timed region, on an evenly spaced sample of the steps
@@ -465,7 +502,7 @@ def main():
     ev_b = {i: torch.cuda.Event(enable_timing=True) for i in ev_steps}
     ev_c = {i: torch.cuda.Event(enable_timing=True) for i in ev_steps}
 
-    def step(i=None, last=False):
+    def step(i=None, last=False, keep=False):
         # timed region of benchmark.py:62-70: log_softmax + loss(+grads) forward
         ev = i is not None and i in ev_a
         if ev:
@@ -476,6 +513,8 @@ def main():
         costs = warp_rnnt.rnnt_loss(lp, ys, xn, yn, gather=gather, fastemit_lambda=lam)
         if ev:
             ev_c[i].record()
+        if keep:
+            kept.update(log_probs=lp, costs=costs)      # (references only: --dump-outputs writes them after the timing)
         if dist is None and not last:
             return None          # single GPU: the step is benchmark.py's, nothing is summed across ranks
         total = costs.sum()
@@ -487,6 +526,7 @@ def main():
         return total
 
     pending = []
+    kept = {}
 
     def fence():
         for h in pending:
@@ -522,7 +562,7 @@ def main():
         t0 = time.perf_counter()
         total = None
         for i in range(a.steps):
-            total = step(i if events else None, last=(i == a.steps - 1))
+            total = step(i if events else None, last=(i == a.steps - 1), keep=dump and i == a.steps - 1)
         fence()
         return time.perf_counter() - t0, total
 
@@ -763,6 +803,9 @@ def main():
         torch.cuda.synchronize()
         extras["ms_per_step_lazy_log_softmax"] = round(e5.elapsed_time(e6) / reps, 4)
 
+    dumped = dump_outputs(a.dump_outputs, kept, rank, world) if dump else None
+    kept.clear()
+
     if rank == 0:
         n_global = a.global_batch if a.global_batch else world * N
         value = n_global / (ms_step * 1e-3)
@@ -815,6 +858,8 @@ def main():
             "preload_ms": a.preload_ms,         # streaming copies enqueued in front of the warm-up steps (not steps)
         }
         out.update(extras)
+        if dump:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if not a.no_cpu_baseline and world == 1:   # the CPU leg is reported at N=1 only
             utts = a.cpu_utts or (16 if a.config in ("c2", "c4") else 4)
             if a.config == "c5":

@@ -88,3 +88,19 @@ def test_c4_line_prices_the_loss_entry_and_the_gather_too():
     assert 0.0 < d["native_compact_ms"] < d["cabi_compact_ms"] < 3.0 * d["native_compact_ms"]
     # the two halves of the step, as the events saw them, make up the step (launch gaps and event packets aside)
     assert abs(d["roofline"]["kernel_ms"] + lp["kernels_ms"] - d["ms_per_step"]) < 0.15 * d["ms_per_step"]
+
+
+def test_dump_outputs_writes_what_the_last_timed_step_computed(tmp_path):
+    import numpy as np
+    d = _run("--config", "c2", "--steps", "7", "--warmup", "2", "--no-cpu-baseline", "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 7 and d["ms_per_step"] > 0
+    assert sorted(d["dump_outputs"]["arrays"]) == ["costs", "log_probs", "log_probs_index"]
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ["costs.npy", "log_probs.npy", "log_probs_index.npy"]
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 << 20
+    costs, lp, idx = (np.load(tmp_path / f) for f in files)
+    assert costs.dtype == np.float32 and costs.shape == (16,) and lp.dtype == np.float32 and idx.dtype == np.float64
+    assert lp.shape == idx.shape and np.all(np.diff(idx) > 0) and idx[-1] < 16 * 150 * 40 * 28
+    # the costs are the step's loss (the line's checksum is their sum); the sampled log-probs are log-probabilities
+    assert abs(float(costs.astype(np.float64).sum()) - d["loss_checksum"]) <= 1e-3 * abs(d["loss_checksum"]) + 1e-3
+    assert np.all(np.isfinite(lp)) and np.all(lp <= 0)

@@ -26,11 +26,16 @@ def test_random_cases_against_the_oracle(kernel, seed):
     assert out.returncode == 0 and "fuzz ok:" in text, text[-3000:]
 
 
+# Six processes with the device open at once, the most a shared GPU node allows: the test session's own (it has
+# initialised the runtime) and five soak processes launching on it.
+SOAK_PROCS = 5
+
+
 @pytest.mark.parametrize("name,env_extra", [("default", {}), ("wl", {"RNNT_DEBUG_LATTICE_KERNEL": "wl"}),
                                             ("k8", {"RNNT_WD_K16_FROM_T": "1000000"})])
 def test_six_processes_on_one_gpu_get_the_reference_bits_every_launch(name, env_extra):
-    """tools/wd_soak.py: six processes launch the loss entry back to back on the soak's shape set at the same time (45 s each
-    leg) and compare every launch -- costs, gradients, alpha and beta planes -- bit for bit with a reference computed once
+    """tools/wd_soak.py: six processes have the GPU open, five of them launch the loss entry back to back on the soak's
+    shape set at the same time (45 s each leg) and compare every launch -- costs, gradients, alpha and beta planes -- bit for bit with a reference computed once
     by the OTHER kernel (k_lattice_ws: compiler-scheduled, no in-place reloads, no hand-over through L2).  This is the load
     that found what no single-process test could: the hand-written lattice blocks with reloads left in flight across the
     barrier (round 5) gave wrong costs in 1-3 % of the launches under it and never otherwise, the storer's dry run without
@@ -39,7 +44,8 @@ def test_six_processes_on_one_gpu_get_the_reference_bits_every_launch(name, env_
     lattices, the plain launch for single column blocks; blocks of 16 diagonals from T >= 1024, the default since round 6),
     k_lattice_wl pinned wherever it fits, and k_lattice_wd with blocks of 8 diagonals everywhere.  The static half of the gate is in the build (warp_rnnt_amd/_isa_check.py)."""
     env = dict(os.environ, **env_extra)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "wd_soak.py"), "--seconds", "45", "--procs", "6"],
-                         env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "wd_soak.py"), "--seconds", "45", "--procs",
+                          str(SOAK_PROCS)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     text = out.stdout.decode()
-    assert out.returncode == 0 and text.count("results differing from the k_lattice_ws reference: 0;") == 6, text[-3000:]
+    assert out.returncode == 0 and text.count("results differing from the k_lattice_ws reference: 0;") == SOAK_PROCS, \
+        text[-3000:]
