@@ -262,6 +262,34 @@ rnntStatus_t rnnt_amd_logits_backward(rnntStream_t stream, const float *logits, 
                                       const float *grads_diagonal, const float *grad_costs, float *dlogits,
                                       int N, int T, int U, int V, int blank);
 
+/*
+ * Half-precision logits on the fused path (version 107).  `dtype` is the element type of the logits:
+ * RNNT_DTYPE_F32, RNNT_DTYPE_BF16 or RNNT_DTYPE_F16; anything else is RNNT_STATUS_INVALID_ARGUMENT, returned before
+ * any HIP call, as is every size the fp32 entry would refuse.  One arithmetic whatever the storage type: the logits
+ * are converted to fp32 as they are loaded and everything behind the load is the fp32 code, so with a base pointer
+ * aligned to 4 elements
+ *   - costs, diagonal-major gradient pairs and log-probs (fp32 at every dtype) are bit-equal to the fp32 entries on
+ *     the logits converted to fp32;
+ *   - d/d logits are in the logits' dtype: the fp32 result converted once, round to nearest even (NaN and inf kept).
+ * Another base pointer runs a kernel that serves any alignment: costs within 1e-6 relative, d/d logits within one ulp
+ * of the storage type.
+ */
+enum {
+    RNNT_DTYPE_F32 = 0,
+    RNNT_DTYPE_BF16 = 1,
+    RNNT_DTYPE_F16 = 2
+};
+/* rnnt_amd_loss(RNNT_IN_LOGITS_DENSE, ...) on logits of type `dtype`: the same grads_kind set (GATHERED, GATHERED_DIAGONAL,
+ * NONE), the same workspace size; with RNNT_DTYPE_F32 it is that call, bit for bit. */
+rnntStatus_t rnnt_amd_loss_logits(rnntStream_t stream, void *workspace, int dtype, const void *logits, const int *labels,
+                                  const int *xn, const int *yn, float *costs, float *grads, int grads_kind, int N, int T,
+                                  int U, int V, int blank, float fastemit_lambda);
+/* rnnt_amd_logits_backward on logits of type `dtype`; dlogits (N,T,U,V) is of that type too (it may alias logits). */
+rnntStatus_t rnnt_amd_logits_backward_typed(rnntStream_t stream, int dtype, const void *logits, const int *labels,
+                                            const float *grads_diagonal, const float *grad_costs, void *dlogits,
+                                            int N, int T, int U, int V, int blank);
+/* rnnt_amd_log_softmax on x of type `dtype`; out is fp32 (it may alias x only for RNNT_DTYPE_F32). */
+rnntStatus_t rnnt_amd_log_softmax_typed(rnntStream_t stream, int dtype, const void *x, float *out, int64_t rows, int V);
 /* Row-wise log-softmax over the last axis; out may alias x. */
 rnntStatus_t rnnt_amd_log_softmax(rnntStream_t stream, const float *x, float *out, int64_t rows, int V);
 

@@ -41,11 +41,16 @@ def _check_cuda(x, name):
         raise RuntimeError(f"{name} must be located in the CUDA")
 
 
-def check_inputs(xs, ys, xn, yn):
-    """binding.cpp:32-51 -- contiguity, then dtypes, then device, then shapes."""
+def check_inputs(xs, ys, xn, yn, xs_dtypes=None):
+    """binding.cpp:32-51 -- contiguity, then dtypes, then device, then shapes.  ``xs_dtypes``: the element types xs may
+    have instead of fp32 only (the fused logits entry: fp32, bf16, fp16); the reference-shaped ops leave it unset."""
     for x, name in ((xs, "xs"), (ys, "ys"), (xn, "xn"), (yn, "yn")):
         _check_contiguous(x, name)
-    _check_float(xs, "xs")
+    if xs_dtypes is None:
+        _check_float(xs, "xs")
+    elif xs.dtype not in xs_dtypes:
+        names = ", ".join(str(d).replace("torch.", "") for d in xs_dtypes[:-1]) + " or " + str(xs_dtypes[-1]).replace("torch.", "")
+        raise RuntimeError(f"xs (logits) must be a {names} tensor, not {xs.dtype}")
     for x, name in ((ys, "ys"), (xn, "xn"), (yn, "yn")):
         _check_int(x, name)
     for x, name in ((xs, "xs"), (ys, "ys"), (xn, "xn"), (yn, "yn")):

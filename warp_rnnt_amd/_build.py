@@ -13,7 +13,8 @@ from . import _isa_check
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwarp_rnnt_amd.so")
-SOURCES = ["api.hip", "lattice.hip", "lattice_ws.hip", "lattice_wd.hip", "grads.hip", "prologue.hip", "expand.hip"]
+SOURCES = ["api.hip", "lattice.hip", "lattice_ws.hip", "lattice_wd.hip", "grads.hip", "prologue.hip", "prologue_half.hip",
+           "expand.hip"]
 HEADERS = ["common.h", "kernels.h", "lattice_step.h", "lattice_wd_body.h", "lattice_single.h", "grads_cell.h",
            os.path.join("..", "..", "include", "warp_rnnt_amd.h")]
 ARCH = "gfx950"
@@ -25,7 +26,8 @@ RELOAD_CHECKED = {"lattice_wd.hip": (8, 600)}
 # Sources with inline assembly of any kind: their ISA is walked for the wait-state hazards the compiler's recognizer does
 # not resolve around an `asm` statement (_isa_check: third rule -- DPP behind a VALU write, a transcendental's result in
 # the next slot, a VALU write behind a wide store).  Value: kernels the file is known to hold at least.
-HAZARD_CHECKED = {"lattice_wd.hip": 8, "lattice.hip": 4, "lattice_ws.hip": 2, "prologue.hip": 60}
+HAZARD_CHECKED = {"lattice_wd.hip": 8, "lattice.hip": 4, "lattice_ws.hip": 2, "prologue.hip": 60,
+                  "prologue_half.hip": 160}
 
 
 def _hipcc():

@@ -21,6 +21,8 @@ STATUS_NAMES = {
 # input_kind / grads_kind enums of rnnt_amd_loss
 IN_LOG_PROBS_DENSE, IN_LOG_PROBS_GATHERED, IN_LOGITS_DENSE = 0, 1, 2
 GRADS_GATHERED, GRADS_GATHERED_DIAGONAL, GRADS_DENSE, GRADS_NONE = 0, 1, 2, 3
+# element type of the logits for the typed entries (rnnt_amd_loss_logits, ..._typed)
+DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 
 # every symbol include/warp_rnnt_amd.h declares: (restype, argtypes)
 _vp, _i, _f, _sz, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
@@ -38,6 +40,9 @@ SYMBOLS = {
     "rnnt_amd_expand_grads": (_i, [_vp] * 7 + [_i] * 6),
     "rnnt_amd_logits_backward": (_i, [_vp] * 6 + [_i] * 5),
     "rnnt_amd_log_softmax": (_i, [_vp, _vp, _vp, _i64, _i]),
+    "rnnt_amd_loss_logits": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f]),
+    "rnnt_amd_logits_backward_typed": (_i, [_vp, _i] + [_vp] * 5 + [_i] * 5),
+    "rnnt_amd_log_softmax_typed": (_i, [_vp, _i, _vp, _vp, _i64, _i]),
     "rnnt_amd_log_softmax_backward": (_i, [_vp, _vp, _vp, _vp, _i64, _i]),
     "rnnt_amd_gather": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "rnnt_amd_workspace_size_compact": (_sz, [_i, _i64, _i, _i]),
@@ -56,7 +61,7 @@ SYMBOLS = {
 }
 
 
-ABI_VERSION = 106   # rnnt_amd_version() of the library these argument lists belong to
+ABI_VERSION = 107   # rnnt_amd_version() of the library these argument lists belong to
 
 
 class RNNTStatusError(RuntimeError):

@@ -69,7 +69,7 @@ bool dims_ok(int N, int T, int U) {
 
 extern "C" {
 
-int rnnt_amd_version(void) { return 106; }
+int rnnt_amd_version(void) { return 107; }
 
 int rnnt_amd_debug_set_lattice_kernel(int kernel) { return set_lattice_kernel_override(kernel); }
 
@@ -197,10 +197,13 @@ rnntStatus_t run_warp_rnnt_gather(rnntStream_t stream, unsigned int* counts, flo
     return RNNT_STATUS_SUCCESS;
 }
 
-rnntStatus_t rnnt_amd_loss(rnntStream_t stream, void* workspace, int input_kind, const float* input,
-                           const int* labels, const int* xn, const int* yn, float* costs, float* grads,
-                           int grads_kind, int N, int T, int U, int V, int blank,
-                           float fastemit_lambda) {
+// rnnt_amd_loss with the element type of the input (RNNT_DTYPE_*: anything but fp32 for RNNT_IN_LOGITS_DENSE only)
+static rnntStatus_t loss_of_type(rnntStream_t stream, void* workspace, int input_kind, int dtype, const void* input_any,
+                                 const int* labels, const int* xn, const int* yn, float* costs, float* grads,
+                                 int grads_kind, int N, int T, int U, int V, int blank, float fastemit_lambda) {
+    if (dtype != RNNT_DTYPE_F32 && (input_kind != RNNT_IN_LOGITS_DENSE || (dtype != RNNT_DTYPE_BF16 && dtype != RNNT_DTYPE_F16)))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    const float* input = static_cast<const float*>(input_any);      // (fp32 input kinds only)
     if (!dims_ok(N, T, U) || !workspace) return RNNT_STATUS_INVALID_ARGUMENT;
     if (reinterpret_cast<uintptr_t>(workspace) % ALIGN) return RNNT_STATUS_INVALID_ARGUMENT;
     const bool gathered_in = input_kind == RNNT_IN_LOG_PROBS_GATHERED;
@@ -231,7 +234,10 @@ rnntStatus_t rnnt_amd_loss(rnntStream_t stream, void* workspace, int input_kind,
             la.prepared = lattice_ring_prep(stream, la, N, LOAD_SKEWED, &prep) ? 1 : 0;
             e = launch_reskew(stream, input, w.ws2, N, T, U, &prep); break;
         case RNNT_IN_LOGITS_DENSE:
-            e = launch_log_softmax_gather_skewed(stream, input, labels, w.ws2, N, T, U, V, blank); break;
+            e = dtype == RNNT_DTYPE_F32
+                    ? launch_log_softmax_gather_skewed(stream, input, labels, w.ws2, N, T, U, V, blank)
+                    : launch_log_softmax_gather_skewed_half(stream, dtype, input_any, labels, w.ws2, N, T, U, V, blank);
+            break;
         default:
             return RNNT_STATUS_INVALID_ARGUMENT;
     }
@@ -269,6 +275,22 @@ rnntStatus_t rnnt_amd_loss(rnntStream_t stream, void* workspace, int input_kind,
         if (launch_unskew(stream, w.ws2, nullptr, grads, N, T, U) != hipSuccess) return RNNT_STATUS_EXPAND_FAILED;
     }
     return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_loss(rnntStream_t stream, void* workspace, int input_kind, const float* input,
+                           const int* labels, const int* xn, const int* yn, float* costs, float* grads,
+                           int grads_kind, int N, int T, int U, int V, int blank,
+                           float fastemit_lambda) {
+    return loss_of_type(stream, workspace, input_kind, RNNT_DTYPE_F32, input, labels, xn, yn, costs, grads, grads_kind, N, T,
+                        U, V, blank, fastemit_lambda);
+}
+
+rnntStatus_t rnnt_amd_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits, const int* labels,
+                                  const int* xn, const int* yn, float* costs, float* grads, int grads_kind, int N, int T,
+                                  int U, int V, int blank, float fastemit_lambda) {
+    if (dtype != RNNT_DTYPE_F32 && dtype != RNNT_DTYPE_BF16 && dtype != RNNT_DTYPE_F16) return RNNT_STATUS_INVALID_ARGUMENT;
+    return loss_of_type(stream, workspace, RNNT_IN_LOGITS_DENSE, dtype, logits, labels, xn, yn, costs, grads, grads_kind, N,
+                        T, U, V, blank, fastemit_lambda);
 }
 
 // Diagnostics: run only the alpha/beta sweep on whatever the workspace holds (after a call to
@@ -576,6 +598,29 @@ rnntStatus_t rnnt_amd_logits_backward(rnntStream_t stream, const float* logits, 
     if (launch_logits_backward(stream, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
         hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_logits_backward_typed(rnntStream_t stream, int dtype, const void* logits, const int* labels,
+                                            const float* grads_diagonal, const float* grad_costs, void* dlogits,
+                                            int N, int T, int U, int V, int blank) {
+    if (dtype == RNNT_DTYPE_F32)
+        return rnnt_amd_logits_backward(stream, static_cast<const float*>(logits), labels, grads_diagonal, grad_costs,
+                                        static_cast<float*>(dlogits), N, T, U, V, blank);
+    if (dtype != RNNT_DTYPE_BF16 && dtype != RNNT_DTYPE_F16) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dims_ok(N, T, U) || V < 1 || blank < 0 || blank >= V) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (U > 1 && !labels) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (launch_logits_backward_half(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
+        hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_log_softmax_typed(rnntStream_t stream, int dtype, const void* x, float* out, int64_t rows, int V) {
+    if (dtype == RNNT_DTYPE_F32) return rnnt_amd_log_softmax(stream, static_cast<const float*>(x), out, rows, V);
+    if (dtype != RNNT_DTYPE_BF16 && dtype != RNNT_DTYPE_F16) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (rows < 0 || V < 1) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (launch_log_softmax_half(stream, dtype, x, out, rows, V) != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
 

@@ -165,6 +165,14 @@ hipError_t launch_log_softmax_gather_skewed(hipStream_t stream, const float* log
 hipError_t launch_logits_backward(hipStream_t stream, const float* logits, const int* labels,
                                   const float* g2_diagonal, const float* scale, float* dlogits, int N, int T,
                                   int U, int V, int blank);
+// the same three for half-precision logits (prologue_half.hip), dtype RNNT_DTYPE_BF16 or RNNT_DTYPE_F16: fp32 arithmetic
+// from the load on, pairs and log-probs in fp32, d/d logits in the logits' type (hipErrorInvalidValue for another dtype)
+hipError_t launch_log_softmax_half(hipStream_t stream, int dtype, const void* x, float* out, int64_t rows, int V);
+hipError_t launch_log_softmax_gather_skewed_half(hipStream_t stream, int dtype, const void* logits, const int* labels,
+                                                 float* ws2, int N, int T, int U, int V, int blank);
+hipError_t launch_logits_backward_half(hipStream_t stream, int dtype, const void* logits, const int* labels,
+                                       const float* g2_diagonal, const float* scale, void* dlogits, int N, int T,
+                                       int U, int V, int blank);
 hipError_t launch_expand(hipStream_t stream, const float* g2_skewed, const int* labels,
                          const int* xn, const int* yn, const float* scale, float* dense, int N,
                          int T, int U, int V, int blank, int overwrite_mode);

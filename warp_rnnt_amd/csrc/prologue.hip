@@ -115,6 +115,39 @@ enum LsmMode : int {
     LSM_BWD = 2      // d(loss)/d(logits) rows from the gathered gradients:
                      //   dz[v] = s*( [v==blank]gB + [v==label]gL - softmax(z)[v]*(gB+gL) )
 };
+// Storage type E of the logits: float, or __bf16 / _Float16 (RNNT_DTYPE_BF16 / _F16, prologue_half.hip).  Half-precision
+// logits are converted to fp32 as they are loaded -- everything behind the load is the fp32 code -- and d/d logits (LSM_BWD)
+// are converted back ONCE, round to nearest even (the compiler's cast: v_cvt_pk_bf16_f32 / v_cvt_f16_f32), as they are
+// stored.  The kernels move rows in vectors of four elements (16 bytes of fp32, 8 of half) and every alignment predicate of
+// dispatch_lsm is stated in those vectors, so a V reaches the same kernel, the same lanes per row and the same reduction
+// tree at every E: the bits of a half-precision row are those of its fp32 upcast.
+template <typename E> struct LsmVec { typedef E type __attribute__((ext_vector_type(4))); };
+template <typename E> using lsm_vec_t = typename LsmVec<E>::type;
+template <int MODE, typename E> using LsmOut = std::conditional_t<MODE == LSM_BWD, E, float>;   // what `out` holds
+template <bool NT, typename E, typename I> __device__ __forceinline__ float4 lsm_ld4(const E* base, I i) {
+    if constexpr (std::is_same_v<E, float>) {
+        return lsm_load4<NT>(reinterpret_cast<const float4*>(base) + i);
+    } else {
+        const lsm_vec_t<E>* p = reinterpret_cast<const lsm_vec_t<E>*>(base) + i;
+        lsm_vec_t<E> h;
+        if constexpr (NT) h = __builtin_nontemporal_load(p); else h = *p;
+        const rnnt_f4 v = __builtin_convertvector(h, rnnt_f4);
+        return make_float4(v.x, v.y, v.z, v.w);
+    }
+}
+template <bool NT, typename E, typename I> __device__ __forceinline__ void lsm_st4(E* base, I i, float4 v) {
+    if constexpr (std::is_same_v<E, float>) {
+        lsm_store4<NT>(reinterpret_cast<float4*>(base) + i, v);
+    } else {
+        const rnnt_f4 w = {v.x, v.y, v.z, v.w};
+        const lsm_vec_t<E> h = __builtin_convertvector(w, lsm_vec_t<E>);
+        lsm_vec_t<E>* p = reinterpret_cast<lsm_vec_t<E>*>(base) + i;
+        if constexpr (NT) __builtin_nontemporal_store(h, p); else *p = h;
+    }
+}
+template <typename E> __device__ __forceinline__ float lsm_ld1(const E* p) { return (float)*p; }
+template <typename E> __device__ __forceinline__ void lsm_st1(E* p, float v) { *p = (E)v; }
+
 struct LsmBwd {
     const float2* g2;    // diagonal-major gathered gradients (RNNT_GRADS_GATHERED_DIAGONAL)
     const float* scale;  // (N,) upstream gradient per utterance, or nullptr
@@ -129,6 +162,12 @@ constexpr int SM_THREADS = RNNT_SM_THREADS;
 #define RNNT_SM_FLOATS 3200
 #endif
 constexpr int SM_FLOATS = RNNT_SM_FLOATS;   // LDS tile budget in floats: one pass of the 256 threads over a 12.5 KiB tile.  (512 threads x 25 KiB: 2 % faster in the isolated probe, slower in bench.py and in the fused gather mode; two passes per tile or 50 KiB tiles are clearly worse.)
+// In the fused gather the shared tile of half-precision logits holds twice the rows: 12.8 KB of HBM per tile, as for fp32
+// (c4, bf16: 178 -> 172 us; the fused backward, which also writes the tile back, 287 -> 290 us with it and keeps the
+// fp32 row count).  Rows per tile do not touch the bits: the lanes of a row and its reduction tree stay the same.
+template <typename E, int MODE> constexpr int sm_floats() {
+    return MODE == LSM_GATHER ? SM_FLOATS * (int)(sizeof(float) / sizeof(E)) : SM_FLOATS;
+}
 constexpr float LOG2E = 1.44269504088896340736f;
 constexpr float LN2 = 0.693147180559945309417f;
 
@@ -142,9 +181,9 @@ __device__ __forceinline__ void wave_sync_lds() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int L, int MODE, bool WP>
+template <typename E, int L, int MODE, bool WP>
 __global__ void __launch_bounds__(SM_THREADS)
-k_lsm_small(const float* x, float* out, const int* __restrict__ labels,
+k_lsm_small(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
             int64_t rows, int V, int R, int q, int T, int U, int blank, LsmBwd bw) {
     constexpr bool GATHER = MODE == LSM_GATHER;
     extern __shared__ __attribute__((aligned(16))) float tile[];
@@ -154,7 +193,7 @@ k_lsm_small(const float* x, float* out, const int* __restrict__ labels,
     if (row0 >= rows) return;
     const int nrows = (int)min((int64_t)R, rows - row0);
     const int nel = nrows * V;                      // floats in this chunk
-    const float* src = x + row0 * V;                // 16-byte aligned: R % 4 == 0 (out may alias x)
+    const E* src = x + row0 * V;                    // vector aligned: R % 4 == 0 (out may alias x)
     // wave-private view of the same tile: rows [wr0, wr0 + wn) of the chunk
     constexpr int RW = (WAVE / L) > 0 ? (WAVE / L) : 1;
     const int lane = tid & (WAVE - 1);
@@ -183,33 +222,31 @@ k_lsm_small(const float* x, float* out, const int* __restrict__ labels,
     // the LDS writes (lanes past the end rewrite the tile's last 16 bytes with the bytes that are there).  A predicate per
     // load comes out as a branch per load with a conservative wait at every join; predicates on the writes alone and the
     // compiler sinks the loads into them.
-    constexpr int STAGE_UN = WP ? 4 : (SM_FLOATS / 4 + SM_THREADS - 1) / SM_THREADS;   // (3200 floats, 256 threads: 4)
+    constexpr int STAGE_UN = WP ? 4 : (sm_floats<E, MODE>() / 4 + SM_THREADS - 1) / SM_THREADS;   // (3200 floats, 256 threads: 4)
     if constexpr (WP) {
-        const float4* wsrc4 = reinterpret_cast<const float4*>(src + (size_t)wr0 * V);
+        const E* wsrc = src + (size_t)wr0 * V;
         for (int base = lane; base < wvec; base += STAGE_UN * WAVE) {
             float4 sv[STAGE_UN];
 #pragma unroll
             for (int k = 0; k < STAGE_UN; ++k)
-                sv[k] = RNNT_LSM_LOAD(wsrc4 + min(base + k * WAVE, wvec - 1));
+                sv[k] = lsm_ld4<RNNT_LSM_NT_MODE(MODE)>(wsrc, min(base + k * WAVE, wvec - 1));
 #pragma unroll
             for (int k = 0; k < STAGE_UN; ++k)
                 reinterpret_cast<float4*>(wtile)[min(base + k * WAVE, wvec - 1)] = sv[k];
         }
-        const float* wsrc = src + (size_t)wr0 * V;
-        for (int e = (wvec << 2) + lane; e < wel; e += WAVE) wtile[e] = wsrc[e];
+        for (int e = (wvec << 2) + lane; e < wel; e += WAVE) wtile[e] = lsm_ld1(wsrc + e);
         wave_sync_lds();
     } else {
-        const float4* src4 = reinterpret_cast<const float4*>(src);
         for (int base = tid; base < nvec; base += STAGE_UN * SM_THREADS) {
             float4 sv[STAGE_UN];
 #pragma unroll
             for (int k = 0; k < STAGE_UN; ++k)
-                sv[k] = RNNT_LSM_LOAD(src4 + min(base + k * SM_THREADS, nvec - 1));
+                sv[k] = lsm_ld4<RNNT_LSM_NT_MODE(MODE)>(src, min(base + k * SM_THREADS, nvec - 1));
 #pragma unroll
             for (int k = 0; k < STAGE_UN; ++k)
                 reinterpret_cast<float4*>(tile)[min(base + k * SM_THREADS, nvec - 1)] = sv[k];
         }
-        for (int e = (nvec << 2) + tid; e < nel; e += SM_THREADS) tile[e] = src[e];   // last chunk only
+        for (int e = (nvec << 2) + tid; e < nel; e += SM_THREADS) tile[e] = lsm_ld1(src + e);   // last chunk only
         __syncthreads();
     }
 
@@ -329,16 +366,28 @@ k_lsm_small(const float* x, float* out, const int* __restrict__ labels,
         }
     } else if constexpr (WP) {
         wave_sync_lds();
-        float* wdst = out + (row0 + wr0) * V;
-        for (int i = lane; i < wvec; i += WAVE)
-            RNNT_LSM_STORE(reinterpret_cast<float4*>(wdst) + i, reinterpret_cast<const float4*>(wtile)[i]);
-        for (int e = (wvec << 2) + lane; e < wel; e += WAVE) wdst[e] = wtile[e];
+        LsmOut<MODE, E>* wdst = out + (row0 + wr0) * V;
+        if constexpr (std::is_same_v<E, float>) {
+            for (int i = lane; i < wvec; i += WAVE)
+                RNNT_LSM_STORE(reinterpret_cast<float4*>(wdst) + i, reinterpret_cast<const float4*>(wtile)[i]);
+            for (int e = (wvec << 2) + lane; e < wel; e += WAVE) wdst[e] = wtile[e];
+        } else {
+            for (int i = lane; i < wvec; i += WAVE)
+                lsm_st4<RNNT_LSM_NT_MODE(MODE)>(wdst, i, reinterpret_cast<const float4*>(wtile)[i]);
+            for (int e = (wvec << 2) + lane; e < wel; e += WAVE) lsm_st1(wdst + e, wtile[e]);
+        }
     } else {
         __syncthreads();
-        float* dst = out + row0 * V;
-        for (int i = tid; i < nvec; i += SM_THREADS)
-            RNNT_LSM_STORE(reinterpret_cast<float4*>(dst) + i, reinterpret_cast<const float4*>(tile)[i]);
-        for (int e = (nvec << 2) + tid; e < nel; e += SM_THREADS) dst[e] = tile[e];
+        LsmOut<MODE, E>* dst = out + row0 * V;
+        if constexpr (std::is_same_v<E, float>) {
+            for (int i = tid; i < nvec; i += SM_THREADS)
+                RNNT_LSM_STORE(reinterpret_cast<float4*>(dst) + i, reinterpret_cast<const float4*>(tile)[i]);
+            for (int e = (nvec << 2) + tid; e < nel; e += SM_THREADS) dst[e] = tile[e];
+        } else {
+            for (int i = tid; i < nvec; i += SM_THREADS)
+                lsm_st4<RNNT_LSM_NT_MODE(MODE)>(dst, i, reinterpret_cast<const float4*>(tile)[i]);
+            for (int e = (nvec << 2) + tid; e < nel; e += SM_THREADS) lsm_st1(dst + e, tile[e]);
+        }
     }
 }
 
@@ -385,9 +434,9 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) 
     return r;
 }
 
-template <int MODE, int LG_THREADS, int LG_MAXVEC>
+template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
 __global__ void __launch_bounds__(LG_THREADS)
-k_lsm_large(const float* x, float* out, const int* __restrict__ labels,
+k_lsm_large(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
             int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
     constexpr bool GATHER = MODE == LSM_GATHER;
     __shared__ float red[LG_THREADS / WAVE];
@@ -398,7 +447,7 @@ k_lsm_large(const float* x, float* out, const int* __restrict__ labels,
     for (size_t it = blockIdx.x; it < items; it += gridDim.x) {
     const size_t row = bw.xcd ? (it & 7) * per_xcd + (it >> 3) : it;
     if (row >= (size_t)rows) continue;
-    const float4* src = reinterpret_cast<const float4*>(x + row * V);
+    const E* src = x + row * V;
     const int nvec = V >> 2;
     // How a lane's LG_MAXVEC loads are issued (round 5).  As first written -- load and running maximum together under
     // `if (j < nvec)` -- every load sits in a branch of its own with an s_waitcnt vmcnt(0) behind it: LG_MAXVEC memory
@@ -420,9 +469,9 @@ k_lsm_large(const float* x, float* out, const int* __restrict__ labels,
         for (int i = 0; i < LG_MAXVEC; ++i) {
             const int j = (int)threadIdx.x + i * LG_THREADS;
             if constexpr (CLAMPED) {
-                v[i] = NT_LOADS ? rnnt_nt_load4(src + min(j, nvec - 1)) : src[min(j, nvec - 1)];
+                v[i] = NT_LOADS ? lsm_ld4<true>(src, min(j, nvec - 1)) : lsm_ld4<false>(src, min(j, nvec - 1));
             } else {
-                if (j < nvec) v[i] = NT_LOADS ? rnnt_nt_load4(src + j) : src[j];
+                if (j < nvec) v[i] = NT_LOADS ? lsm_ld4<true>(src, j) : lsm_ld4<false>(src, j);
             }
         }
     }
@@ -433,8 +482,8 @@ k_lsm_large(const float* x, float* out, const int* __restrict__ labels,
     if constexpr (MODE != LSM_NORM) {
         m = map_cell(row, labels, T, U, V, blank);
         if constexpr (GATHER) {
-            const float* xr = x + row * V;
-            side = make_float2(xr[blank], xr[m.label]);
+            const E* xr = x + row * V;
+            side = make_float2(lsm_ld1(xr + blank), lsm_ld1(xr + m.label));
         } else {
             side = bw.g2[m.sk];
             sc = bw.scale ? bw.scale[m.n] : 1.0f;
@@ -451,7 +500,7 @@ k_lsm_large(const float* x, float* out, const int* __restrict__ labels,
             mx = fmaxf(fmaxf(mx, fmaxf(v[i].x, v[i].y)), fmaxf(v[i].z, v[i].w));
         } else {
             if (j < nvec) {
-                v[i] = NT_LOADS ? rnnt_nt_load4(src + j) : src[j];
+                v[i] = NT_LOADS ? lsm_ld4<true>(src, j) : lsm_ld4<false>(src, j);
                 mx = fmaxf(fmaxf(mx, fmaxf(v[i].x, v[i].y)), fmaxf(v[i].z, v[i].w));
             }
         }
@@ -475,7 +524,7 @@ k_lsm_large(const float* x, float* out, const int* __restrict__ labels,
         const float2 g = side;
         const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
         const float mb2 = -(mx + ls) * LOG2E;
-        float4* dst = reinterpret_cast<float4*>(out + row * V);
+        LsmOut<MODE, E>* dst = out + row * V;
 #pragma unroll
         for (int i = 0; i < LG_MAXVEC; ++i) {
             const int j = threadIdx.x + i * LG_THREADS;
@@ -489,19 +538,19 @@ k_lsm_large(const float* x, float* out, const int* __restrict__ labels,
                     d += (e == m.label) ? gL : 0.0f;
                     o[cc] = d;
                 }
-                if ((RNNT_LG_NT_FUSED * RNNT_LG_NT) & 2) rnnt_nt_store4(dst + j, make_float4(o[0], o[1], o[2], o[3]));
-                else dst[j] = make_float4(o[0], o[1], o[2], o[3]);
+                if ((RNNT_LG_NT_FUSED * RNNT_LG_NT) & 2) lsm_st4<true>(dst, j, make_float4(o[0], o[1], o[2], o[3]));
+                else lsm_st4<false>(dst, j, make_float4(o[0], o[1], o[2], o[3]));
             }
         }
     } else {
-        float4* dst = reinterpret_cast<float4*>(out + row * V);
+        float* dst = out + row * V;
 #pragma unroll
         for (int i = 0; i < LG_MAXVEC; ++i) {
             const int j = threadIdx.x + i * LG_THREADS;
             if (j < nvec) {
                 const float4 r = make_float4((v[i].x - mx) - ls, (v[i].y - mx) - ls, (v[i].z - mx) - ls,
                                              (v[i].w - mx) - ls);
-                if (RNNT_LG_NT & 2) rnnt_nt_store4(dst + j, r); else dst[j] = r;
+                if (RNNT_LG_NT & 2) lsm_st4<true>(dst, j, r); else lsm_st4<false>(dst, j, r);
             }
         }
     }
@@ -511,43 +560,43 @@ k_lsm_large(const float* x, float* out, const int* __restrict__ labels,
 // ---------------------------------------------------------------------------
 // Generic fallback (any V, any alignment): one wave per row, three passes.
 // ---------------------------------------------------------------------------
-template <int MODE>
+template <typename E, int MODE>
 __global__ void __launch_bounds__(256)
-k_lsm_generic(const float* x, float* out, const int* __restrict__ labels,
+k_lsm_generic(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
               int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
     constexpr bool GATHER = MODE == LSM_GATHER;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int lane = threadIdx.x & 63;
-    const float* xr = x + row * V;
+    const E* xr = x + row * V;
     float mx = -__builtin_inff();
-    for (int c = lane; c < V; c += WAVE) mx = fmaxf(mx, xr[c]);
+    for (int c = lane; c < V; c += WAVE) mx = fmaxf(mx, lsm_ld1(xr + c));
     mx = group_max<WAVE>(mx);
     float s = 0.0f;
-    for (int c = lane; c < V; c += WAVE) s += expf(xr[c] - mx);
+    for (int c = lane; c < V; c += WAVE) s += expf(lsm_ld1(xr + c) - mx);
     s = group_sum<WAVE>(s);
     const float ls = logf(s);
     if constexpr (GATHER) {
         if (lane == 0) {
             const CellMap m = map_cell((size_t)row, labels, T, U, V, blank);
             reinterpret_cast<float2*>(out)[m.sk] =
-                make_float2((xr[blank] - mx) - ls, (xr[m.label] - mx) - ls);
+                make_float2((lsm_ld1(xr + blank) - mx) - ls, (lsm_ld1(xr + m.label) - mx) - ls);
         }
     } else if constexpr (MODE == LSM_BWD) {
         const CellMap m = map_cell((size_t)row, labels, T, U, V, blank);
         const float sc = bw.scale ? bw.scale[m.n] : 1.0f;
         const float2 g = bw.g2[m.sk];
         const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
-        float* o = out + row * V;
+        LsmOut<MODE, E>* o = out + row * V;
         for (int c = lane; c < V; c += WAVE) {
-            float d = -expf((xr[c] - mx) - ls) * gs;
+            float d = -expf((lsm_ld1(xr + c) - mx) - ls) * gs;
             d += (c == blank) ? gB : 0.0f;
             d += (c == m.label) ? gL : 0.0f;
-            o[c] = d;
+            lsm_st1(o + c, d);
         }
     } else {
         float* o = out + row * V;
-        for (int c = lane; c < V; c += WAVE) o[c] = (xr[c] - mx) - ls;
+        for (int c = lane; c < V; c += WAVE) o[c] = (lsm_ld1(xr + c) - mx) - ls;
     }
 }
 
@@ -657,8 +706,8 @@ constexpr int RG_UN = RNNT_LSM_REGS_UN;   // groups per half and wave, loads fir
 #ifndef RNNT_LSM_REGS_NT
 #define RNNT_LSM_REGS_NT 3
 #endif
-template <int KR, int NT>
-__global__ void __launch_bounds__(256) k_lsm_regs(const float* __restrict__ x, float* __restrict__ out,
+template <typename E, int KR, int NT>
+__global__ void __launch_bounds__(256) k_lsm_regs(const E* __restrict__ x, float* __restrict__ out,
                                                   const int64_t ngroups, const int V, const int xcd) {
     const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
     const int g4 = (KR * V) >> 2;                  // float4 per group
@@ -682,7 +731,11 @@ __global__ void __launch_bounds__(256) k_lsm_regs(const float* __restrict__ x, f
         const int64_t g = (w * RG_UN + i) * 2 + half;
         const float ninf = -__builtin_inff();
         v[i] = lsm_f4{ninf, ninf, ninf, ninf};
-        if (act && g < ngroups) v[i] = (NT & 1) ? __builtin_nontemporal_load(xin + g * g4 + j) : xin[g * g4 + j];
+        if constexpr (std::is_same_v<E, float>) {
+            if (act && g < ngroups) v[i] = (NT & 1) ? __builtin_nontemporal_load(xin + g * g4 + j) : xin[g * g4 + j];
+        } else {
+            if (act && g < ngroups) { const float4 t = lsm_ld4<(NT & 1) != 0>(x, g * g4 + j); v[i] = lsm_f4{t.x, t.y, t.z, t.w}; }
+        }
     }
 #pragma unroll
     for (int i = 0; i < RG_UN; ++i) {
@@ -787,8 +840,8 @@ template <int L> struct RowsShape {
 
 // loads (all passes first), row maxima and log-sums of the rows at src[p] (one pointer per lane and pass: the lane's
 // first float4 of its row)
-template <int L, int Q, int MODE>
-__device__ __forceinline__ void lsm_rows_stats(const float* const (&src)[RowsShape<L>::UN], bool last_ok,
+template <typename E, int L, int Q, int MODE>
+__device__ __forceinline__ void lsm_rows_stats(const E* const (&src)[RowsShape<L>::UN], bool last_ok,
                                                float (&mx)[RowsShape<L>::UN], float (&ls)[RowsShape<L>::UN]) {
     constexpr int UN = RowsShape<L>::UN, VEC = 4;
     const float ninf = -__builtin_inff();
@@ -799,7 +852,7 @@ __device__ __forceinline__ void lsm_rows_stats(const float* const (&src)[RowsSha
 #pragma unroll
         for (int i = 0; i < Q; ++i) {
             const unsigned off = i < Q - 1 ? i * L : last_off;
-            const float4 t = RNNT_LSM_LOAD(reinterpret_cast<const float4*>(src[p]) + off);
+            const float4 t = lsm_ld4<RNNT_LSM_NT_MODE(MODE)>(src[p], off);
             v[p][i][0] = t.x; v[p][i][1] = t.y; v[p][i][2] = t.z; v[p][i][3] = t.w;
         }
     }
@@ -844,9 +897,9 @@ __device__ __forceinline__ void lsm_rows_stats_of_lane(int lane, const float (&m
 }
 
 // consecutive rows per wave
-template <int L, int Q>
+template <typename E, int L, int Q>
 __global__ void __launch_bounds__(256)
-k_lsm_rows(const float* x, float* out, const int* __restrict__ labels, int64_t rows, int V, int T, int U, int blank) {
+k_lsm_rows(const E* x, float* out, const int* __restrict__ labels, int64_t rows, int V, int T, int U, int blank) {
     constexpr int MODE = LSM_GATHER, VEC = 4;
     constexpr int UN = RowsShape<L>::UN, RW = RowsShape<L>::RW, RPW = RowsShape<L>::RPW;
     const int lane = threadIdx.x & 63, h = lane % L, rr = lane / L;
@@ -855,7 +908,7 @@ k_lsm_rows(const float* x, float* out, const int* __restrict__ labels, int64_t r
     if (row0 >= rows) return;
     const bool last_ok = (h + (Q - 1) * L) * VEC < V;   // the lane's last float4 is part of the row
     const bool whole = row0 + RPW <= rows;              // (uniform) every row of this wave exists
-    const float* const wave_src = x + row0 * V;
+    const E* const wave_src = x + row0 * V;
     const unsigned lane_off = (unsigned)rr * (unsigned)V + (unsigned)h * VEC;      // floats inside a pass
     // lane l < RPW owns the pair of row row0 + l.  Its two logits are requested FIRST, next to the row loads that bring
     // the same lines (asked for after the rows have streamed through, they are fetched a second time: forward 252 vs 216
@@ -865,11 +918,11 @@ k_lsm_rows(const float* x, float* out, const int* __restrict__ labels, int64_t r
     const bool own = lane < RPW && row0 + lane < rows;
     if (own) {
         cm = map_cell((size_t)(row0 + lane), labels, T, U, V, blank);
-        const float* xr = x + (row0 + lane) * V;
-        xb = xr[blank];
-        xl = xr[cm.label];
+        const E* xr = x + (row0 + lane) * V;
+        xb = lsm_ld1(xr + blank);
+        xl = lsm_ld1(xr + cm.label);
     }
-    const float* src[UN];
+    const E* src[UN];
 #pragma unroll
     for (int p = 0; p < UN; ++p) {
         src[p] = wave_src + (size_t)(p * RW) * V + lane_off;
@@ -877,7 +930,7 @@ k_lsm_rows(const float* x, float* out, const int* __restrict__ labels, int64_t r
         if (!whole && row0 + p * RW + rr >= rows) src[p] = x + (rows - 1) * V + h * VEC;
     }
     float mx[UN], ls[UN];
-    lsm_rows_stats<L, Q, MODE>(src, last_ok, mx, ls);
+    lsm_rows_stats<E, L, Q, MODE>(src, last_ok, mx, ls);
     float m, lg;
     lsm_rows_stats_of_lane<L>(lane, mx, ls, m, lg);
 #ifdef RNNT_LSM_ROWS_PROBE_LINEAR_STORE      // timing probe only (wrong layout): what the scattered 8-byte stores cost
@@ -893,9 +946,9 @@ k_lsm_rows(const float* x, float* out, const int* __restrict__ labels, int64_t r
 // bytes written per pair; with the pairs stored linearly the kernel is 12-17 us of 145 faster at V = 128, N*T*U = 1.6 M).
 // V = 32 / 64: forward 96.5 / 134 us against 102 / 144; from V = 96 on the scattered rows cost what the stores save (174
 // vs 177, 199 vs 193: consecutive rows kept there).  No index division: grid = (T / 4 rounded up, column blocks of 16, N).
-template <int Q>
+template <typename E, int Q>
 __global__ void __launch_bounds__(256)
-k_lsm_rows_diag(const float* x, float* out, const int* __restrict__ labels, int V, int T, int U, int blank) {
+k_lsm_rows_diag(const E* x, float* out, const int* __restrict__ labels, int V, int T, int U, int blank) {
     constexpr int L = 8, VEC = 4, MODE = LSM_GATHER;
     constexpr int UN = RowsShape<L>::UN, RW = RowsShape<L>::RW, RPW = RowsShape<L>::RPW;
     static_assert(RPW == 16, "one run of 16 pairs per wave");
@@ -913,11 +966,11 @@ k_lsm_rows_diag(const float* x, float* out, const int* __restrict__ labels, int 
         int t = tp - lane;
         t += t < 0 ? T : 0;
         const int lab = (u < U - 1) ? safe_label(labels[(size_t)n * (U - 1) + u], V, blank) : blank;
-        const float* xr = x + ((plane + t) * U + u) * V;
-        xb = xr[blank];
-        xl = xr[lab];
+        const E* xr = x + ((plane + t) * U + u) * V;
+        xb = lsm_ld1(xr + blank);
+        xl = lsm_ld1(xr + lab);
     }
-    const float* src[UN];
+    const E* src[UN];
 #pragma unroll
     for (int p = 0; p < UN; ++p) {
         const int k = p * RW + rr;
@@ -927,7 +980,7 @@ k_lsm_rows_diag(const float* x, float* out, const int* __restrict__ labels, int 
         src[p] = x + ((plane + t) * U + u) * V + h * VEC;
     }
     float mx[UN], ls[UN];
-    lsm_rows_stats<L, Q, MODE>(src, last_ok, mx, ls);
+    lsm_rows_stats<E, L, Q, MODE>(src, last_ok, mx, ls);
     float m, lg;
     lsm_rows_stats_of_lane<L>(lane, mx, ls, m, lg);
     int r = tp + u0;
@@ -945,13 +998,15 @@ static int lsm_regs_rows_per_group(int V) {
     return (best && (best * V) / 4 >= 20) ? best : 0;
 }
 
-template <int MODE>
-static hipError_t dispatch_lsm(hipStream_t stream, const float* x, float* out, const int* labels,
+// E: the storage type of x (and of out in LSM_BWD).  Every byte predicate of the routing is one of whole four-element
+// vectors (16 bytes of fp32, 8 of half), so a V takes the same kernel and the same lanes per row at every E.
+template <int MODE, typename E = float>
+static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const int* labels,
                                int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
     constexpr bool GATHER = MODE == LSM_GATHER;
     if (rows <= 0) return hipSuccess;
-    const bool aligned = (reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
-                         (GATHER || reinterpret_cast<uintptr_t>(out) % 16 == 0);
+    const bool aligned = (reinterpret_cast<uintptr_t>(x) % (4 * sizeof(E)) == 0) &&
+                         (GATHER || reinterpret_cast<uintptr_t>(out) % (4 * sizeof(*out)) == 0);
     if constexpr (MODE == LSM_NORM) {
         // rows in registers where the vocabulary allows it (RNNT_LSM_NO_REGS=1: the LDS-staged kernel, for A/B runs)
         static const bool no_regs = ab_getenv("RNNT_LSM_NO_REGS") != nullptr;
@@ -971,13 +1026,13 @@ static hipError_t dispatch_lsm(hipStream_t stream, const float* x, float* out, c
             if (regs_xcd) grid = (grid + 7) / 8 * 8;
             if (grid < ((int64_t)1 << 31)) {
 #define LSM_REGS(KR) \
-    case KR: k_lsm_regs<KR, RNNT_LSM_REGS_NT><<<(unsigned)grid, 256, 0, stream>>>(x, out, ngroups, V, regs_xcd); break;
+    case KR: k_lsm_regs<E, KR, RNNT_LSM_REGS_NT><<<(unsigned)grid, 256, 0, stream>>>(x, out, ngroups, V, regs_xcd); break;
                 switch (kr) { LSM_REGS(1) LSM_REGS(2) LSM_REGS(3) LSM_REGS(4) }
 #undef LSM_REGS
                 const hipError_t e = hipGetLastError();
-                const int64_t done = ngroups * kr;              // (a group boundary: 16-byte aligned)
+                const int64_t done = ngroups * kr;              // (a group boundary: vector aligned)
                 if (e != hipSuccess || done == rows) return e;
-                return dispatch_lsm<MODE>(stream, x + done * V, out + done * V, labels, rows - done, V, T, U, blank, bw);
+                return dispatch_lsm<MODE, E>(stream, x + done * V, out + done * V, labels, rows - done, V, T, U, blank, bw);
             }
         }
     }
@@ -992,7 +1047,7 @@ static hipError_t dispatch_lsm(hipStream_t stream, const float* x, float* out, c
         if (aligned && !no_lgr && V % 4 == 0 && V > 128 && V <= 1024) {
             const int nvec = V >> 2, th = (nvec + 63) / 64 * 64;
             const unsigned grid = (unsigned)(rows < (1 << 22) ? rows : (1 << 22));
-#define LGR(TH, NV) { k_lsm_large<MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw); return hipGetLastError(); }
+#define LGR(TH, NV) { k_lsm_large<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw); return hipGetLastError(); }
             if (nvec == 64) LGR(64, 1)
             if (nvec == 128) LGR(64, 2)
             if (nvec == 192) LGR(64, 3)
@@ -1033,15 +1088,15 @@ static hipError_t dispatch_lsm(hipStream_t stream, const float* x, float* out, c
             const int64_t N = rows / ((int64_t)T * U), nub = (U + 15) / 16;
             if (V <= 64 && V % 32 == 0 && T >= 16 && !no_diag && N <= 65535 && nub <= 65535) {
                 const dim3 grid((unsigned)((T + 3) / 4), (unsigned)nub, (unsigned)N);
-                if (q == 1) k_lsm_rows_diag<1><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
-                else k_lsm_rows_diag<2><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
+                if (q == 1) k_lsm_rows_diag<E, 1><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
+                else k_lsm_rows_diag<E, 2><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
                 return hipGetLastError();
             }
             const int64_t rpw = L <= 8 ? 2 * (WAVE / L) : WAVE / L;       // RowsShape<L>::RPW
             const int64_t grid = stream_grid<XCD_LSM_ROWS>((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
             if ((rows + 4 * rpw - 1) / (4 * rpw) < ((int64_t)1 << 31) - 8) {
 #define LSM_ROWS(LL, QQ) \
-    if (L == LL && q == QQ) k_lsm_rows<LL, QQ><<<(unsigned)grid, 256, 0, stream>>>(x, out, labels, rows, V, T, U, blank);
+    if (L == LL && q == QQ) k_lsm_rows<E, LL, QQ><<<(unsigned)grid, 256, 0, stream>>>(x, out, labels, rows, V, T, U, blank);
 #define LSM_ROWS_L(LL) LSM_ROWS(LL, 1) LSM_ROWS(LL, 2) LSM_ROWS(LL, 3) LSM_ROWS(LL, 4)
                 LSM_ROWS_L(8) LSM_ROWS_L(16) LSM_ROWS_L(32) LSM_ROWS_L(64)
 #undef LSM_ROWS_L
@@ -1058,7 +1113,7 @@ static hipError_t dispatch_lsm(hipStream_t stream, const float* x, float* out, c
 #endif
         const int q = (V + L - 1) / L;
         const int rpp = SM_THREADS / L;                // rows per pass, a multiple of 4
-        int R = (SM_FLOATS / V) / rpp * rpp;           // whole passes
+        int R = (sm_floats<E, MODE>() / V) / rpp * rpp;   // whole passes
         if (R < rpp) R = rpp;
         // wave-private tiles: each wave owns WAVE/L rows (a multiple of 4 for L <= 16), one pass
         static const bool no_wp = ab_getenv("RNNT_LSM_NO_WP") != nullptr;
@@ -1076,10 +1131,10 @@ static hipError_t dispatch_lsm(hipStream_t stream, const float* x, float* out, c
 #define LSM_SMALL(LL)                                                                           \
     case LL:                                                                                    \
         if (wp && LL <= 16)                                                                     \
-            k_lsm_small<LL, MODE, (LL <= 16)><<<grid, SM_THREADS, lds, stream>>>(x, out, labels, rows, V, R, q, \
+            k_lsm_small<E, LL, MODE, (LL <= 16)><<<grid, SM_THREADS, lds, stream>>>(x, out, labels, rows, V, R, q, \
                                                                                  T, U, blank, bw);             \
         else                                                                                    \
-            k_lsm_small<LL, MODE, false><<<grid, SM_THREADS, lds, stream>>>(x, out, labels, rows, V, R, q, T,   \
+            k_lsm_small<E, LL, MODE, false><<<grid, SM_THREADS, lds, stream>>>(x, out, labels, rows, V, R, q, T,   \
                                                                             U, blank, bw);                     \
         break;
         switch (L) {
@@ -1111,7 +1166,7 @@ static hipError_t dispatch_lsm(hipStream_t stream, const float* x, float* out, c
         if (const char* e = ab_getenv("RNNT_LG_VARIANT")) {
             int th = 0, nv = 0;
             sscanf(e, "%d,%d", &th, &nv);
-#define LGV(TH, NV) if (th == TH && nv == NV && V <= TH * 4 * NV) { k_lsm_large<MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw); return hipGetLastError(); }
+#define LGV(TH, NV) if (th == TH && nv == NV && V <= TH * 4 * NV) { k_lsm_large<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw); return hipGetLastError(); }
             LGV(64, 20) LGV(64, 40) LGV(128, 10) LGV(128, 20) LGV(256, 2) LGV(256, 4) LGV(256, 8) LGV(256, 16) LGV(512, 2) LGV(512, 4) LGV(512, 8) LGV(1024, 2) LGV(1024, 4)
 #undef LGV
         }
@@ -1128,18 +1183,18 @@ static hipError_t dispatch_lsm(hipStream_t stream, const float* x, float* out, c
             // The thread count is a template parameter on purpose (the same kernel with blockDim.x read at run
             // time: 780 us at V=5000).
             const int nvec = V >> 2;
-#define LGN(TH, NV) case TH: k_lsm_large<MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw); break;
+#define LGN(TH, NV) case TH: k_lsm_large<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw); break;
             if (nvec > 3072) {
-                k_lsm_large<MODE, 512, 8><<<grid, 512, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                k_lsm_large<E, MODE, 512, 8><<<grid, 512, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
             } else if (nvec > 2048) {
                 const int th = (nvec + 383) / 384 * 128;
                 switch (th) { LGN(768, 3) LGN(896, 3) LGN(1024, 3) }
             } else if (nvec > 1536) {
-                k_lsm_large<MODE, 1024, 2><<<grid, 1024, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                k_lsm_large<E, MODE, 1024, 2><<<grid, 1024, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
             } else if (nvec > 1408) {
-                k_lsm_large<MODE, 768, 2><<<grid, 768, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                k_lsm_large<E, MODE, 768, 2><<<grid, 768, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
             } else if (nvec > 1024) {
-                k_lsm_large<MODE, 512, 3><<<grid, 512, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                k_lsm_large<E, MODE, 512, 3><<<grid, 512, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
             } else {
                 int th = (nvec + 255) / 256 * 128;
                 th = th < 256 ? 256 : th;
@@ -1149,19 +1204,20 @@ static hipError_t dispatch_lsm(hipStream_t stream, const float* x, float* out, c
         } else {
             // read-mostly modes (fused gather, fused backward): the smallest cover, for the residency
             if (V <= 4096)
-                k_lsm_large<MODE, 256, 4><<<grid, 256, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                k_lsm_large<E, MODE, 256, 4><<<grid, 256, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
             else if (V <= 8192)
-                k_lsm_large<MODE, 256, 8><<<grid, 256, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                k_lsm_large<E, MODE, 256, 8><<<grid, 256, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
             else
-                k_lsm_large<MODE, 512, 8><<<grid, 512, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                k_lsm_large<E, MODE, 512, 8><<<grid, 512, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
         }
     } else {
-        k_lsm_generic<MODE><<<(unsigned)((rows + 3) / 4), 256, 0, stream>>>(x, out, labels, rows, V, T,
+        k_lsm_generic<E, MODE><<<(unsigned)((rows + 3) / 4), 256, 0, stream>>>(x, out, labels, rows, V, T,
                                                                              U, blank, bw);
     }
     return hipGetLastError();
 }
 
+#ifndef RNNT_PROLOGUE_LSM_ONLY      // (prologue_half.hip includes the log-softmax kernels above and nothing below)
 hipError_t launch_log_softmax(hipStream_t stream, const float* x, float* out, int64_t rows, int V) {
     return dispatch_lsm<LSM_NORM>(stream, x, out, nullptr, rows, V, 1, 1, 0, LsmBwd{nullptr, nullptr});
 }
@@ -2073,5 +2129,7 @@ hipError_t launch_compact_offsets(hipStream_t stream, const int* xn, const int* 
     k_compact_offsets<<<1, CP_THREADS, 0, stream>>>(xn, yn, N, cell_offs, label_offs, stats, bounds ? *bounds : none);
     return hipGetLastError();
 }
+
+#endif  // RNNT_PROLOGUE_LSM_ONLY
 
 }  // namespace rnnt

@@ -17,6 +17,12 @@ dtype, device, autograd history) but has not computed them.
     gradients add up in ``logits.grad`` as autograd's always do.
 
 ``log_softmax(x, lazy=False)`` is the eager function of rounds 2-5 (same kernels, an ordinary tensor at once).
+
+Half-precision logits (bf16 / fp16, e.g. a joint network under ``torch.autocast``) are taken as they are: the handle (and
+the eager result) is **fp32** -- what ``torch.log_softmax`` returns under autocast, and the only dtype every route of
+``rnnt_loss`` takes.  The fused route reads the half-precision logits themselves (2V+8 B/cell forward, 4V+8 backward) and
+gives ``logits.grad`` in their dtype; the materialised log-probs are those of ``x.float()`` bit for bit, and the gradient
+through them arrives in ``x.dtype`` as well.
 """
 import torch
 from torch.utils._pytree import tree_map
@@ -45,7 +51,8 @@ class LazyLogSoftmax(torch.Tensor):
     @staticmethod
     def __new__(cls, cell):
         x = cell.x
-        r = torch.Tensor._make_wrapper_subclass(cls, x.shape, dtype=x.dtype, device=x.device, requires_grad=False)
+        # (fp32 whatever the logits' dtype: what the kernels produce from bf16 / fp16 logits too)
+        r = torch.Tensor._make_wrapper_subclass(cls, x.shape, dtype=torch.float32, device=x.device, requires_grad=False)
         r._cell = cell
         r._src = None
         return r
@@ -89,7 +96,8 @@ class _LazyLogSoftmaxFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        return ops.log_softmax_backward(grad_out.contiguous(), ctx.cell.value())
+        g = ops.log_softmax_backward(grad_out.contiguous(), ctx.cell.value())
+        return g.to(ctx.cell.x.dtype)         # (bf16 / fp16 logits: the fp32 gradient rounded once)
 
 
 class _LogSoftmax(torch.autograd.Function):
@@ -98,20 +106,22 @@ class _LogSoftmax(torch.autograd.Function):
     def forward(ctx, x):
         y = ops.log_softmax(x.contiguous())
         ctx.save_for_backward(y)
+        ctx.x_dtype = x.dtype
         return y
 
     @staticmethod
     def backward(ctx, grad_out):
         y, = ctx.saved_tensors
-        return ops.log_softmax_backward(grad_out.contiguous(), y)
+        return ops.log_softmax_backward(grad_out.contiguous(), y).to(ctx.x_dtype)
 
 
 def log_softmax(x: torch.Tensor, lazy: bool = True) -> torch.Tensor:
-    """``torch.log_softmax(x, dim=-1)`` for fp32 GPU tensors.  ``lazy=True`` (default): the handle described in the
-    module docstring -- free until somebody other than ``rnnt_loss(..., gather=True)`` looks at it.  ``lazy=False``:
-    computed now (forward and backward in HIP, about 2x the speed of torch's own kernels at V=50 on MI355X)."""
-    if x.dtype != torch.float32 or not x.is_cuda:
-        raise RuntimeError("warp_rnnt_amd.functional.log_softmax needs an fp32 tensor on the GPU")
+    """``torch.log_softmax(x, dim=-1)`` for fp32, bf16 or fp16 GPU tensors; the result is fp32 in every case (module
+    docstring).  ``lazy=True`` (default): the handle described in the module docstring -- free until somebody other than
+    ``rnnt_loss(..., gather=True)`` looks at it.  ``lazy=False``: computed now (forward and backward in HIP, about 2x the
+    speed of torch's own kernels at V=50 on MI355X)."""
+    if x.dtype not in (torch.float32, torch.bfloat16, torch.float16) or not x.is_cuda:
+        raise RuntimeError("warp_rnnt_amd.functional.log_softmax needs an fp32 tensor on the GPU (or a bf16 / fp16 one)")
     if not lazy:
         return _LogSoftmax.apply(x)
     out = _LazyLogSoftmaxFn.apply(x)

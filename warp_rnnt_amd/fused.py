@@ -6,6 +6,10 @@ forward, and backward materialises a dense gradient w.r.t. them before the log-s
 turns it into a gradient w.r.t. the logits -- about 28V bytes of HBM traffic per lattice cell.
 Here forward reads the logits once (log-softmax + gather fused, 4V+8 B/cell) and backward reads them
 once more and writes d(logits) (8V B/cell); log-probabilities never exist in HBM.
+
+The logits may be fp32, bf16 or fp16 (what a joint network under ``torch.autocast`` produces): half-precision logits are
+converted to fp32 as the kernels load them, so the costs (fp32 at every dtype) are bit-equal to those of ``logits.float()``
+and d(logits) comes back in the logits' dtype, the fp32 result rounded once -- at half the bytes (2V+8 / 4V+8 B/cell).
 """
 from typing import Optional
 
@@ -15,11 +19,18 @@ from . import ops
 from warp_rnnt import _C as _core
 
 
+def check_logits_inputs(xs, ys, xn, yn):
+    """The reference's checks, in its order and with its texts (binding.cpp:32-51, warp_rnnt._C.check_inputs) -- except
+    that the logits may be fp32, bf16 or fp16.  (Without ``xs_dtypes`` check_inputs keeps asking for a Float tensor: the
+    reference-shaped op takes fp32 log-probs only.)"""
+    _core.check_inputs(xs, ys, xn, yn, xs_dtypes=tuple(ops.LOGITS_DTYPES))
+
+
 class RNNTLossFromLogits(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
-        _core.check_inputs(logits, labels, frames_lengths, labels_lengths)
+        check_logits_inputs(logits, labels, frames_lengths, labels_lengths)
         costs, grads = ops.loss(logits, labels, frames_lengths, labels_lengths, ops.IN_LOGITS_DENSE,
                                 ops.GRADS_GATHERED_DIAGONAL, blank, fastemit_lambda)
         ctx.save_for_backward(logits, labels, grads)
@@ -43,7 +54,7 @@ def rnnt_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, frames_len
     assert isinstance(blank, int)
     costs = RNNTLossFromLogits.apply(logits, labels, frames_lengths, labels_lengths, blank, fastemit_lambda)
     if average_frames:
-        costs = costs / frames_lengths.to(logits)
+        costs = costs / frames_lengths.to(costs)      # (fp32 costs: T_n rounded to bf16 would be 1499 -> 1496)
     if reduction == "none" or reduction is None:
         return costs
     if reduction == "sum":

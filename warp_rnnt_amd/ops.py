@@ -8,6 +8,14 @@ from . import _lib, _mismatch
 from ._lib import (GRADS_DENSE, GRADS_GATHERED, GRADS_GATHERED_DIAGONAL, GRADS_NONE,  # noqa: F401
                    IN_LOG_PROBS_DENSE, IN_LOG_PROBS_GATHERED, IN_LOGITS_DENSE, STATUS_NAMES)
 
+# element types the logits entries take (C ABI: RNNT_DTYPE_*); every other entry is fp32 only
+LOGITS_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+
+
+def _half(t):
+    """True for bf16 / fp16 tensors: served by the typed entries (fp32 arithmetic from the load on)."""
+    return t.dtype in (torch.bfloat16, torch.float16)
+
 
 def _ptr(t):
     return 0 if t is None else t.data_ptr()
@@ -34,7 +42,8 @@ def _mismatch_policy():
 
 def loss(input, labels, xn, yn, input_kind, grads_kind, blank=0, fastemit_lambda=0.0, return_mismatch=False):
     """costs (N,), grads (layout per grads_kind; None for GRADS_NONE) [, mismatch (N,) int32].
-    Tensors must be validated by the caller (contiguous, fp32/int32, same GPU).  ``mismatch[n]`` is 1
+    Tensors must be validated by the caller (contiguous, fp32/int32, same GPU; IN_LOGITS_DENSE also takes bf16 / fp16
+    logits -- costs and gradient pairs stay fp32).  ``mismatch[n]`` is 1
     where the forward/backward consistency guard zeroed an utterance's gradients (or its lengths were
     out of range); without asking for it the same event surfaces as a RuntimeWarning a little later, with no
     synchronisation (warp_rnnt_amd/_mismatch.py)."""
@@ -64,9 +73,14 @@ def loss(input, labels, xn, yn, input_kind, grads_kind, blank=0, fastemit_lambda
                                f"N={N} T={T} U={U}")
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
         _mismatch.poll(dev)          # (what an EARLIER call's kernels reported; sets the device's words up at first use)
-        st = L.rnnt_amd_loss(_stream(dev), ws.data_ptr(), input_kind, input.data_ptr(), _ptr(labels),
-                             xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(grads), grads_kind,
-                             N, T, U, V, blank, float(fastemit_lambda))
+        if input_kind == IN_LOGITS_DENSE and _half(input):
+            st = L.rnnt_amd_loss_logits(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[input.dtype], input.data_ptr(),
+                                        _ptr(labels), xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(grads),
+                                        grads_kind, N, T, U, V, blank, float(fastemit_lambda))
+        else:
+            st = L.rnnt_amd_loss(_stream(dev), ws.data_ptr(), input_kind, input.data_ptr(), _ptr(labels),
+                                 xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(grads), grads_kind,
+                                 N, T, U, V, blank, float(fastemit_lambda))
         _check(st)
         policy = _mismatch_policy()
         if policy not in ("warn", "raise", "1", "on"):
@@ -119,7 +133,10 @@ _NATIVE = False
 
 
 def log_softmax(x, out=None):
-    """Row-wise log-softmax over the last axis (fp32, contiguous, GPU). ``out`` may be ``x``."""
+    """Row-wise log-softmax over the last axis (contiguous, GPU). ``out`` may be ``x``.  fp32 in, fp32 out; bf16 / fp16
+    in, fp32 out (bit-equal to the fp32 call on ``x.float()``; ``out`` must then be a separate fp32 tensor)."""
+    if _half(x):
+        return _log_softmax_half(x, out)
     nb = _native_binding()
     if nb is not None:
         return nb.log_softmax(x, out)
@@ -131,6 +148,22 @@ def log_softmax(x, out=None):
     rows = x.numel() // max(V, 1)
     with torch.cuda.device(x.device):
         _check(L.rnnt_amd_log_softmax(_stream(x.device), x.data_ptr(), out.data_ptr(), rows, V))
+    return out
+
+
+def _log_softmax_half(x, out=None):
+    L = _lib.load()
+    if not (x.is_cuda and x.is_contiguous()):
+        raise RuntimeError("log_softmax: x must be a contiguous tensor on the GPU")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if not (out.is_contiguous() and out.dtype == torch.float32 and out.shape == x.shape and out.device == x.device):
+        raise RuntimeError("log_softmax: out must be a contiguous float32 tensor like x (bf16 / fp16 input)")
+    V = x.shape[-1] if x.dim() else 1
+    rows = x.numel() // max(V, 1)
+    with torch.cuda.device(x.device):
+        _check(L.rnnt_amd_log_softmax_typed(_stream(x.device), LOGITS_DTYPES[x.dtype], x.data_ptr(), out.data_ptr(),
+                                            rows, V))
     return out
 
 
@@ -218,7 +251,8 @@ def compact_scatter_grads(grad_cost, grad_xs, cum_lens, loc, V, blank):
 
 
 def logits_backward(logits, labels, grads_diagonal, grad_costs, blank=0, out=None):
-    """d(sum_n grad_costs[n]*cost[n]) / d(logits) for the fused RNNT_IN_LOGITS_DENSE path."""
+    """d(sum_n grad_costs[n]*cost[n]) / d(logits) for the fused RNNT_IN_LOGITS_DENSE path, in the logits' dtype (fp32,
+    bf16 or fp16: the fp32 result rounded once)."""
     L = _lib.load()
     N, T, U, V = logits.shape
     dev = logits.device
@@ -227,9 +261,16 @@ def logits_backward(logits, labels, grads_diagonal, grad_costs, blank=0, out=Non
             out = torch.empty_like(logits)
         if N == 0:
             return out
-        _check(L.rnnt_amd_logits_backward(_stream(dev), logits.data_ptr(), _ptr(labels),
-                                          grads_diagonal.data_ptr(), _ptr(grad_costs), out.data_ptr(),
-                                          N, T, U, V, blank))
+        if _half(logits):
+            if out.dtype != logits.dtype:
+                raise RuntimeError("logits_backward: out must have the logits' dtype")
+            _check(L.rnnt_amd_logits_backward_typed(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
+                                                    _ptr(labels), grads_diagonal.data_ptr(), _ptr(grad_costs),
+                                                    out.data_ptr(), N, T, U, V, blank))
+        else:
+            _check(L.rnnt_amd_logits_backward(_stream(dev), logits.data_ptr(), _ptr(labels),
+                                              grads_diagonal.data_ptr(), _ptr(grad_costs), out.data_ptr(),
+                                              N, T, U, V, blank))
     return out
 
 
