@@ -135,7 +135,7 @@ def test_results_do_not_depend_on_timing_or_workspace_contents():
 def test_cells_outside_an_utterance_never_reach_a_result(N, T, U, poison):
     """Ragged batch with every pair OUTSIDE an utterance's own (T_n, U_n) lattice poisoned.  The hand-written blocks run
     unpredicated: lanes compute on before their first frame (head blocks), behind their last (since round 6 the blocks
-    lanes finish in run the steady-state code too, csrc/lattice_wd_body.h: RNNT_WD_FAST_TAIL) and in columns beyond U_n --
+    lanes finish in run the steady-state code too, csrc/lattice_wd_body.h: sweep(), full_end) and in columns beyond U_n --
     on whatever the planes hold there.  None of it may reach a cost, a gradient, or the forward/backward check: the same
     bits as the single-workgroup kernel on the clean batch, from every kernel and both block sizes' default route."""
     logits, labels, xn, yn = make_case(77 + N + T + U, N, T, U, 5, ragged=True)

@@ -449,6 +449,29 @@ def test_the_build_refuses_a_planted_reload_violation(monkeypatch):
             assert f.read() == g.read()
 
 
+def test_compile_time_switches_are_the_kept_builds_only():
+    """Every RNNT_* macro the native sources test in a preprocessor conditional belongs to a build that has a user: the
+    four _build.VARIANTS, the diagnostics build of tools/wd_trace.py (RNNT_WD_STATS) and the half-precision translation
+    unit (RNNT_PROLOGUE_LSM_ONLY).  A new experiment switch is added here on purpose or goes through ab_getenv (common.h)."""
+    from warp_rnnt_amd import _build
+    allowed = {"RNNT_AB_KNOBS", "RNNT_WD_SPIN_LIMIT", "RNNT_LATTICE_LEGACY", "RNNT_PRECISE_LIBM",
+               "RNNT_PLANT_RELOAD_VIOLATION", "RNNT_WD_STATS", "RNNT_PROLOGUE_LSM_ONLY"}
+    found = {}
+    for d in (_build.CSRC, os.path.join(ROOT, "include")):
+        for name in sorted(os.listdir(d)):
+            if not name.endswith((".h", ".hip", ".cpp")):
+                continue
+            with open(os.path.join(d, name)) as f:
+                text = f.read().replace("\\\n", " ")
+            conds = re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)$", text, re.M)
+            conds += re.findall(r"\bdefined\s*\(?\s*(RNNT_\w+)", text)
+            for c in conds:
+                for m in re.findall(r"\bRNNT_\w+", c):
+                    found.setdefault(m, name)
+    assert set(found) == allowed, {m: found.get(m) for m in set(found) ^ allowed}
+    assert set(_build.VARIANTS) == {"precise", "short_spin", "ab", "planted_violation"}
+
+
 def test_the_build_refuses_inline_assembly_stores_of_more_than_64_bits(tmp_path):
     """gfx950: a VMEM store of more than 64 bits reads its data registers up to two wait states after it issues; the compiler
     pads its own, not one inside `asm` (found by tools/ubench/lsm_store_policy.hip's bit check in round 6).  The build

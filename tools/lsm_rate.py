@@ -14,23 +14,9 @@ cases = [(50, g) for g in (0.36, 0.72, 1.44, 2.88, 5.76)] + [(5000, g) for g in 
         [(10000, g) for g in (1.92, 3.84)] + [(1000, 1.92), (2048, 1.92), (4096, 1.92), (8192, 1.92)]
 if len(sys.argv) > 1:
     cases = [(int(a.split(":")[0]), float(a.split(":")[1])) for a in sys.argv[1:]]
-# LG_VARIANTS="640,2 320,4 ...": with a -DRNNT_LG_PROBE build (WARP_RNNT_AMD_LIB, WARP_RNNT_AMD_NO_NATIVE_BINDING=1) every
-# case is run once per "threads,float4-per-thread" cover of the row-per-workgroup kernel (RNNT_LG_VARIANT, read per call)
-variants = os.environ.get("LG_VARIANTS", "").split() or [None]
-chunks = os.environ.get("XCD_CHUNKS", "").split() or [None]      # RNNT_XCD_CHUNK values (probe build): XCD run lengths
-cases = [(V, gb, v, c) for V, gb in cases for v in variants for c in chunks]
 backward = bool(os.environ.get("LSM_BACKWARD"))               # time ops.log_softmax_backward (three streams) instead
 inplace = bool(os.environ.get("LSM_INPLACE"))                 # out = x (how c5 runs: 144 GB of logits leave no room for a copy)
-for V, gb, variant, chunk in cases:
-    if chunk is not None:
-        os.environ["RNNT_XCD_CHUNK"] = chunk
-        print(f"[xcd run {chunk:>5s}] ", end="")
-    if variant is not None:
-        th, nv = (int(t) for t in variant.split(","))
-        if V > th * 4 * nv or V % 4:
-            continue
-        os.environ["RNNT_LG_VARIANT"] = variant
-        print(f"[{variant:>8s}] ", end="")
+for V, gb in cases:
     rows = int(gb * 1e9 / 4 / V)
     x = torch.randn(rows, V, device=dev)
     out = x if inplace else torch.empty_like(x)

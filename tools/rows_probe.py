@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Times the row-wide kernels (log-softmax, its backward, the dense expansion) at (N,T,U,V) with HIP events and
-checks them against torch. Usage: rows_probe.py N T U V    (RNNT_LSM_NO_SHIFT=1 selects the unshifted lane map)"""
+checks them against torch. Usage: rows_probe.py N T U V"""
 import os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -36,8 +36,7 @@ def timed(name, fn, nbytes):
           f"{nbytes / (statistics.median(ts) * 1e-6) / 1e12:.2f} TB/s (median)", flush=True)
 
 
-tag = "unshifted" if os.environ.get("RNNT_LSM_NO_SHIFT") else "line-aligned"
-print(f"N={N} T={T} U={U} V={V} ({x.numel() * 4 / 1e9:.2f} GB per tensor), {tag}")
+print(f"N={N} T={T} U={U} V={V} ({x.numel() * 4 / 1e9:.2f} GB per tensor)")
 timed("log_softmax", lambda: ops.log_softmax(x, y), x.numel() * 8)
 ref = torch.log_softmax(x[0, :8], -1)
 print("   err", (y[0, :8] - ref).abs().max().item())

@@ -69,26 +69,9 @@ VARIANTS = {
     # hand-over waits that give up at once: every column block that catches up with its neighbour flags its sweep
     # for the kernel behind (the "producer lost" path, which never triggers otherwise)
     "short_spin": ["-DRNNT_WD_SPIN_LIMIT=0"],
-    # A/B of k_lattice_wl's wave placement: six waves in column-block-major order / compute waves at raised priority
-    "wl_nopad": ["-DRNNT_WL_PAD=0"],
-    "wl_noprio": ["-DRNNT_WL_PRIO=0"],
     # the build that reads the kernel-selection knobs of DESIGN.md section 10 from the environment (common.h: ab_getenv); the
     # probes under tools/ load it through WARP_RNNT_AMD_LIB -- the shipped library ignores those variables
     "ab": ["-DRNNT_AB_KNOBS"],
-    # A/B: the dense gather's pair stores left dirty in L2 (rounds 1-5) instead of written through (sc1)
-    "gather_plain_stores": ["-DRNNT_GATHER_STORE_SC1=0"],
-    # A/B: the blocks of k_lattice_wd / k_lattice_wl in which lanes finish in the predicated C++ form (rounds 4-6) instead of
-    # the hand-written steady-state code
-    "wd_masked_tail": ["-DRNNT_WD_FAST_TAIL=0"],
-    # A/B: the register log-softmax kernel's row maxima by fmaxf() on DPP results (rounds 3-5) instead of v_max_f32_dpp
-    "lsm_regs_c_max": ["-DRNNT_LSM_REGS_ASM_MAX=0"],
-    # A/B: ... its results stored straight from the registers (400-byte segments at V=50) instead of in address order via LDS
-    "lsm_regs_direct": ["-DRNNT_LSM_REGS_LINEAR=0"],
-    "lsm_regs_r05": ["-DRNNT_LSM_REGS_LINEAR=0", "-DRNNT_LSM_REGS_ASM_MAX=0"],
-    "lsm_regs_nt_stores": ["-DRNNT_LSM_REGS_STORE_WT=0"],
-    # timing probes of the fused logits -> pairs kernel's stores (WRONG results: tools/fused_store_probe.py only)
-    "probe_hot_pairs": ["-DRNNT_PROBE_HOT_PAIRS"],
-    "probe_linear_pairs": ["-DRNNT_PROBE_LINEAR_PAIRS"],
     # a build that MUST FAIL: the hand-written blocks end with two of their in-place reloads still in flight -- the bug
     # class of round 5; tests/test_host_cpu.py checks that build() refuses it (warp_rnnt_amd/_isa_check.py)
     "planted_violation": ["-DRNNT_PLANT_RELOAD_VIOLATION"],

@@ -63,17 +63,14 @@ __device__ __forceinline__ float readlane(float v, int lane) {
 // Which chunk of a streaming kernel's work an XCD takes.  Workgroups go to the eight XCDs by blockIdx mod 8: with
 // chunk = blockIdx every XCD works on every eighth chunk of one moving front; stream_block() renumbers the workgroups so
 // that XCD k streams the k-th contiguous eighth (grid = stream_grid(chunks): a multiple of 8; renumbered blocks beyond the
-// last chunk return).  Per kernel family, bit of RNNT_XCD_STREAM (measured per family: profiles/r04_lsm_xcd_order_ab.txt).
-#ifndef RNNT_XCD_STREAM
-#define RNNT_XCD_STREAM 15      // all four: c4, three interleaved pairs against -DRNNT_XCD_STREAM=0: fused forward 0.467 -> 0.464 ms,
-#endif                          // fused training step 0.978 -> 0.963, native log-softmax chain 1.86 -> 1.82, run_warp_rnnt 0.893 -> 0.879
-enum : int { XCD_LSM_SMALL = 1, XCD_EXPAND_SMALL = 2, XCD_LSMBWD_SMALL = 4, XCD_LSM_ROWS = 8 };
-template <int FAMILY> __device__ __forceinline__ unsigned stream_block() {
-    if constexpr ((RNNT_XCD_STREAM & FAMILY) != 0) return (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    else return blockIdx.x;
+// last chunk return).  Every family streams this way (measured per family: profiles/r04_lsm_xcd_order_ab.txt; all four
+// at c4, three interleaved pairs against chunk = blockIdx: fused forward 0.467 -> 0.464 ms, fused training step
+// 0.978 -> 0.963, native log-softmax chain 1.86 -> 1.82, run_warp_rnnt 0.893 -> 0.879).
+__device__ __forceinline__ unsigned stream_block() {
+    return (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
 }
-template <int FAMILY> inline unsigned stream_grid(unsigned chunks) {
-    return (RNNT_XCD_STREAM & FAMILY) != 0 ? (chunks + 7u) & ~7u : chunks;
+inline unsigned stream_grid(unsigned chunks) {
+    return (chunks + 7u) & ~7u;
 }
 
 struct UttLens {

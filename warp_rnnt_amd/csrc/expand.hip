@@ -25,19 +25,12 @@
 
 namespace rnnt {
 
-// cache policy of the dense-row writes (a pure writer of 4V bytes per cell): 1 = non-temporal stores (round 3: the
+// cache policy of the dense-row writes (a pure writer of 4V bytes per cell): non-temporal stores (round 3: the
 // gather=True training step through the native log-softmax function 1.96 -> 1.90 ms at c4, profiles/r03_bwd_nt_ab.txt)
-#ifndef RNNT_EX_NT
-#define RNNT_EX_NT 1
-#endif
 typedef float ex_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void ex_store4(float4* p, float4 v) {
-    if (RNNT_EX_NT) {
-        const ex_f4 w = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(w, reinterpret_cast<ex_f4*>(p));
-    } else {
-        *p = v;
-    }
+    const ex_f4 w = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(w, reinterpret_cast<ex_f4*>(p));
 }
 
 struct ExpandCell {
@@ -179,7 +172,7 @@ __global__ void __launch_bounds__(EX_THREADS)
 k_expand_small(const Rows rows, float* __restrict__ dense, unsigned cells, int R, int V, int blank) {
     extern __shared__ __attribute__((aligned(16))) float tile[];
     const int tid = threadIdx.x;
-    const unsigned blk = stream_block<XCD_EXPAND_SMALL>();
+    const unsigned blk = stream_block();
     if ((unsigned long long)blk * (unsigned)R >= cells) return;
     const unsigned cell0 = blk * (unsigned)R;
     const int nrows = (int)min((unsigned)R, cells - cell0);
@@ -229,7 +222,7 @@ static hipError_t launch_rows(hipStream_t stream, const Rows& rows, float* dense
         int R = (EX_FLOATS / V) / 4 * 4;          // R % 4 == 0 keeps every tile start 16-byte aligned
         if (R < 4) R = 4;
         const size_t lds = (size_t)R * V * sizeof(float);
-        k_expand_small<Rows><<<stream_grid<XCD_EXPAND_SMALL>((cells + R - 1) / R), EX_THREADS, lds, stream>>>(rows, dense, cells, R,
+        k_expand_small<Rows><<<stream_grid((cells + R - 1) / R), EX_THREADS, lds, stream>>>(rows, dense, cells, R,
                                                                                                        V, blank);
     } else {
         const unsigned grid = cells < (1u << 22) ? cells : (1u << 22);

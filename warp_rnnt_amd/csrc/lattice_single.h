@@ -13,25 +13,13 @@
 namespace rnnt {
 namespace single {
 
-#ifndef RNNT_K
-#define RNNT_K 8
-#endif
-constexpr int K = RNNT_K;     // diagonals per block (= inter-wave lag)
-// Register ring of NB blocks: log-probs are prefetched NB-1 blocks ahead (24 diagonals for the
+constexpr int K = 8;          // diagonals per block (= inter-wave lag)
+// Register ring of four blocks: log-probs are prefetched three blocks ahead (24 diagonals for the
 // diagonal-major loader: an L2-miss/MALL round trip is ~1 us, a block ~0.3 us).  The two
 // reference-layout loaders need 64-bit addresses per load and keep a 2-deep ring.
-#ifndef RNNT_STORE_AUX
-#define RNNT_STORE_AUX 0
-#endif
-#ifndef RNNT_NB
-#define RNNT_NB 4
-#endif
-template <int LOADER> constexpr int ring_depth() { return LOADER == LOAD_SKEWED ? RNNT_NB : 2; }
+template <int LOADER> constexpr int ring_depth() { return LOADER == LOAD_SKEWED ? 4 : 2; }
 constexpr int RING = 4 * K;   // mailbox ring entries per wave boundary
-#ifndef RNNT_MAXW
-#define RNNT_MAXW 16
-#endif
-constexpr int MAXW = RNNT_MAXW;   // waves per workgroup
+constexpr int MAXW = 16;      // waves per workgroup
 constexpr int MAIL_TRASH = WAVE + K;   // per-wave dump area for the lanes that are not lane 63
 
 struct Cell { float b, l; };  // blank / label log-prob of one lattice cell
@@ -126,25 +114,19 @@ __device__ __forceinline__ void run_block(const Cell (&cur)[K], const float mvec
             RNNT_PIN();
         }
         if (k > 0) {
-#ifndef RNNT_PROBE_NOSTORE
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, pval), rs_out, pvoff, soff[k - 1], RNNT_STORE_AUX);
-#endif
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, pval), rs_out, pvoff, soff[k - 1], 0);
             RNNT_PIN();
         }
         if (k == K) {
-#ifndef RNNT_PROBE_NOMAIL
             if constexpr (MAIL) mail_slot[k - 1] = pX;
-#endif
             break;
         }
         float emit;
         if constexpr (BETA) { emit = left + cur[k].l; } else { emit = left; skip = Y; }   // chain
         RNNT_PIN();
         if (k > 0) {
-#ifndef RNNT_PROBE_NOMAIL
             // only lane 63's pointer aims at the mailbox, the others at a dump area
             if constexpr (MAIL) mail_slot[k - 1] = pX;
-#endif
             RNNT_PIN();
         }
         // ---- lse(skip, emit), see common.h ----
@@ -166,16 +148,14 @@ __device__ __forceinline__ void run_block(const Cell (&cur)[K], const float mvec
 #if defined(RNNT_PRECISE_LIBM)
         float val = mx + log1pf(expf(-__builtin_fabsf(t)));
         (void)l2;
-#elif !defined(RNNT_LSE_UNCORRECTED)
+#else
+        // (max + ln2*log2(1+e) in one fma, the rounding of 1+e left uncorrected, was 4 % faster but pushed gradients
+        // past the 1e-4 parity bar at T=150,U=40 -- not used)
         const float c = e - (u - 1.0f);                                                // shadow
         RNNT_PIN();
         const float l = __builtin_fmaf(l2, 0.693147180559945309417f, c);               // chain
         RNNT_PIN();
         float val = mx + l;                                                            // chain
-#else
-        // Probe only: max + ln2*log2(1+e) in one fma, rounding of 1+e left uncorrected.  4 % faster,
-        // but pushes gradients past the 1e-4 parity bar at T=150,U=40 -- not used.
-        float val = __builtin_fmaf(l2, 0.693147180559945309417f, mx);                  // chain
 #endif
         RNNT_PIN();
         // the rim of the lattice is plain sums in the reference, not lse (lattice_step.h: a -inf there must stay -inf,
@@ -348,14 +328,12 @@ __device__ __forceinline__ void sweep(const LatticeArgs& a, const int n, float (
                                                      T, U, mail_slot);
                 }
             }
-#ifndef RNNT_PROBE_NOBARRIER
             if (nwa > 1) {
                 // LDS-only release/acquire around the barrier: global prefetches stay in flight.
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
             }
-#endif
         };
 
         auto barrier_only = [&]() {

@@ -84,9 +84,7 @@ __device__ __forceinline__ void compute_block(const f32x2 (&cur)[K], const float
             // beta: the value of the previous diagonal is published, then extended by this cell's
             // blank log-prob -- both read `Y` and sit between its producer and the DPP below
             if (k > 0) {
-#ifndef RNNT_WS_NOVAL
                 vslot[(k - 1) * WAVE] = pval;
-#endif
                 RNNT_PIN();
             }
             skip = Y + cur[k].x;
@@ -138,9 +136,7 @@ __device__ __forceinline__ void compute_block(const f32x2 (&cur)[K], const float
         } else {
             Xn = val + cur[k].y;                                                       // chain (feeds the DPP)
             RNNT_PIN();
-#ifndef RNNT_WS_NOVAL
             vslot[k * WAVE] = val;
-#endif
             RNNT_PIN();
             Yn = val + cur[k].x;
             RNNT_PIN();
@@ -156,9 +152,7 @@ __device__ __forceinline__ void compute_block(const f32x2 (&cur)[K], const float
         if constexpr (MAIL) { mail_slot[k] = X; RNNT_PIN(); }
     }
     if constexpr (BETA) {
-#ifndef RNNT_WS_NOVAL
         vslot[(K - 1) * WAVE] = pval;
-#endif
     }
 #undef RNNT_PIN
 }

@@ -219,7 +219,7 @@ int wl_max_blocks() {
     // RNNT_WL_MAX_BLOCKS = 0 ... 5 overrides (0: the kernel is never chosen), for A/B runs.
     static const int v = [] {
         const char* e = ab_getenv("RNNT_WL_MAX_BLOCKS");
-        const int d = e ? atoi(e) : RNNT_WL_DEFAULT_MAX_BLOCKS;
+        const int d = e ? atoi(e) : 5;
         return d < 0 ? 0 : (d > 5 ? 5 : d);
     }();
     return v;
@@ -230,7 +230,7 @@ hipError_t launch_lattice_wl(hipStream_t stream, const LatticeArgs& a, int N, in
     const int nA = (a.U + WAVE - 1) / WAVE;
     const size_t lds = sizeof(wd8::Smem) * nA;
     if (nA > max_blocks || nA > 5 || lds > 160 * 1024) return hipErrorNotSupported;
-    const dim3 grid(2 * N), block((RNNT_WL_PAD && nA == 2 ? 8 : 3 * nA) * WAVE);
+    const dim3 grid(2 * N), block((nA == 2 ? 8 : 3 * nA) * WAVE);
     const bool compact = is_compact(a);
     const bool wide = nA > 2;                           // which instantiation (launch bounds: 512 / 960 threads)
     const void* fn = wide ? (compact ? reinterpret_cast<const void*>(&wd8::k_lattice_wl<true, 5>)

@@ -18,10 +18,7 @@ using ws::RSRC_WORD3;
 using ws::OOB;
 constexpr int TRASH = WAVE + K;
 
-#ifndef RNNT_WD_DLOAD
-#define RNNT_WD_DLOAD 2
-#endif
-constexpr int DLOAD = RNNT_WD_DLOAD;   // the loader fetches a block this many intervals before the compute wave reads it
+constexpr int DLOAD = 2;               // the loader fetches a block this many intervals before the compute wave reads it
 constexpr int PSLOTS = DLOAD + 4;      // LDS ring of pair blocks: fetched DLOAD intervals before the compute wave's first
                                        // read, kept until the storer has taken the last column's label log-probs (3 later)
 constexpr int VSLOTS = 2;              // LDS ring of value blocks
@@ -32,22 +29,7 @@ static_assert(DLOAD >= 2 && DLOAD + 2 <= MIN_SLOTS, "ring depths");
 #define RNNT_WD_SPIN_LIMIT (1 << 21)
 #endif
 constexpr int SPIN_LIMIT = RNNT_WD_SPIN_LIMIT;   // polls before a hand-over is declared lost (seconds)
-#ifndef RNNT_WD_LAG
-#define RNNT_WD_LAG 1
-#endif
-#ifndef RNNT_WD_FAST_TAIL
-#define RNNT_WD_FAST_TAIL 1    // the blocks lanes finish in run the hand-written steady-state code (sweep(): full_end)
-#endif
-#ifndef RNNT_WL_PAD
-#define RNNT_WL_PAD 1          // two column blocks: eight waves, the compute waves alone on their SIMDs (k_lattice_wl)
-#endif
-#ifndef RNNT_WL_PRIO
-#define RNNT_WL_PRIO 2         // s_setprio of the compute waves of k_lattice_wl from three column blocks on, where they
-#endif                         // share SIMDs with loaders and storers (N=16, T=1500, U=300: 142 -> 137 us; nothing at two)
-#ifndef RNNT_WL_DEFAULT_MAX_BLOCKS
-#define RNNT_WL_DEFAULT_MAX_BLOCKS 5
-#endif
-constexpr int LAG = RNNT_WD_LAG; // blocks a column block lets its left neighbour get ahead once it has caught up with it
+constexpr int LAG = 1;           // blocks a column block lets its left neighbour get ahead once it has caught up with it
 
 typedef unsigned long long u64;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -90,11 +72,7 @@ __device__ __forceinline__ i32x4 make_rsrc(const void* p, unsigned bytes) {
 // there: nothing the compiler generates for these waves reads M0.
 __device__ __forceinline__ void dma16(const int voff, const i32x4 rs, const int soff, unsigned lds) {
     lds = __builtin_amdgcn_readfirstlane(lds);
-#ifdef RNNT_WD_DMA_ALL_SC1
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen sc1 lds" ::"v"(voff), "s"(rs), "s"(soff), "s"(lds) : "memory");
-#else
     asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(rs), "s"(soff), "s"(lds) : "memory");
-#endif
 }
 __device__ __forceinline__ void dma16_agent(const int voff, const i32x4 rs, unsigned lds) {   // agent scope (sc1)
     lds = __builtin_amdgcn_readfirstlane(lds);
@@ -332,7 +310,6 @@ __device__ __forceinline__ void sweep(const LatticeArgs& a, const Item it, const
             lb = lo;
             // (a lattice so short that lanes start and finish in the same blocks: everything in the general variant)
             head_end = fb0 < fb1 ? fb0 : lo; full_end = fb0 < fb1 ? fb1 : lo; tail_end = hi;
-#if RNNT_WD_FAST_TAIL
             // The blocks lanes FINISH in (none starts: they lie behind fb0) run the steady-state code as well.  What a lane
             // computes behind its last frame reaches no result: the storer predicates the stores of every block outside
             // [sfb0, sfb1) per lane; its right neighbour's last live cell (row T_n - 1, one diagonal later) reads the lane's
@@ -342,7 +319,6 @@ __device__ __forceinline__ void sweep(const LatticeArgs& a, const Item it, const
             // the loop -- and that lane finishes on the sweep's very last diagonal: the last block of the last column block
             // of an alpha sweep stays in the general variant, nothing else.
             if (fb0 < fb1) full_end = max(fb1, (!BETA && idx == nwa - 1) ? hi - 1 : hi);
-#endif
         }
         int slot = 0;                                          // LDS slot of block lb's pairs (block lo = slot 0)
         const unsigned pairs0 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)&sm.pairs[0][0][pos];
@@ -560,7 +536,7 @@ __global__ void __launch_bounds__((NA_MAX == 2 ? 8 : 3 * NA_MAX) * WAVE) k_latti
     // other two.  From three column blocks on the compute waves cannot all be alone: column-block-major order.
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int idx, role, nA;
-    if (RNNT_WL_PAD && NA_MAX == 2 && blockDim.x == 8 * WAVE) {
+    if (NA_MAX == 2 && blockDim.x == 8 * WAVE) {
         if (w == 4 || w == 5) return;
         nA = 2;
         idx = (w == 1 || w >= 6) ? 1 : 0;
@@ -569,7 +545,9 @@ __global__ void __launch_bounds__((NA_MAX == 2 ? 8 : 3 * NA_MAX) * WAVE) k_latti
         idx = w / 3; role = w - 3 * idx;
         nA = blockDim.x / (3 * WAVE);
     }
-    if (RNNT_WL_PRIO && role == 0 && nA >= 3) __builtin_amdgcn_s_setprio(RNNT_WL_PRIO);   // (the dependent chain first)
+    // From three column blocks on, the compute waves run at raised priority (the dependent chain first): there they share
+    // SIMDs with loaders and storers (N=16, T=1500, U=300: 142 -> 137 us; nothing at two)
+    if (role == 0 && nA >= 3) __builtin_amdgcn_s_setprio(2);
     Item it;
     it.n = (int)n; it.dir = (int)dir; it.cb = idx;
     if (len.Un == 1) {                                 // no labels: one wave's prefix / suffix sums (uniform, no barrier)

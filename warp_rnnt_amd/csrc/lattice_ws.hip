@@ -113,7 +113,6 @@ __device__ __forceinline__ void sweep(const LatticeArgs& a, const int n, Smem* s
         auto io_step = [&](const int p, auto ph, auto guarded) {
             constexpr int PH = decltype(ph)::value;           // p mod NBR
             constexpr bool GUARDED = decltype(guarded)::value;
-#ifndef RNNT_WS_NOIO
             if (!GUARDED || (p >= lo && p < hi)) {
                 f32x2* dst = &sm.pairs[p % PSLOTS][0][lane];
 #pragma unroll
@@ -133,7 +132,6 @@ __device__ __forceinline__ void sweep(const LatticeArgs& a, const int n, Smem* s
                 }
             }
             if (!GUARDED || (p + DLOAD >= lo && p + DLOAD < hi)) load_block(regs[(PH + DLOAD) % NBR]);
-#endif
             block_barrier();
         };
         auto io_any = [&](const int p, auto guarded) {        // dispatch on p mod NBR
@@ -158,9 +156,7 @@ __device__ __forceinline__ void sweep(const LatticeArgs& a, const int n, Smem* s
         // registers they filled, and it would make the first step of EVERY iteration wait for (nearly) everything in
         // flight -- a memory round trip every third block (round 4: `vmcnt(3)` at the loop head in the ISA).  With a
         // known-empty queue here only the loop's own back edge decides, and that one it counts exactly.
-#ifndef RNNT_WS_NO_DRAIN
         __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
-#endif
         for (; p + NBR <= ps1; p += NBR) {
             io_step(p, std::integral_constant<int, 0>{}, std::false_type{});
             io_step(p + 1, std::integral_constant<int, 1>{}, std::false_type{});
@@ -173,9 +169,6 @@ __device__ __forceinline__ void sweep(const LatticeArgs& a, const int n, Smem* s
     }
 
     // ------------------------------ compute wave ------------------------------
-#ifdef RNNT_WS_PRIO
-    __builtin_amdgcn_s_setprio(3);   // the dependent chain is the critical path; I/O waves yield
-#endif
     float Y = (ucol == 0) ? 0.0f : NEG_INF;
     float X = NEG_INF;
     f32x2 bufA[K], bufB[K];

@@ -12,7 +12,6 @@
 // Output of the gather kernels is the diagonal-major float2 workspace
 // (common.h) that the lattice sweep reads with coalesced row loads.
 #include <climits>
-#include <cstdio>
 #include <cstdlib>
 #include <algorithm>
 
@@ -79,7 +78,7 @@ __device__ __forceinline__ CellMap map_cell(size_t cell, const int* __restrict__
 // Cache policy of the LDS-staged kernel's 16-byte global loads and stores: non-temporal in the fused modes (gather:
 // a read-only stream of the logits; backward: logits in, d/d logits out -- fused forward 0.472 -> 0.464 ms, fused
 // training step 1.00 -> 0.975 ms at c4, profiles/r03_bwd_nt_ab.txt), plain for the log-softmax itself, where the
-// hints measured nothing to worse in rounds 1-2 (HISTORY.md).  -DRNNT_LSM_NT forces them everywhere (A/B builds).
+// hints measured nothing to worse in rounds 1-2 (HISTORY.md).
 // Written-through stores (sc1 / sc1 nt; round 6, after the dense gather gained from them): nothing at c4 in any mode of this
 // kernel, c3's row-per-workgroup kernel 0.658 -> 0.73-0.76 ms, the register kernel 480 -> 520-580 us -- they pay only where
 // every store instruction covers whole 128-byte lines (profiles/r06_lsm_store_policy.txt).
@@ -100,11 +99,7 @@ template <bool NT> __device__ __forceinline__ void lsm_store4(float4* p, float4 
         *p = v;
     }
 }
-#ifdef RNNT_LSM_NT
-#define RNNT_LSM_NT_MODE(MODE) true
-#else
 #define RNNT_LSM_NT_MODE(MODE) ((MODE) != LSM_NORM)
-#endif
 #define RNNT_LSM_LOAD(p) lsm_load4<RNNT_LSM_NT_MODE(MODE)>(p)
 #define RNNT_LSM_STORE(p, v) lsm_store4<RNNT_LSM_NT_MODE(MODE)>(p, v)
 
@@ -154,14 +149,8 @@ struct LsmBwd {
     int xcd;             // row-per-workgroup kernel: 1 = every XCD streams a contiguous eighth of the rows
 };
 
-#ifndef RNNT_SM_THREADS
-#define RNNT_SM_THREADS 256
-#endif
-constexpr int SM_THREADS = RNNT_SM_THREADS;
-#ifndef RNNT_SM_FLOATS
-#define RNNT_SM_FLOATS 3200
-#endif
-constexpr int SM_FLOATS = RNNT_SM_FLOATS;   // LDS tile budget in floats: one pass of the 256 threads over a 12.5 KiB tile.  (512 threads x 25 KiB: 2 % faster in the isolated probe, slower in bench.py and in the fused gather mode; two passes per tile or 50 KiB tiles are clearly worse.)
+constexpr int SM_THREADS = 256;
+constexpr int SM_FLOATS = 3200;   // LDS tile budget in floats: one pass of the 256 threads over a 12.5 KiB tile.  (512 threads x 25 KiB: 2 % faster in the isolated probe, slower in bench.py and in the fused gather mode; two passes per tile or 50 KiB tiles are clearly worse.)
 // In the fused gather the shared tile of half-precision logits holds twice the rows: 12.8 KB of HBM per tile, as for fp32
 // (c4, bf16: 178 -> 172 us; the fused backward, which also writes the tile back, 287 -> 290 us with it and keeps the
 // fp32 row count).  Rows per tile do not touch the bits: the lanes of a row and its reduction tree stay the same.
@@ -189,7 +178,7 @@ k_lsm_small(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
     extern __shared__ __attribute__((aligned(16))) float tile[];
     float2* stat = reinterpret_cast<float2*>(tile + (size_t)R * V);   // GATHER: (max, log-sum) per row
     const int tid = threadIdx.x;
-    const int64_t row0 = (int64_t)stream_block<XCD_LSM_SMALL>() * R;
+    const int64_t row0 = (int64_t)stream_block() * R;
     if (row0 >= rows) return;
     const int nrows = (int)min((int64_t)R, rows - row0);
     const int nel = nrows * V;                      // floats in this chunk
@@ -355,14 +344,10 @@ k_lsm_small(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
             const float2 st = stat[r];
             const float* row = tile + r * V;
             const float2 pr = make_float2((row[blank] - st.x) - st.y, (row[m.label] - st.x) - st.y);
-#ifdef RNNT_PROBE_HOT_PAIRS     // timing probe (wrong results): the pairs into a 64 KB region that stays in L2 -- what the
-                                // kernel costs without its DRAM writes (the gather's stores cost 40-55 us in any shape)
-            reinterpret_cast<float2*>(out)[m.sk & 8191] = pr;
-#elif defined(RNNT_PROBE_LINEAR_PAIRS)   // ... and with the pairs in row-major order (coalesced 512-byte runs; wrong layout)
-            reinterpret_cast<float2*>(out)[row0 + r] = pr;
-#else
-            reinterpret_cast<float2*>(out)[m.sk] = pr;      // (written through, sc1: +38 us at c4 -- scattered 8-byte stores need L2 to merge them)
-#endif
+            // (written through, sc1: +38 us at c4 -- scattered 8-byte stores need L2 to merge them.  Timing probes that sent
+            // the pairs into a 64 KB region that stays in L2, or stored them in row-major order as coalesced 512-byte runs:
+            // the gather's stores cost 40-55 us in any shape)
+            reinterpret_cast<float2*>(out)[m.sk] = pr;
         }
     } else if constexpr (WP) {
         wave_sync_lds();
@@ -401,16 +386,11 @@ k_lsm_small(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
 // picks 1.25-2.5 float4 per thread for the plain log-softmax and the smallest cover for the read-mostly fused modes
 // (dispatch_lsm).
 constexpr int LG_MAXV = 16384;
-// cache policy of the plain (LSM_NORM) row-per-workgroup stream: bit 0 = non-temporal loads, bit 1 = non-temporal stores.
+// cache policy of the plain (LSM_NORM) row-per-workgroup stream: non-temporal loads and non-temporal stores.
 // Both (round 3; round 1 had tried them on the LDS-staged small-V kernel only, where they do nothing): c5 (V=10000, in
 // place, 288 GB of traffic) 57.4 -> 51.3 ms per step, c3 (V=5000) 0.708 -> 0.695 ms; loads alone are WORSE (c3 0.733),
-// stores alone neutral (profiles/r03_lg_nt_ab.txt)
-#ifndef RNNT_LG_NT
-#define RNNT_LG_NT 3
-#endif
-#ifndef RNNT_LG_NT_FUSED      // the same policy in the fused gather / backward modes: c3 fused forward 0.336 -> 0.325 ms,
-#define RNNT_LG_NT_FUSED 1    // fused training step 1.051 -> 1.018 ms (profiles/r03_lg_fused_nt_ab.txt)
-#endif
+// stores alone neutral (profiles/r03_lg_nt_ab.txt).  The same policy in the fused gather / backward modes: c3 fused forward
+// 0.336 -> 0.325 ms, fused training step 1.051 -> 1.018 ms (profiles/r03_lg_fused_nt_ab.txt)
 typedef float lg_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 rnnt_nt_load4(const float4* p) {
     const lg_f4 v = __builtin_nontemporal_load(reinterpret_cast<const lg_f4*>(p));
@@ -461,7 +441,6 @@ k_lsm_large(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
     //     behind them), so those take the predicated form and everything else stays as it was.
     constexpr bool CLAMPED = MODE != LSM_NORM;
     constexpr bool PREDICATED = MODE == LSM_NORM && LG_THREADS >= 768;
-    constexpr bool NT_LOADS = (((MODE == LSM_NORM ? 1 : RNNT_LG_NT_FUSED) * RNNT_LG_NT) & 1) != 0;
     float4 v[LG_MAXVEC];
     float mx = -__builtin_inff();
     if constexpr (CLAMPED || PREDICATED) {
@@ -469,9 +448,9 @@ k_lsm_large(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
         for (int i = 0; i < LG_MAXVEC; ++i) {
             const int j = (int)threadIdx.x + i * LG_THREADS;
             if constexpr (CLAMPED) {
-                v[i] = NT_LOADS ? lsm_ld4<true>(src, min(j, nvec - 1)) : lsm_ld4<false>(src, min(j, nvec - 1));
+                v[i] = lsm_ld4<true>(src, min(j, nvec - 1));
             } else {
-                if (j < nvec) v[i] = NT_LOADS ? lsm_ld4<true>(src, j) : lsm_ld4<false>(src, j);
+                if (j < nvec) v[i] = lsm_ld4<true>(src, j);
             }
         }
     }
@@ -500,7 +479,7 @@ k_lsm_large(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
             mx = fmaxf(fmaxf(mx, fmaxf(v[i].x, v[i].y)), fmaxf(v[i].z, v[i].w));
         } else {
             if (j < nvec) {
-                v[i] = NT_LOADS ? lsm_ld4<true>(src, j) : lsm_ld4<false>(src, j);
+                v[i] = lsm_ld4<true>(src, j);
                 mx = fmaxf(fmaxf(mx, fmaxf(v[i].x, v[i].y)), fmaxf(v[i].z, v[i].w));
             }
         }
@@ -538,8 +517,7 @@ k_lsm_large(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
                     d += (e == m.label) ? gL : 0.0f;
                     o[cc] = d;
                 }
-                if ((RNNT_LG_NT_FUSED * RNNT_LG_NT) & 2) lsm_st4<true>(dst, j, make_float4(o[0], o[1], o[2], o[3]));
-                else lsm_st4<false>(dst, j, make_float4(o[0], o[1], o[2], o[3]));
+                lsm_st4<true>(dst, j, make_float4(o[0], o[1], o[2], o[3]));
             }
         }
     } else {
@@ -550,7 +528,7 @@ k_lsm_large(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
             if (j < nvec) {
                 const float4 r = make_float4((v[i].x - mx) - ls, (v[i].y - mx) - ls, (v[i].z - mx) - ls,
                                              (v[i].w - mx) - ls);
-                if (RNNT_LG_NT & 2) lsm_st4<true>(dst, j, r); else lsm_st4<false>(dst, j, r);
+                lsm_st4<true>(dst, j, r);
             }
         }
     }
@@ -617,11 +595,6 @@ template <int CTRL> __device__ __forceinline__ float lsm_dpp(float v) {
 __device__ __forceinline__ float lsm_swz16(float v) {   // lane ^ 16 inside each 32-lane half
     return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));
 }
-__device__ __forceinline__ float half_max32(float v) {
-    v = fmaxf(v, lsm_dpp<0xB1>(v)); v = fmaxf(v, lsm_dpp<0x4E>(v)); v = fmaxf(v, lsm_dpp<0x124>(v));
-    v = fmaxf(v, lsm_dpp<0x128>(v));
-    return fmaxf(v, lsm_swz16(v));
-}
 __device__ __forceinline__ float half_sum32(float v) {
     v += lsm_dpp<0xB1>(v); v += lsm_dpp<0x4E>(v); v += lsm_dpp<0x124>(v); v += lsm_dpp<0x128>(v);
     return v + lsm_swz16(v);
@@ -642,22 +615,12 @@ __device__ __forceinline__ float half_sum32(float v) {
 // In the step (bench.py, c4, interleaved processes, profiles/r06_lsm_regs_ab.txt): 0.7997 -> 0.7924 ms on one box, 0.8418 ->
 // 0.8323 on another; and with the stores then also written through AND streaming (sc1 nt: whole granules that nothing
 // else will add to -- the case in which write-through pays) 0.8323 -> 0.8267.  Blocks of four groups per
-// half (RNNT_LSM_REGS_UN=4) lose 20 us.
-#ifndef RNNT_LSM_REGS_LINEAR
-#define RNNT_LSM_REGS_LINEAR 1
-#endif
-#ifndef RNNT_LSM_REGS_STORE_WT
-#define RNNT_LSM_REGS_STORE_WT RNNT_LSM_REGS_LINEAR
-#endif
-#ifndef RNNT_LSM_REGS_ASM_MAX
-#define RNNT_LSM_REGS_ASM_MAX 1
-#endif
+// half lose 20 us.
 #define RNNT_DPPMAX(R, CTRL) "v_max_f32_dpp " R ", " R ", " R " " CTRL " row_mask:0xf bank_mask:0xf\n\t"
 #define RNNT_DPPMAX_STEPS(BODY, GAP)                                                                     \
     "s_nop 1\n\t" BODY("quad_perm:[1,0,3,2]") GAP BODY("quad_perm:[2,3,0,1]") GAP BODY("row_ror:4") GAP BODY("row_ror:8")
 template <int KR> __device__ __forceinline__ void half_max32_rows(float (&M)[KR]) {
     static_assert(KR >= 1 && KR <= 4, "one to four rows per group");
-#if RNNT_LSM_REGS_ASM_MAX
     float t0, t1, t2, t3;
     if constexpr (KR == 1) {
 #define RNNT_B1(C) RNNT_DPPMAX("%0", C)
@@ -690,32 +653,21 @@ template <int KR> __device__ __forceinline__ void half_max32_rows(float (&M)[KR]
                      : "+v"(M[0]), "+v"(M[1]), "+v"(M[2]), "+v"(M[3]), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3));
 #undef RNNT_B4
     }
-#else
-#pragma unroll
-    for (int r = 0; r < KR; ++r) M[r] = half_max32(M[r]);
-#endif
 }
 #undef RNNT_DPPMAX_STEPS
 #undef RNNT_DPPMAX
-#ifndef RNNT_LSM_REGS_UN
-#define RNNT_LSM_REGS_UN 2
-#endif
-constexpr int RG_UN = RNNT_LSM_REGS_UN;   // groups per half and wave, loads first (1: 500 us, 2: 462-484, 4: 482-498)
+constexpr int RG_UN = 2;   // groups per half and wave, loads first (1: 500 us, 2: 462-484, 4: 482-498)
 
-// NT: bit 0 = non-temporal loads, bit 1 = non-temporal stores (both: 462 us for the c4 tensor, neither: 484)
-#ifndef RNNT_LSM_REGS_NT
-#define RNNT_LSM_REGS_NT 3
-#endif
+// NT: bit 0 = non-temporal loads, bit 1 = non-temporal stores (both: 462 us for the c4 tensor, neither: 484); the launch
+// passes 3, and the stores leave through the strip written through and streaming
 template <typename E, int KR, int NT>
 __global__ void __launch_bounds__(256) k_lsm_regs(const E* __restrict__ x, float* __restrict__ out,
                                                   const int64_t ngroups, const int V, const int xcd) {
     const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
     const int g4 = (KR * V) >> 2;                  // float4 per group
     const bool act = j < g4;
-#if RNNT_LSM_REGS_LINEAR
     __shared__ lsm_f4 strip[4][64 * RG_UN];        // per wave: its 2 * RG_UN groups of <= 32 float4 in address order
     const int wv = threadIdx.x >> 6;
-#endif
     // xcd: the eight XCDs (blockIdx mod 8; the grid is a multiple of 8) each stream a contiguous eighth of the groups
     const unsigned wg = xcd ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
     const int64_t w = (int64_t)wg * 4 + (threadIdx.x >> 6);
@@ -739,7 +691,6 @@ __global__ void __launch_bounds__(256) k_lsm_regs(const E* __restrict__ x, float
     }
 #pragma unroll
     for (int i = 0; i < RG_UN; ++i) {
-        [[maybe_unused]] const int64_t g = (w * RG_UN + i) * 2 + half;
         const lsm_f4 t = v[i];
         const float ninf = -__builtin_inff();
         // maxima of the lane's two parts, then of every row of the group over the half
@@ -778,13 +729,8 @@ __global__ void __launch_bounds__(256) k_lsm_regs(const E* __restrict__ x, float
                                   ns > 1 ? (t.y - m_first) - l_first : (t.y - m_second) - l_second,
                                   ns > 2 ? (t.z - m_first) - l_first : (t.z - m_second) - l_second,
                                   ns > 3 ? (t.w - m_first) - l_first : (t.w - m_second) - l_second};
-#if RNNT_LSM_REGS_LINEAR
         if (act) strip[wv][(2 * i + half) * g4 + j] = res;
-#else
-        if (act && g < ngroups) { if (NT & 2) __builtin_nontemporal_store(res, xout + g * g4 + j); else xout[g * g4 + j] = res; }
-#endif
     }
-#if RNNT_LSM_REGS_LINEAR
     // the wave's 2 * RG_UN groups are 64 * g4 contiguous bytes: out of the strip in address order, one store instruction of
     // 1024 bytes and one of the rest -- every instruction whole 64-byte granules (the strip is the wave's own: no barrier)
     wave_sync_lds();
@@ -795,14 +741,10 @@ __global__ void __launch_bounds__(256) k_lsm_regs(const E* __restrict__ x, float
         const int f = k * 64 + lane;
         if (f < nw && f0 + f < nf) {
             const lsm_f4 r = strip[wv][f];
-#if RNNT_LSM_REGS_STORE_WT      // written through and streaming (the s_nop: _isa_check.py, second rule)
+            // written through and streaming (the s_nop: _isa_check.py, second rule)
             asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(xout + f0 + f), "v"(r) : "memory");
-#else
-            if (NT & 2) __builtin_nontemporal_store(r, xout + f0 + f); else xout[f0 + f] = r;
-#endif
         }
     }
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -904,7 +846,7 @@ k_lsm_rows(const E* x, float* out, const int* __restrict__ labels, int64_t rows,
     constexpr int UN = RowsShape<L>::UN, RW = RowsShape<L>::RW, RPW = RowsShape<L>::RPW;
     const int lane = threadIdx.x & 63, h = lane % L, rr = lane / L;
     // wave-uniform values kept in scalar registers (the 64-bit row arithmetic runs on the scalar unit)
-    const int64_t row0 = ((int64_t)stream_block<XCD_LSM_ROWS>() * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * RPW;
+    const int64_t row0 = ((int64_t)stream_block() * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * RPW;
     if (row0 >= rows) return;
     const bool last_ok = (h + (Q - 1) * L) * VEC < V;   // the lane's last float4 is part of the row
     const bool whole = row0 + RPW <= rows;              // (uniform) every row of this wave exists
@@ -933,11 +875,7 @@ k_lsm_rows(const E* x, float* out, const int* __restrict__ labels, int64_t rows,
     lsm_rows_stats<E, L, Q, MODE>(src, last_ok, mx, ls);
     float m, lg;
     lsm_rows_stats_of_lane<L>(lane, mx, ls, m, lg);
-#ifdef RNNT_LSM_ROWS_PROBE_LINEAR_STORE      // timing probe only (wrong layout): what the scattered 8-byte stores cost
-    if (own) reinterpret_cast<float2*>(out)[row0 + lane] = make_float2((xb - m) - lg, (xl - m) - lg);
-#else
     if (own) reinterpret_cast<float2*>(out)[cm.sk] = make_float2((xb - m) - lg, (xl - m) - lg);
-#endif
 }
 
 // Along the diagonals (rows that are one or two whole 128-byte lines: V = 32, 64; T >= 16): a wave takes the 16 cells
@@ -1026,7 +964,7 @@ static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* 
             if (regs_xcd) grid = (grid + 7) / 8 * 8;
             if (grid < ((int64_t)1 << 31)) {
 #define LSM_REGS(KR) \
-    case KR: k_lsm_regs<E, KR, RNNT_LSM_REGS_NT><<<(unsigned)grid, 256, 0, stream>>>(x, out, ngroups, V, regs_xcd); break;
+    case KR: k_lsm_regs<E, KR, 3><<<(unsigned)grid, 256, 0, stream>>>(x, out, ngroups, V, regs_xcd); break;
                 switch (kr) { LSM_REGS(1) LSM_REGS(2) LSM_REGS(3) LSM_REGS(4) }
 #undef LSM_REGS
                 const hipError_t e = hipGetLastError();
@@ -1093,7 +1031,7 @@ static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* 
                 return hipGetLastError();
             }
             const int64_t rpw = L <= 8 ? 2 * (WAVE / L) : WAVE / L;       // RowsShape<L>::RPW
-            const int64_t grid = stream_grid<XCD_LSM_ROWS>((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
+            const int64_t grid = stream_grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
             if ((rows + 4 * rpw - 1) / (4 * rpw) < ((int64_t)1 << 31) - 8) {
 #define LSM_ROWS(LL, QQ) \
     if (L == LL && q == QQ) k_lsm_rows<E, LL, QQ><<<(unsigned)grid, 256, 0, stream>>>(x, out, labels, rows, V, T, U, blank);
@@ -1108,9 +1046,6 @@ static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* 
     if (aligned && V <= 1024) {
         int L = 1;
         while (L < 64 && L * 16 < V) L <<= 1;          // <= 16 columns per lane
-#ifdef RNNT_LG_PROBE
-        if (const char* e = ab_getenv("RNNT_LSM_L")) { const int l = atoi(e); if (l >= 1 && l <= 64 && (l & (l - 1)) == 0) L = l; }
-#endif
         const int q = (V + L - 1) / L;
         const int rpp = SM_THREADS / L;                // rows per pass, a multiple of 4
         int R = (sm_floats<E, MODE>() / V) / rpp * rpp;   // whole passes
@@ -1123,11 +1058,8 @@ static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* 
         static const bool wp_fused = ab_getenv("RNNT_LSM_WP_FUSED") != nullptr;      // (A/B: the wave-private form in the fused modes)
         const bool wp = (L <= 16) && !no_wp && (MODE == LSM_NORM || wp_fused);
         if (wp) R = rpp;
-        size_t lds = (size_t)R * V * sizeof(float) + (GATHER ? (size_t)R * sizeof(float2) : 0);
-#ifdef RNNT_LG_PROBE      // probe: fewer resident workgroups per CU (LDS the kernel does not use)
-        if (const char* e = ab_getenv("RNNT_LSM_LDS")) { const size_t want = (size_t)atoi(e); if (want > lds && want <= 65536) lds = want; }
-#endif
-        const unsigned grid = stream_grid<XCD_LSM_SMALL>((unsigned)((rows + R - 1) / R));
+        const size_t lds = (size_t)R * V * sizeof(float) + (GATHER ? (size_t)R * sizeof(float2) : 0);
+        const unsigned grid = stream_grid((unsigned)((rows + R - 1) / R));
 #define LSM_SMALL(LL)                                                                           \
     case LL:                                                                                    \
         if (wp && LL <= 16)                                                                     \
@@ -1162,15 +1094,6 @@ static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* 
         }
         unsigned grid = (unsigned)(rows < (1 << 22) ? rows : (1 << 22));
         if (bw.xcd) grid = (grid + 7u) & ~7u;
-#ifdef RNNT_LG_PROBE
-        if (const char* e = ab_getenv("RNNT_LG_VARIANT")) {
-            int th = 0, nv = 0;
-            sscanf(e, "%d,%d", &th, &nv);
-#define LGV(TH, NV) if (th == TH && nv == NV && V <= TH * 4 * NV) { k_lsm_large<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw); return hipGetLastError(); }
-            LGV(64, 20) LGV(64, 40) LGV(128, 10) LGV(128, 20) LGV(256, 2) LGV(256, 4) LGV(256, 8) LGV(256, 16) LGV(512, 2) LGV(512, 4) LGV(512, 8) LGV(1024, 2) LGV(1024, 4)
-#undef LGV
-        }
-#endif
         if constexpr (MODE == LSM_NORM) {
             // The read + write stream wants about two float4 per thread and (nearly) every thread busy in every pass;
             // workgroups of 512 or 1024 threads (which tile a CU's 2048 exactly) beat the sizes in between.  Round 2
@@ -1236,14 +1159,9 @@ hipError_t launch_logits_backward(hipStream_t stream, const float* logits, const
 }
 
 // ---------------------------------------------------------------------------
-// cache policy of the log-softmax backward streams: bit 0 = non-temporal loads (dy, y), bit 1 = non-temporal stores (dx)
+// cache policy of the log-softmax backward streams: non-temporal loads (dy, y) and non-temporal stores (dx).
 // Both (round 3): the reference's call chain with the native log-softmax autograd function 1.96 -> 1.89 ms per training
 // step at c4 (with the expand kernel's non-temporal stores on top: 1.84), profiles/r03_bwd_nt_ab.txt.
-#ifndef RNNT_LSMB_NT
-#define RNNT_LSMB_NT 3
-#endif
-#define LSMB_LD(p) ((RNNT_LSMB_NT & 1) ? rnnt_nt_load4(p) : *(p))
-#define LSMB_ST(p, v) do { if (RNNT_LSMB_NT & 2) rnnt_nt_store4((p), (v)); else *(p) = (v); } while (0)
 
 // Backward of log-softmax: dx = dy - exp(y) * sum_v(dy), y = the log-probabilities.
 // Same three shapes as the forward kernels (LDS row tiles / one row per workgroup in
@@ -1258,15 +1176,15 @@ k_lsmbwd_small(const float* dy, const float* y, float* dx, int64_t rows, int V, 
     float* tdy = tile;
     float* ty = tile + (size_t)R * V;
     const int tid = threadIdx.x;
-    const int64_t row0 = (int64_t)stream_block<XCD_LSMBWD_SMALL>() * R;
+    const int64_t row0 = (int64_t)stream_block() * R;
     if (row0 >= rows) return;
     const int nrows = (int)min((int64_t)R, rows - row0);
     const int nel = nrows * V, nvec = nel >> 2;
     const float* sdy = dy + row0 * V;
     const float* sy = y + row0 * V;
     for (int i = tid; i < nvec; i += SMB_THREADS) {
-        reinterpret_cast<float4*>(tdy)[i] = LSMB_LD(reinterpret_cast<const float4*>(sdy) + i);
-        reinterpret_cast<float4*>(ty)[i] = LSMB_LD(reinterpret_cast<const float4*>(sy) + i);
+        reinterpret_cast<float4*>(tdy)[i] = rnnt_nt_load4(reinterpret_cast<const float4*>(sdy) + i);
+        reinterpret_cast<float4*>(ty)[i] = rnnt_nt_load4(reinterpret_cast<const float4*>(sy) + i);
     }
     for (int e = (nvec << 2) + tid; e < nel; e += SMB_THREADS) { tdy[e] = sdy[e]; ty[e] = sy[e]; }
     __syncthreads();
@@ -1315,7 +1233,7 @@ k_lsmbwd_small(const float* dy, const float* y, float* dx, int64_t rows, int V, 
     __syncthreads();
     float* dst = dx + row0 * V;
     for (int i = tid; i < nvec; i += SMB_THREADS)
-        LSMB_ST(reinterpret_cast<float4*>(dst) + i, reinterpret_cast<const float4*>(tdy)[i]);
+        rnnt_nt_store4(reinterpret_cast<float4*>(dst) + i, reinterpret_cast<const float4*>(tdy)[i]);
     for (int e = (nvec << 2) + tid; e < nel; e += SMB_THREADS) dst[e] = tdy[e];
 }
 
@@ -1336,7 +1254,7 @@ k_lsmbwd_large(const float* dy, const float* y, float* dx, int64_t rows, int V, 
 #pragma unroll
         for (int i = 0; i < LG_MAXVEC; ++i) {
             const int j = threadIdx.x + i * LG_THREADS;
-            if (j < nvec) { g[i] = LSMB_LD(sdy + j); s += (g[i].x + g[i].y) + (g[i].z + g[i].w); }
+            if (j < nvec) { g[i] = rnnt_nt_load4(sdy + j); s += (g[i].x + g[i].y) + (g[i].z + g[i].w); }
         }
         s = block_reduce<LG_THREADS>(s, false, red);
         float4* dst = reinterpret_cast<float4*>(dx + row * V);
@@ -1344,11 +1262,11 @@ k_lsmbwd_large(const float* dy, const float* y, float* dx, int64_t rows, int V, 
         for (int i = 0; i < LG_MAXVEC; ++i) {
             const int j = threadIdx.x + i * LG_THREADS;
             if (j < nvec) {
-                const float4 p = LSMB_LD(sy + j);
-                LSMB_ST(dst + j, make_float4(__builtin_fmaf(-__builtin_amdgcn_exp2f(p.x * LOG2E), s, g[i].x),
-                                             __builtin_fmaf(-__builtin_amdgcn_exp2f(p.y * LOG2E), s, g[i].y),
-                                             __builtin_fmaf(-__builtin_amdgcn_exp2f(p.z * LOG2E), s, g[i].z),
-                                             __builtin_fmaf(-__builtin_amdgcn_exp2f(p.w * LOG2E), s, g[i].w)));
+                const float4 p = rnnt_nt_load4(sy + j);
+                rnnt_nt_store4(dst + j, make_float4(__builtin_fmaf(-__builtin_amdgcn_exp2f(p.x * LOG2E), s, g[i].x),
+                                                    __builtin_fmaf(-__builtin_amdgcn_exp2f(p.y * LOG2E), s, g[i].y),
+                                                    __builtin_fmaf(-__builtin_amdgcn_exp2f(p.z * LOG2E), s, g[i].z),
+                                                    __builtin_fmaf(-__builtin_amdgcn_exp2f(p.w * LOG2E), s, g[i].w)));
             }
         }
     }
@@ -1380,7 +1298,7 @@ hipError_t launch_log_softmax_backward(hipStream_t stream, const float* dy, cons
         int R = (SMB_FLOATS / V) / 4 * 4;
         if (R < 4) R = 4;
         const size_t lds = (size_t)R * V * sizeof(float) * 2;
-        const unsigned grid = stream_grid<XCD_LSMBWD_SMALL>((unsigned)((rows + R - 1) / R));
+        const unsigned grid = stream_grid((unsigned)((rows + R - 1) / R));
 #define LSMB_SMALL(LL) case LL: k_lsmbwd_small<LL><<<grid, SMB_THREADS, lds, stream>>>(dy, y, dx, rows, V, R, q); break;
         switch (L) { LSMB_SMALL(1) LSMB_SMALL(2) LSMB_SMALL(4) LSMB_SMALL(8) LSMB_SMALL(16) LSMB_SMALL(32) LSMB_SMALL(64) }
 #undef LSMB_SMALL
@@ -1433,21 +1351,12 @@ constexpr int TD = 32;   // tile edge
 // the end of a freshly written 1.44 GB tensor in 22 us, from its beginning in 33-45 us).  Worth 8 us of the c4 step
 // (0.4237 -> 0.4157 ms for the loss entry inside bench.py, three interleaved runs each); nothing on a tensor that
 // was not just written (252 vs 249 us alone) -- which is how round 1 measured it and found no change.
-#ifndef RNNT_GATHER_REVERSE
-#define RNNT_GATHER_REVERSE 1
-#endif
 
-#ifndef RNNT_GATHER_TT
-#define RNNT_GATHER_TT 32
-#endif
 // The dense gather's pair stores are written THROUGH (sc1) -- round 6: what its 58 MB of stores cost is dirty lines on their
 // way out of L2 holding back the fills of the read stream; written through, nothing is left dirty: the kernel
 // alone 252.0 -> 247.6 us (tools/ubench/gather_r06.hip), inside bench.py's c4 step 0.2215 -> 0.2182 ms (four interleaved
-// pairs, profiles/r06_gather_sc1_ab.txt).  sc0 sc1 the same, nt / sc0 sc1 nt worse.  -DRNNT_GATHER_STORE_SC1=0: plain stores.
-#ifndef RNNT_GATHER_STORE_SC1
-#define RNNT_GATHER_STORE_SC1 1
-#endif
-constexpr int TT = RNNT_GATHER_TT;   // frames per tile of k_to_diagonal (columns: TD)
+// pairs, profiles/r06_gather_sc1_ab.txt).  sc0 sc1 the same, nt / sc0 sc1 nt worse.
+constexpr int TT = 32;   // frames per tile of k_to_diagonal (columns: TD)
 
 // The preparation of the ring kernel that follows in the same call (kernels.h: RingPrep; lattice_wd.hip: k_prepare is the
 // stand-alone form), carried out at the tail of a producer's workgroups: every workgroup zeroes its slice of the rings,
@@ -1470,7 +1379,7 @@ __global__ void __launch_bounds__(256)
 k_to_diagonal(const float* __restrict__ src, const int* __restrict__ labels, float2* __restrict__ ws2,
               int T, int U, int V, int blank, int tiles_t, int tiles_u, const RingPrep prep) {
     __shared__ float2 tile[TTK][TD];
-    unsigned b = (DENSE && RNNT_GATHER_REVERSE) ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+    unsigned b = DENSE ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
     const int tu = b % tiles_u; b /= tiles_u;
     const int tt = b % tiles_t;
     const int n = b / tiles_t;
@@ -1509,14 +1418,13 @@ k_to_diagonal(const float* __restrict__ src, const int* __restrict__ labels, flo
             if (t < T && u < U) {
                 int r = t + u;
                 r = r >= T ? r % T : r;
-#if RNNT_GATHER_STORE_SC1
                 // written THROUGH (agent scope): nothing is left dirty in L2 for the read stream's fills to wait behind
                 // (tools/ubench/gather_r06.hip: 247.6 vs 252.0 us alone)
                 if constexpr (DENSE) {
                     asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(ws2 + nbase + (size_t)r * U + u), "v"(tile[tl][ul]) : "memory");
-                } else
-#endif
-                ws2[nbase + (size_t)r * U + u] = tile[tl][ul];
+                } else {
+                    ws2[nbase + (size_t)r * U + u] = tile[tl][ul];
+                }
             }
         }
     }
@@ -1739,10 +1647,7 @@ k_gather_compact(const float* __restrict__ xs, const int* __restrict__ ys, const
 // 0.1-0.4 GB because its grid covers the batch maxima: profiles/r04_shape_map.md).  Every lane reads its two dwords from
 // a row of its own either way, so nothing is lost on the read side; the pairs leave as scattered 8-byte stores (the
 // tiles write runs of up to 256 bytes), loc as one coalesced stream.
-#ifndef RNNT_GCL_CELLS
-#define RNNT_GCL_CELLS 4
-#endif
-constexpr int GCL_CELLS = RNNT_GCL_CELLS;       // cells per thread
+constexpr int GCL_CELLS = 4;       // cells per thread
 __global__ void __launch_bounds__(256)
 k_gather_compact_linear(const float* __restrict__ xs, const int* __restrict__ ys, const int* __restrict__ xn,
                         const int* __restrict__ yn, const int64_t* __restrict__ offs,
