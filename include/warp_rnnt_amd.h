@@ -290,6 +290,40 @@ rnntStatus_t rnnt_amd_logits_backward_typed(rnntStream_t stream, int dtype, cons
                                             int N, int T, int U, int V, int blank);
 /* rnnt_amd_log_softmax on x of type `dtype`; out is fp32 (it may alias x only for RNNT_DTYPE_F32). */
 rnntStatus_t rnnt_amd_log_softmax_typed(rnntStream_t stream, int dtype, const void *x, float *out, int64_t rows, int V);
+
+/*
+ * The fused path on the compact (ragged packed) layout (version 107, additive): rnnt_amd_loss_compact with LOGITS of
+ * type `dtype` (STU,V) in place of log-probs -- log-softmax and gather in one read of the logits, the same workspace
+ * (rnnt_amd_workspace_size_compact / _bounded), the same lattice and gradient kernels.  The log-probabilities never
+ * exist in HBM.  grads2 (STU,2) row-major [blank,label] gradients, fully written (NULL = costs only); there is no loc.
+ * Packed row c belongs to utterance n, the first n with cell_offsets[n+1] > c, as cell (t,u) of its row-major
+ * (xn[n], yn[n]+1) block.  A row outside its owner's range, of an owner whose range is not xn*(yn+1) rows inside the
+ * tensor, or whose label index is not inside ys, belongs to nobody: it gets no pair here and a zero row of d/d logits in
+ * the backward.  ys holds label_offsets[N] labels (the bounded form: n_labels).  Refused with
+ * RNNT_STATUS_INVALID_ARGUMENT before any HIP call: an unknown dtype, every size rnnt_amd_loss_compact refuses,
+ * V < 1, blank outside [0,V), a NULL or misaligned workspace, NULL ys while labels exist (Umax > 1; n_labels > 0).
+ * Bits: as for the dense logits entries, costs are those of the fp32 call on the upcast logits.
+ */
+rnntStatus_t rnnt_amd_loss_compact_logits(rnntStream_t stream, void *workspace, int dtype, const void *logits,
+                                          const int *ys, const int *xn, const int *yn, const int64_t *cell_offsets,
+                                          const int *label_offsets, float *costs, float *grads2, int N, int64_t STU,
+                                          int Tmax, int Umax, int V, int blank, float fastemit_lambda);
+/* The same with caller-supplied launch bounds, as rnnt_amd_loss_compact_bounded: offsets and checks on the device,
+ * nothing read back, capturable; a batch that does not fit gets NaN costs and zero pairs. */
+rnntStatus_t rnnt_amd_loss_compact_logits_bounded(rnntStream_t stream, void *workspace, int dtype, const void *logits,
+                                                  const int *ys, int64_t n_labels, const int *xn, const int *yn,
+                                                  float *costs, float *grads2, int N, int64_t STU, int Tmax, int Umax,
+                                                  int V, int blank, float fastemit_lambda);
+/* Backward of either: d(sum_n grad_costs[n]*cost[n]) / d(logits), (STU,V) in the logits' dtype, every row written
+ * (grad_costs NULL = 1; dlogits may alias logits), dz[v] = s_n ([v==blank] gB + [v==label] gL - softmax(z)[v] (gB+gL))
+ * from the forward's grads2.  cell_offsets / label_offsets are those rnnt_amd_compact_offsets enqueues (no host
+ * synchronisation: after the bounded forward, enqueue it on the same lengths); n_labels = the elements of ys, which
+ * bounds every label read.  Refusals as above (no workspace here; NULL ys while n_labels > 0, n_labels < 0). */
+rnntStatus_t rnnt_amd_compact_logits_backward(rnntStream_t stream, int dtype, const void *logits, const int *ys,
+                                              int64_t n_labels, const int *xn, const int *yn,
+                                              const int64_t *cell_offsets, const int *label_offsets,
+                                              const float *grads2, const float *grad_costs, void *dlogits, int N,
+                                              int64_t STU, int V, int blank);
 /* Row-wise log-softmax over the last axis; out may alias x. */
 rnntStatus_t rnnt_amd_log_softmax(rnntStream_t stream, const float *x, float *out, int64_t rows, int V);
 

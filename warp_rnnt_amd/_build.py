@@ -16,6 +16,7 @@ LIB = os.path.join(HERE, "libwarp_rnnt_amd.so")
 SOURCES = ["api.hip", "lattice.hip", "lattice_ws.hip", "lattice_wd.hip", "grads.hip", "prologue.hip", "prologue_half.hip",
            "expand.hip"]
 HEADERS = ["common.h", "kernels.h", "lattice_step.h", "lattice_wd_body.h", "lattice_single.h", "grads_cell.h",
+           "lsm_body_small.h", "lsm_body_large.h", "lsm_body_generic.h", "lsm_body_rows.h",
            os.path.join("..", "..", "include", "warp_rnnt_amd.h")]
 ARCH = "gfx950"
 # Sources whose kernels refill live registers with inline-assembly LDS loads the compiler does not count (lattice_step.h):

@@ -446,6 +446,93 @@ rnntStatus_t rnnt_amd_loss_compact_bounded(rnntStream_t stream, void* workspace,
     return RNNT_STATUS_SUCCESS;
 }
 
+// The compact layout with LOGITS (fp32 / bf16 / fp16) in place of log-probs: the fused log-softmax + gather over the packed
+// rows (prologue.hip: CompactMap) replaces the gather, everything behind it is rnnt_amd_loss_compact's.
+namespace {
+bool compact_logits_args_ok(int dtype, int N, int64_t STU, int Tmax, int Umax, int V, int blank) {
+    return (dtype == RNNT_DTYPE_F32 || dtype == RNNT_DTYPE_BF16 || dtype == RNNT_DTYPE_F16) &&
+           compact_dims_ok(N, STU, Tmax, Umax) && V >= 1 && blank >= 0 && blank < V;
+}
+rnntStatus_t compact_logits_core(rnntStream_t stream, void* workspace, int dtype, const void* logits, const int* ys,
+                                 int64_t n_labels, const int* xn, const int* yn, const int64_t* cell_offsets,
+                                 const int* label_offsets, float* costs, float* grads2, int N, int64_t STU, int Tmax,
+                                 int Umax, int V, int blank, float fastemit_lambda) {
+    CompactWorkspace w;
+    carve_compact(workspace, N, STU, Tmax > 0 ? Tmax : 1, Umax > 0 ? Umax : 1, &w);
+    const PackedRows cr{cell_offsets, label_offsets, xn, yn, ys, n_labels, STU, N};
+    const hipError_t e = dtype == RNNT_DTYPE_F32
+                             ? launch_lsm_gather_compact(stream, static_cast<const float*>(logits), w.ws2, cr, V, blank)
+                             : launch_lsm_gather_compact_half(stream, dtype, logits, w.ws2, cr, V, blank);
+    if (e != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
+    LatticeArgs la{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, Tmax, Umax, 2, 0, cell_offsets, w.redo,
+                   w.redo + 2 * N, w.mail};
+    if (launch_lattice(stream, la, N, LOAD_SKEWED) != hipSuccess) return RNNT_STATUS_WARP_FAILED;
+    GradArgs ga{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, grads2 ? grads2 : w.ws2, costs, w.mismatch,
+                Tmax, Umax, 2, 0, fastemit_lambda, cell_offsets};
+    if (launch_grads(stream, ga, N, LOAD_SKEWED, grads2 ? WRITE_ROWMAJOR2 : WRITE_SKEWED2) != hipSuccess)
+        return RNNT_STATUS_GRADS_BLANK_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+}  // namespace
+
+rnntStatus_t rnnt_amd_loss_compact_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                          const int* ys, const int* xn, const int* yn, const int64_t* cell_offsets,
+                                          const int* label_offsets, float* costs, float* grads2, int N, int64_t STU,
+                                          int Tmax, int Umax, int V, int blank, float fastemit_lambda) {
+    if (!compact_logits_args_ok(dtype, N, STU, Tmax, Umax, V, blank) || !workspace) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(workspace) % ALIGN) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (Umax > 1 && !ys) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0 || STU == 0) return RNNT_STATUS_SUCCESS;
+    // (ys holds label_offsets[N] labels: the kernels read no further)
+    return compact_logits_core(stream, workspace, dtype, logits, ys, -1, xn, yn, cell_offsets, label_offsets, costs, grads2,
+                               N, STU, Tmax, Umax, V, blank, fastemit_lambda);
+}
+
+rnntStatus_t rnnt_amd_loss_compact_logits_bounded(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                                  const int* ys, int64_t n_labels, const int* xn, const int* yn,
+                                                  float* costs, float* grads2, int N, int64_t STU, int Tmax, int Umax,
+                                                  int V, int blank, float fastemit_lambda) {
+    if (!compact_logits_args_ok(dtype, N, STU, Tmax, Umax, V, blank) || !workspace || Tmax < 1 || Umax < 1 ||
+        n_labels < 0)
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(workspace) % ALIGN) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (n_labels > 0 && !ys) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    if (STU == 0) {      // (as rnnt_amd_loss_compact_bounded: a batch this entry always refuses)
+        if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(costs), 0x7fc00000, (size_t)N, stream) != hipSuccess)
+            return RNNT_STATUS_COSTS_FAILED;
+        return RNNT_STATUS_SUCCESS;
+    }
+    BoundedExtra e;
+    carve_bounded(static_cast<char*>(workspace), rnnt_amd_workspace_size_compact(N, STU, Tmax, Umax), N, &e);
+    const CompactBounds b{e.xn_checked, STU, n_labels, Tmax, Umax};
+    if (launch_compact_offsets(stream, xn, yn, N, e.cell_offsets, e.label_offsets, e.stats, &b) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    const rnntStatus_t st = compact_logits_core(stream, workspace, dtype, logits, ys, n_labels, e.xn_checked, yn,
+                                                e.cell_offsets, e.label_offsets, costs, grads2, N, STU, Tmax, Umax, V,
+                                                blank, fastemit_lambda);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (launch_zero_if_refused(stream, e.stats + 4, grads2, (size_t)STU) != hipSuccess) return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_compact_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* ys,
+                                              int64_t n_labels, const int* xn, const int* yn,
+                                              const int64_t* cell_offsets, const int* label_offsets,
+                                              const float* grads2, const float* grad_costs, void* dlogits, int N,
+                                              int64_t STU, int V, int blank) {
+    if (!compact_logits_args_ok(dtype, N, STU, 1, 1, V, blank) || n_labels < 0) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (n_labels > 0 && !ys) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (STU == 0) return RNNT_STATUS_SUCCESS;
+    const PackedRows cr{cell_offsets, label_offsets, xn, yn, ys, n_labels, STU, N};
+    const hipError_t e =
+        dtype == RNNT_DTYPE_F32
+            ? launch_logits_backward_compact(stream, static_cast<const float*>(logits), grads2, grad_costs,
+                                             static_cast<float*>(dlogits), cr, V, blank)
+            : launch_logits_backward_compact_half(stream, dtype, logits, grads2, grad_costs, dlogits, cr, V, blank);
+    return e == hipSuccess ? RNNT_STATUS_SUCCESS : RNNT_STATUS_EXPAND_FAILED;
+}
+
 // Replaces run_scatter_grad_for_compact (core.h:56-60, core_compact.cu:456-500): dense (STU,V)
 // gradient rows, fully written.  cum_lens = inclusive prefix sums of xn*(yn+1) (int32, as the
 // reference's RNNTLossCompact.forward builds them, __init__.py:38).

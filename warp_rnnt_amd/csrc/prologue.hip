@@ -62,6 +62,118 @@ __device__ __forceinline__ CellMap map_cell(size_t cell, const int* __restrict__
     return m;
 }
 
+// The row -> cell map of the fused log-softmax kernels is a policy, passed by value and chosen by a template parameter.
+// chunk(first, last) is called by every wave of a kernel, wave-uniformly, before at() is asked for rows in [first, last];
+// pair() and scale() read the backward's gradient pair and upstream scale of a mapped row, put() stores the gather's pair.
+//   DenseMap: the (N,T,U,V) tensor, map_cell -- what the dense kernels have always done.
+struct DenseMap {
+    static constexpr bool COMPACT = false;
+    const int* labels;
+    int T, U;
+    __device__ __forceinline__ void chunk(int64_t, int64_t) {}
+    __device__ __forceinline__ CellMap at(size_t cell, int V, int blank) const {
+        return map_cell(cell, labels, T, U, V, blank);
+    }
+    template <class B> __device__ __forceinline__ float2 pair(const B& bw, const CellMap m) const { return bw.g2[m.sk]; }
+    template <class B> __device__ __forceinline__ float scale(const B& bw, const CellMap m) const {
+        return bw.scale ? bw.scale[m.n] : 1.0f;
+    }
+    __device__ __forceinline__ void put(float* out, const CellMap m, float2 p) const {
+        reinterpret_cast<float2*>(out)[m.sk] = p;
+    }
+};
+
+// The owner of packed row c -- the first n with offs[n+1] > c, N when there is none -- searched by a whole wave: its lanes
+// probe 64 evenly spaced utterances at once and the first that already ends past c narrows the range 64-fold, so N <= 64
+// costs one round of loads and N <= 4096 two (a binary search costs log2 N dependent loads, ~0.5 us each from L2).
+// Lanes 0-31 search for `first`, lanes 32-63 for `last`, 32 probes per round each.  For offsets that are not
+// non-decreasing the search still ends on one utterance of [0, N]; CompactMap::at checks the row against its range.
+__device__ __forceinline__ void compact_owner_range(const int64_t* __restrict__ offs, int N, int64_t first, int64_t last,
+                                                    int& n0, int& n1) {
+    const int lane = threadIdx.x & (WAVE - 1), half = lane >> 5, j = lane & 31;
+    const int64_t c = half ? last : first;
+    int lo = 0, hi = N;                                // answer in [lo, hi]; hi = N stands for "no utterance"
+    for (;;) {
+        const bool more = lo < hi;
+        const uint64_t act = __ballot(more);
+        if (act == 0) break;
+        const int step = (hi - lo + 31) >> 5;
+        const int m = lo + j * step;
+        const bool p = more && (m >= hi || offs[m + 1] > c);
+        const uint64_t b = __ballot(p);
+        const unsigned mine = (unsigned)(b >> (32 * half));   // this half's probes
+        if (more) {
+            if (mine) {
+                const int f = __builtin_ctz(mine);
+                hi = min(hi, lo + f * step);
+                lo = f ? lo + (f - 1) * step + 1 : lo;
+            } else {
+                lo = lo + 31 * step + 1;
+            }
+            lo = min(lo, hi);
+        }
+    }
+    n0 = __shfl(lo, 0, WAVE);
+    n1 = __shfl(lo, 32, WAVE);
+}
+
+//   CompactMap: ragged packed rows (kernels.h: PackedRows).  The pair slot in the forward is the skewed one of the compact
+//   workspace, offs[n] + ((t+u) mod T_n)*U_n + u; in the backward the row-major (STU,2) pairs are read at the row itself.
+//   at() finds the owner inside the chunk's [n0, n1] only; m.n = -1 marks a row that belongs to nobody.
+template <bool SKEW>
+struct CompactMap {
+    static constexpr bool COMPACT = true;
+    PackedRows r;
+    int n0, n1;
+    __device__ __forceinline__ void chunk(int64_t first, int64_t last) {
+        compact_owner_range(r.offs, r.N, first, last, n0, n1);
+        n1 = min(n1, r.N - 1);
+    }
+    __device__ __forceinline__ CellMap at(size_t cell, int V, int blank) const {
+        CellMap m = {0, blank, -1};
+        const int64_t c = (int64_t)cell;
+        int n = n0, hi = n1;
+        while (n < hi) {
+            const int mid = (n + hi) >> 1;
+            if (r.offs[mid + 1] > c) hi = mid; else n = mid + 1;
+        }
+        if (n >= r.N || c >= r.rows) return m;
+        const int64_t o = r.offs[n], e = r.offs[n + 1];
+        const int T = r.xn[n], U = r.yn[n] + 1;
+        // the owner's range must be exactly its T_n*U_n rows inside the tensor, or none of them is mapped
+        if (c < o || c >= e || o < 0 || e > r.rows || T < 1 || U < 1 || e - o != (int64_t)T * U) return m;
+        const unsigned local = (unsigned)(c - o);      // (< T_n*U_n < 2^32)
+        const unsigned t = local / (unsigned)U;
+        const int u = (int)(local - t * (unsigned)U);
+        int lab = blank;
+        if (u < U - 1) {
+            const int64_t li = (int64_t)r.loffs[n] + u;
+            const int64_t lim = r.nlab >= 0 ? r.nlab : (int64_t)r.loffs[r.N];
+            if (li < 0 || li >= lim) return m;
+            lab = safe_label(r.ys[li], V, blank);
+        }
+        if (SKEW) {
+            int d = (int)t + u;
+            d = d >= T ? d % T : d;
+            m.sk = (size_t)o + (size_t)d * U + u;
+        } else {
+            m.sk = cell;
+        }
+        m.label = lab;
+        m.n = n;
+        return m;
+    }
+    template <class B> __device__ __forceinline__ float2 pair(const B& bw, const CellMap& m) const {
+        return m.n >= 0 ? bw.g2[m.sk] : make_float2(0.0f, 0.0f);
+    }
+    template <class B> __device__ __forceinline__ float scale(const B& bw, const CellMap& m) const {
+        return (bw.scale && m.n >= 0) ? bw.scale[m.n] : 1.0f;
+    }
+    __device__ __forceinline__ void put(float* out, const CellMap& m, float2 p) const {
+        if (m.n >= 0) reinterpret_cast<float2*>(out)[m.sk] = p;
+    }
+};
+
 // ---------------------------------------------------------------------------
 // Small vocabularies (V <= 1024): a workgroup stages R whole rows in LDS with
 // 16-byte coalesced loads (ds_write_b128, rows kept at their natural stride V so
@@ -174,207 +286,17 @@ template <typename E, int L, int MODE, bool WP>
 __global__ void __launch_bounds__(SM_THREADS)
 k_lsm_small(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
             int64_t rows, int V, int R, int q, int T, int U, int blank, LsmBwd bw) {
-    constexpr bool GATHER = MODE == LSM_GATHER;
-    extern __shared__ __attribute__((aligned(16))) float tile[];
-    float2* stat = reinterpret_cast<float2*>(tile + (size_t)R * V);   // GATHER: (max, log-sum) per row
-    const int tid = threadIdx.x;
-    const int64_t row0 = (int64_t)stream_block() * R;
-    if (row0 >= rows) return;
-    const int nrows = (int)min((int64_t)R, rows - row0);
-    const int nel = nrows * V;                      // floats in this chunk
-    const E* src = x + row0 * V;                    // vector aligned: R % 4 == 0 (out may alias x)
-    // wave-private view of the same tile: rows [wr0, wr0 + wn) of the chunk
-    constexpr int RW = (WAVE / L) > 0 ? (WAVE / L) : 1;
-    const int lane = tid & (WAVE - 1);
-    const int wr0 = (tid >> 6) * RW;
-    const int wn = min(max(nrows - wr0, 0), RW);
-    const int wel = wn * V, wvec = wel >> 2;
-    float* wtile = tile + wr0 * V;
-
-    // ---- stage: the tile is a plain copy of the chunk ----
-    const int nvec = nel >> 2;
-    // fused backward: the gradient pair (and scale) of the row this thread works on first, requested before the tile
-    [[maybe_unused]] CellMap pm = {0, 0, 0};
-    [[maybe_unused]] float2 pg = make_float2(0.0f, 0.0f);
-    [[maybe_unused]] float psc = 1.0f;
-    if constexpr (MODE == LSM_BWD) {
-        pm = map_cell((size_t)(row0 + min(tid / L, nrows - 1)), labels, T, U, V, blank);
-        pg = bw.g2[pm.sk];
-        psc = bw.scale ? bw.scale[pm.n] : 1.0f;
-    }
-    // LOADS FIRST (round 5).  Written as `for (i ...) tile[i] = load(src + i)` the compiler emits load, s_waitcnt vmcnt(0),
-    // ds_write per iteration: a wave had ONE 16-byte load per lane in flight at a time and paid the memory latency three
-    // to four times per tile -- 1 KB per wave in flight, 32 KB per CU, which at ~1.5 us of loaded latency is the 5.2 TB/s
-    // the fused gather ran at (read-only streams reach 7.0, tools/ubench/copy_rate.hip).  A tile is at most four passes
-    // of the threads that stage it (SM_FLOATS, and V <= 16 L for the wave-private form): all of a lane's loads are
-    // issued before the first of them is written to LDS -- unconditionally, at an index clamped into the tile, and so are
-    // the LDS writes (lanes past the end rewrite the tile's last 16 bytes with the bytes that are there).  A predicate per
-    // load comes out as a branch per load with a conservative wait at every join; predicates on the writes alone and the
-    // compiler sinks the loads into them.
-    constexpr int STAGE_UN = WP ? 4 : (sm_floats<E, MODE>() / 4 + SM_THREADS - 1) / SM_THREADS;   // (3200 floats, 256 threads: 4)
-    if constexpr (WP) {
-        const E* wsrc = src + (size_t)wr0 * V;
-        for (int base = lane; base < wvec; base += STAGE_UN * WAVE) {
-            float4 sv[STAGE_UN];
-#pragma unroll
-            for (int k = 0; k < STAGE_UN; ++k)
-                sv[k] = lsm_ld4<RNNT_LSM_NT_MODE(MODE)>(wsrc, min(base + k * WAVE, wvec - 1));
-#pragma unroll
-            for (int k = 0; k < STAGE_UN; ++k)
-                reinterpret_cast<float4*>(wtile)[min(base + k * WAVE, wvec - 1)] = sv[k];
-        }
-        for (int e = (wvec << 2) + lane; e < wel; e += WAVE) wtile[e] = lsm_ld1(wsrc + e);
-        wave_sync_lds();
-    } else {
-        for (int base = tid; base < nvec; base += STAGE_UN * SM_THREADS) {
-            float4 sv[STAGE_UN];
-#pragma unroll
-            for (int k = 0; k < STAGE_UN; ++k)
-                sv[k] = lsm_ld4<RNNT_LSM_NT_MODE(MODE)>(src, min(base + k * SM_THREADS, nvec - 1));
-#pragma unroll
-            for (int k = 0; k < STAGE_UN; ++k)
-                reinterpret_cast<float4*>(tile)[min(base + k * SM_THREADS, nvec - 1)] = sv[k];
-        }
-        for (int e = (nvec << 2) + tid; e < nel; e += SM_THREADS) tile[e] = lsm_ld1(src + e);   // last chunk only
-        __syncthreads();
-    }
-
-    // ---- per-row max / sum(exp) / normalise: L lanes per row, lane h owns columns h, h+L, ... ----
-    constexpr int RPP = SM_THREADS / L;             // rows per pass
-    const int h = tid % L, rr = tid / L;
-    const int ctail = h + (q - 1) * L;              // this lane's last column, may be >= V
-    const bool tail_ok = ctail < V;
-    // One row: the lane's q values are read ONCE into registers by a straight-line sequence (all LDS reads in flight
-    // together), reduced, and -- in the modes that rewrite the row -- written back from the registers.  QC = q as a
-    // compile-time constant (9 ... 16: what the launcher's choice of L gives for V > 16); the run-time loops of the first
-    // version waited for every LDS read of the max pass on its own (~9 instructions and one LDS latency per element) and
-    // read every element a second time for the sum.
-    auto one_row = [&](auto QC, const int r) {
-        constexpr int Q = decltype(QC)::value;
-        float* row = tile + r * V;
-        float v[Q];
-#pragma unroll
-        for (int i = 0; i < Q - 1; ++i) v[i] = row[h + i * L];
-        v[Q - 1] = tail_ok ? row[ctail] : -__builtin_inff();
-        float mx = v[0];
-#pragma unroll
-        for (int i = 1; i < Q; ++i) mx = fmaxf(mx, v[i]);
-        mx = group_max<L>(mx);
-        const float mb = -mx * LOG2E;
-        float s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < Q; ++i) s += __builtin_amdgcn_exp2f(__builtin_fmaf(v[i], LOG2E, mb));   // (exp2(-inf) = 0)
-        s = group_sum<L>(s);
-        const float ls = __builtin_amdgcn_logf(s) * LN2;
-        if constexpr (GATHER) {
-            if (h == 0) stat[r] = make_float2(mx, ls);
-        } else if constexpr (MODE == LSM_BWD) {
-            const bool first = r == rr;                // (the row whose pair was requested up front)
-            const CellMap m = first ? pm : map_cell((size_t)(row0 + r), labels, T, U, V, blank);
-            const float sc = first ? psc : (bw.scale ? bw.scale[m.n] : 1.0f);
-            const float2 g = first ? pg : bw.g2[m.sk];
-            const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
-            const float mb2 = -(mx + ls) * LOG2E;
-#pragma unroll
-            for (int i = 0; i < Q - 1; ++i)
-                row[h + i * L] = -__builtin_amdgcn_exp2f(__builtin_fmaf(v[i], LOG2E, mb2)) * gs;
-            if (tail_ok) row[ctail] = -__builtin_amdgcn_exp2f(__builtin_fmaf(v[Q - 1], LOG2E, mb2)) * gs;
-            // the L lanes of a row sit in one wave and LDS operations of a wave retire in order
-            if (h == 0) { row[blank] += gB; row[m.label] += gL; }
-        } else {
-#pragma unroll
-            for (int i = 0; i < Q - 1; ++i) row[h + i * L] = (v[i] - mx) - ls;
-            if (tail_ok) row[ctail] = (v[Q - 1] - mx) - ls;
-        }
-    };
-    auto all_rows = [&](auto QC) {
-        for (int r = rr; r < nrows; r += RPP) one_row(QC, r);
-    };
-    switch (q) {
-#define LSM_Q(QQ) case QQ: all_rows(std::integral_constant<int, QQ>{}); break;
-        LSM_Q(9) LSM_Q(10) LSM_Q(11) LSM_Q(12) LSM_Q(13) LSM_Q(14) LSM_Q(15) LSM_Q(16)
-#undef LSM_Q
-        default:      // q <= 8 (V <= 16, or rows shorter than the lane cover): run-time loops
-    for (int r = rr; r < nrows; r += RPP) {
-        float* row = tile + r * V;
-        float mx = -__builtin_inff();
-        for (int i = 0, c = h; i < q - 1; ++i, c += L) mx = fmaxf(mx, row[c]);
-        if (tail_ok) mx = fmaxf(mx, row[ctail]);
-        mx = group_max<L>(mx);
-        const float mb = -mx * LOG2E;
-        float s = 0.0f;
-        for (int i = 0, c = h; i < q - 1; ++i, c += L) s += __builtin_amdgcn_exp2f(__builtin_fmaf(row[c], LOG2E, mb));
-        if (tail_ok) s += __builtin_amdgcn_exp2f(__builtin_fmaf(row[ctail], LOG2E, mb));
-        s = group_sum<L>(s);
-        const float ls = __builtin_amdgcn_logf(s) * LN2;
-        if constexpr (GATHER) {
-            if (h == 0) stat[r] = make_float2(mx, ls);
-        } else if constexpr (MODE == LSM_BWD) {
-            const CellMap m = map_cell((size_t)(row0 + r), labels, T, U, V, blank);
-            const float sc = bw.scale ? bw.scale[m.n] : 1.0f;
-            const float2 g = bw.g2[m.sk];
-            const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
-            const float mb2 = -(mx + ls) * LOG2E;
-            for (int i = 0, c = h; i < q - 1; ++i, c += L)
-                row[c] = -__builtin_amdgcn_exp2f(__builtin_fmaf(row[c], LOG2E, mb2)) * gs;
-            if (tail_ok) row[ctail] = -__builtin_amdgcn_exp2f(__builtin_fmaf(row[ctail], LOG2E, mb2)) * gs;
-            // the L lanes of a row sit in one wave and LDS operations of a wave retire in order
-            if (h == 0) { row[blank] += gB; row[m.label] += gL; }
-        } else {
-            for (int i = 0, c = h; i < q - 1; ++i, c += L) row[c] = (row[c] - mx) - ls;
-            if (tail_ok) row[ctail] = (row[ctail] - mx) - ls;
-        }
-    }
-    }
-    if constexpr (GATHER && WP) {
-        wave_sync_lds();
-        for (int r = wr0 + lane; r < wr0 + wn; r += WAVE) {
-            const CellMap m = map_cell((size_t)(row0 + r), labels, T, U, V, blank);
-            const float2 st = stat[r];
-            const float* row = tile + r * V;
-            reinterpret_cast<float2*>(out)[m.sk] =
-                make_float2((row[blank] - st.x) - st.y, (row[m.label] - st.x) - st.y);
-        }
-    } else if constexpr (GATHER) {
-        // one lane per row with all lanes busy (the per-row index arithmetic costs ~60 instructions;
-        // doing it inside the L-lane row loop ran it with a quarter of the lanes)
-        __syncthreads();
-        for (int r = tid; r < nrows; r += SM_THREADS) {
-            const CellMap m = map_cell((size_t)(row0 + r), labels, T, U, V, blank);
-            const float2 st = stat[r];
-            const float* row = tile + r * V;
-            const float2 pr = make_float2((row[blank] - st.x) - st.y, (row[m.label] - st.x) - st.y);
-            // (written through, sc1: +38 us at c4 -- scattered 8-byte stores need L2 to merge them.  Timing probes that sent
-            // the pairs into a 64 KB region that stays in L2, or stored them in row-major order as coalesced 512-byte runs:
-            // the gather's stores cost 40-55 us in any shape)
-            reinterpret_cast<float2*>(out)[m.sk] = pr;
-        }
-    } else if constexpr (WP) {
-        wave_sync_lds();
-        LsmOut<MODE, E>* wdst = out + (row0 + wr0) * V;
-        if constexpr (std::is_same_v<E, float>) {
-            for (int i = lane; i < wvec; i += WAVE)
-                RNNT_LSM_STORE(reinterpret_cast<float4*>(wdst) + i, reinterpret_cast<const float4*>(wtile)[i]);
-            for (int e = (wvec << 2) + lane; e < wel; e += WAVE) wdst[e] = wtile[e];
-        } else {
-            for (int i = lane; i < wvec; i += WAVE)
-                lsm_st4<RNNT_LSM_NT_MODE(MODE)>(wdst, i, reinterpret_cast<const float4*>(wtile)[i]);
-            for (int e = (wvec << 2) + lane; e < wel; e += WAVE) lsm_st1(wdst + e, wtile[e]);
-        }
-    } else {
-        __syncthreads();
-        LsmOut<MODE, E>* dst = out + row0 * V;
-        if constexpr (std::is_same_v<E, float>) {
-            for (int i = tid; i < nvec; i += SM_THREADS)
-                RNNT_LSM_STORE(reinterpret_cast<float4*>(dst) + i, reinterpret_cast<const float4*>(tile)[i]);
-            for (int e = (nvec << 2) + tid; e < nel; e += SM_THREADS) dst[e] = tile[e];
-        } else {
-            for (int i = tid; i < nvec; i += SM_THREADS)
-                lsm_st4<RNNT_LSM_NT_MODE(MODE)>(dst, i, reinterpret_cast<const float4*>(tile)[i]);
-            for (int e = (nvec << 2) + tid; e < nel; e += SM_THREADS) lsm_st1(dst + e, tile[e]);
-        }
-    }
+    DenseMap map{labels, T, U};
+#include "lsm_body_small.h"
 }
+template <typename E, int L, int MODE, bool WP>
+__global__ void __launch_bounds__(SM_THREADS)
+k_lsm_small_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int R, int q, int blank,
+                    LsmBwd bw) {
+    CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
+#include "lsm_body_small.h"
+}
+
 
 // ---------------------------------------------------------------------------
 // Large vocabularies (1024 < V <= 16384, V % 4 == 0): one workgroup per row,
@@ -418,121 +340,14 @@ template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
 __global__ void __launch_bounds__(LG_THREADS)
 k_lsm_large(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
             int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
-    constexpr bool GATHER = MODE == LSM_GATHER;
-    __shared__ float red[LG_THREADS / WAVE];
-    // bw.xcd: every XCD (workgroups go to them by blockIdx mod 8; the grid is a multiple of 8) streams a contiguous
-    // eighth of the rows instead of every eighth row -- see dispatch_lsm
-    const size_t per_xcd = ((size_t)rows + 7) / 8;
-    const size_t items = bw.xcd ? per_xcd * 8 : (size_t)rows;
-    for (size_t it = blockIdx.x; it < items; it += gridDim.x) {
-    const size_t row = bw.xcd ? (it & 7) * per_xcd + (it >> 3) : it;
-    if (row >= (size_t)rows) continue;
-    const E* src = x + row * V;
-    const int nvec = V >> 2;
-    // How a lane's LG_MAXVEC loads are issued (round 5).  As first written -- load and running maximum together under
-    // `if (j < nvec)` -- every load sits in a branch of its own with an s_waitcnt vmcnt(0) behind it: LG_MAXVEC memory
-    // round trips per row, one after the other.  Measured against two loads-first forms (tools/ab_kernels.py, three
-    // interleaved rounds, profiles/r05_loads_first_ab.txt):
-    //   * the read-mostly FUSED modes gain 5-7 % from all loads issued unconditionally at an index clamped into the row,
-    //     what lies beyond the row replaced by -inf afterwards (c3: fused forward 317 -> 300 us, fused backward 739 -> 689);
-    //   * the plain log-softmax -- a read and a write stream at the rate of a copy -- does not: V = 5000 629 -> 647 us,
-    //     4096 596 -> 606, 2048 590 -> 594, nothing at 1000, 3000, 8192; only the three-pass covers of 768 threads and more
-    //     gain (c5's V = 10000: 693 -> 674 clamped, -> 665 with the loads alone under their predicates and the maxima
-    //     behind them), so those take the predicated form and everything else stays as it was.
-    constexpr bool CLAMPED = MODE != LSM_NORM;
-    constexpr bool PREDICATED = MODE == LSM_NORM && LG_THREADS >= 768;
-    float4 v[LG_MAXVEC];
-    float mx = -__builtin_inff();
-    if constexpr (CLAMPED || PREDICATED) {
-#pragma unroll
-        for (int i = 0; i < LG_MAXVEC; ++i) {
-            const int j = (int)threadIdx.x + i * LG_THREADS;
-            if constexpr (CLAMPED) {
-                v[i] = lsm_ld4<true>(src, min(j, nvec - 1));
-            } else {
-                if (j < nvec) v[i] = lsm_ld4<true>(src, j);
-            }
-        }
-    }
-    // what the fused modes need besides the row, requested behind it instead of after the reductions
-    [[maybe_unused]] CellMap m = {0, 0, 0};
-    [[maybe_unused]] float2 side = make_float2(0.0f, 0.0f);      // GATHER: the row's (blank, label) logits; BWD: its gradient pair
-    [[maybe_unused]] float sc = 1.0f;
-    if constexpr (MODE != LSM_NORM) {
-        m = map_cell(row, labels, T, U, V, blank);
-        if constexpr (GATHER) {
-            const E* xr = x + row * V;
-            side = make_float2(lsm_ld1(xr + blank), lsm_ld1(xr + m.label));
-        } else {
-            side = bw.g2[m.sk];
-            sc = bw.scale ? bw.scale[m.n] : 1.0f;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < LG_MAXVEC; ++i) {
-        const int j = (int)threadIdx.x + i * LG_THREADS;
-        if constexpr (CLAMPED || PREDICATED) {
-            if (j >= nvec) {
-                const float ninf = -__builtin_inff();
-                v[i] = make_float4(ninf, ninf, ninf, ninf);
-            }
-            mx = fmaxf(fmaxf(mx, fmaxf(v[i].x, v[i].y)), fmaxf(v[i].z, v[i].w));
-        } else {
-            if (j < nvec) {
-                v[i] = lsm_ld4<true>(src, j);
-                mx = fmaxf(fmaxf(mx, fmaxf(v[i].x, v[i].y)), fmaxf(v[i].z, v[i].w));
-            }
-        }
-    }
-    mx = block_reduce<LG_THREADS>(mx, true, red);
-    const float mb = -mx * LOG2E;
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < LG_MAXVEC; ++i) {
-        const int j = threadIdx.x + i * LG_THREADS;
-        if (j < nvec)
-            s += (__builtin_amdgcn_exp2f(__builtin_fmaf(v[i].x, LOG2E, mb)) + __builtin_amdgcn_exp2f(__builtin_fmaf(v[i].y, LOG2E, mb))) +
-                 (__builtin_amdgcn_exp2f(__builtin_fmaf(v[i].z, LOG2E, mb)) + __builtin_amdgcn_exp2f(__builtin_fmaf(v[i].w, LOG2E, mb)));
-    }
-    s = block_reduce<LG_THREADS>(s, false, red);
-    const float ls = logf(s);
-    if constexpr (GATHER) {
-        if (threadIdx.x == 0)
-            reinterpret_cast<float2*>(out)[m.sk] = make_float2((side.x - mx) - ls, (side.y - mx) - ls);
-    } else if constexpr (MODE == LSM_BWD) {
-        const float2 g = side;
-        const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
-        const float mb2 = -(mx + ls) * LOG2E;
-        LsmOut<MODE, E>* dst = out + row * V;
-#pragma unroll
-        for (int i = 0; i < LG_MAXVEC; ++i) {
-            const int j = threadIdx.x + i * LG_THREADS;
-            if (j < nvec) {
-                float o[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
-#pragma unroll
-                for (int cc = 0; cc < 4; ++cc) {
-                    const int e = 4 * j + cc;
-                    float d = -__builtin_amdgcn_exp2f(__builtin_fmaf(o[cc], LOG2E, mb2)) * gs;
-                    d += (e == blank) ? gB : 0.0f;
-                    d += (e == m.label) ? gL : 0.0f;
-                    o[cc] = d;
-                }
-                lsm_st4<true>(dst, j, make_float4(o[0], o[1], o[2], o[3]));
-            }
-        }
-    } else {
-        float* dst = out + row * V;
-#pragma unroll
-        for (int i = 0; i < LG_MAXVEC; ++i) {
-            const int j = threadIdx.x + i * LG_THREADS;
-            if (j < nvec) {
-                const float4 r = make_float4((v[i].x - mx) - ls, (v[i].y - mx) - ls, (v[i].z - mx) - ls,
-                                             (v[i].w - mx) - ls);
-                lsm_st4<true>(dst, j, r);
-            }
-        }
-    }
-    }
+    DenseMap map{labels, T, U};
+#include "lsm_body_large.h"
+}
+template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
+__global__ void __launch_bounds__(LG_THREADS)
+k_lsm_large_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
+    CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
+#include "lsm_body_large.h"
 }
 
 // ---------------------------------------------------------------------------
@@ -542,40 +357,14 @@ template <typename E, int MODE>
 __global__ void __launch_bounds__(256)
 k_lsm_generic(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
               int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
-    constexpr bool GATHER = MODE == LSM_GATHER;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const E* xr = x + row * V;
-    float mx = -__builtin_inff();
-    for (int c = lane; c < V; c += WAVE) mx = fmaxf(mx, lsm_ld1(xr + c));
-    mx = group_max<WAVE>(mx);
-    float s = 0.0f;
-    for (int c = lane; c < V; c += WAVE) s += expf(lsm_ld1(xr + c) - mx);
-    s = group_sum<WAVE>(s);
-    const float ls = logf(s);
-    if constexpr (GATHER) {
-        if (lane == 0) {
-            const CellMap m = map_cell((size_t)row, labels, T, U, V, blank);
-            reinterpret_cast<float2*>(out)[m.sk] =
-                make_float2((lsm_ld1(xr + blank) - mx) - ls, (lsm_ld1(xr + m.label) - mx) - ls);
-        }
-    } else if constexpr (MODE == LSM_BWD) {
-        const CellMap m = map_cell((size_t)row, labels, T, U, V, blank);
-        const float sc = bw.scale ? bw.scale[m.n] : 1.0f;
-        const float2 g = bw.g2[m.sk];
-        const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
-        LsmOut<MODE, E>* o = out + row * V;
-        for (int c = lane; c < V; c += WAVE) {
-            float d = -expf((lsm_ld1(xr + c) - mx) - ls) * gs;
-            d += (c == blank) ? gB : 0.0f;
-            d += (c == m.label) ? gL : 0.0f;
-            lsm_st1(o + c, d);
-        }
-    } else {
-        float* o = out + row * V;
-        for (int c = lane; c < V; c += WAVE) o[c] = (lsm_ld1(xr + c) - mx) - ls;
-    }
+    DenseMap map{labels, T, U};
+#include "lsm_body_generic.h"
+}
+template <typename E, int MODE>
+__global__ void __launch_bounds__(256)
+k_lsm_generic_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
+    CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
+#include "lsm_body_generic.h"
 }
 
 // ---------------------------------------------------------------------------
@@ -842,40 +631,14 @@ __device__ __forceinline__ void lsm_rows_stats_of_lane(int lane, const float (&m
 template <typename E, int L, int Q>
 __global__ void __launch_bounds__(256)
 k_lsm_rows(const E* x, float* out, const int* __restrict__ labels, int64_t rows, int V, int T, int U, int blank) {
-    constexpr int MODE = LSM_GATHER, VEC = 4;
-    constexpr int UN = RowsShape<L>::UN, RW = RowsShape<L>::RW, RPW = RowsShape<L>::RPW;
-    const int lane = threadIdx.x & 63, h = lane % L, rr = lane / L;
-    // wave-uniform values kept in scalar registers (the 64-bit row arithmetic runs on the scalar unit)
-    const int64_t row0 = ((int64_t)stream_block() * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * RPW;
-    if (row0 >= rows) return;
-    const bool last_ok = (h + (Q - 1) * L) * VEC < V;   // the lane's last float4 is part of the row
-    const bool whole = row0 + RPW <= rows;              // (uniform) every row of this wave exists
-    const E* const wave_src = x + row0 * V;
-    const unsigned lane_off = (unsigned)rr * (unsigned)V + (unsigned)h * VEC;      // floats inside a pass
-    // lane l < RPW owns the pair of row row0 + l.  Its two logits are requested FIRST, next to the row loads that bring
-    // the same lines (asked for after the rows have streamed through, they are fetched a second time: forward 252 vs 216
-    // us at V = 128, profiles/r04_lsm_rows_ab.txt)
-    CellMap cm = {0, 0, 0};
-    float xb = 0.0f, xl = 0.0f;
-    const bool own = lane < RPW && row0 + lane < rows;
-    if (own) {
-        cm = map_cell((size_t)(row0 + lane), labels, T, U, V, blank);
-        const E* xr = x + (row0 + lane) * V;
-        xb = lsm_ld1(xr + blank);
-        xl = lsm_ld1(xr + cm.label);
-    }
-    const E* src[UN];
-#pragma unroll
-    for (int p = 0; p < UN; ++p) {
-        src[p] = wave_src + (size_t)(p * RW) * V + lane_off;
-        // (rows past the end of the tensor -- last wave only -- re-read the last row and are dropped at the stores)
-        if (!whole && row0 + p * RW + rr >= rows) src[p] = x + (rows - 1) * V + h * VEC;
-    }
-    float mx[UN], ls[UN];
-    lsm_rows_stats<E, L, Q, MODE>(src, last_ok, mx, ls);
-    float m, lg;
-    lsm_rows_stats_of_lane<L>(lane, mx, ls, m, lg);
-    if (own) reinterpret_cast<float2*>(out)[cm.sk] = make_float2((xb - m) - lg, (xl - m) - lg);
+    DenseMap map{labels, T, U};
+#include "lsm_body_rows.h"
+}
+template <typename E, int L, int Q>
+__global__ void __launch_bounds__(256)
+k_lsm_rows_compact(const E* x, float* out, PackedRows cr, int64_t rows, int V, int blank) {
+    CompactMap<true> map{cr, 0, 0};
+#include "lsm_body_rows.h"
 }
 
 // Along the diagonals (rows that are one or two whole 128-byte lines: V = 32, 64; T >= 16): a wave takes the 16 cells
@@ -936,11 +699,47 @@ static int lsm_regs_rows_per_group(int V) {
     return (best && (best * V) / 4 >= 20) ? best : 0;
 }
 
+// One launch of a fused log-softmax kernel family, dense or compact by the map policy.
+template <typename E, int L, int MODE, bool WP, class Map>
+static void launch_lsm_small(unsigned grid, size_t lds, hipStream_t stream, const E* x, LsmOut<MODE, E>* out,
+                             const Map& map, int64_t rows, int V, int R, int q, int blank, LsmBwd bw) {
+    if constexpr (Map::COMPACT)
+        k_lsm_small_compact<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.r, rows, V, R, q, blank, bw);
+    else
+        k_lsm_small<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.labels, rows, V, R, q, map.T, map.U,
+                                                                       blank, bw);
+}
+template <typename E, int MODE, int TH, int NV, class Map>
+static void launch_lsm_large(unsigned grid, hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const Map& map,
+                             int64_t rows, int V, int blank, LsmBwd bw) {
+    if constexpr (Map::COMPACT)
+        k_lsm_large_compact<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
+    else
+        k_lsm_large<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
+}
+template <typename E, int MODE, class Map>
+static void launch_lsm_generic(unsigned grid, hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const Map& map,
+                               int64_t rows, int V, int blank, LsmBwd bw) {
+    if constexpr (Map::COMPACT)
+        k_lsm_generic_compact<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
+    else
+        k_lsm_generic<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
+}
+template <typename E, int L, int Q, class Map>
+static void launch_lsm_rows(unsigned grid, hipStream_t stream, const E* x, float* out, const Map& map, int64_t rows,
+                            int V, int blank) {
+    if constexpr (Map::COMPACT)
+        k_lsm_rows_compact<E, L, Q><<<grid, 256, 0, stream>>>(x, out, map.r, rows, V, blank);
+    else
+        k_lsm_rows<E, L, Q><<<grid, 256, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank);
+}
+
 // E: the storage type of x (and of out in LSM_BWD).  Every byte predicate of the routing is one of whole four-element
 // vectors (16 bytes of fp32, 8 of half), so a V takes the same kernel and the same lanes per row at every E.
-template <int MODE, typename E = float>
-static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const int* labels,
-                               int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
+// Map: the row -> cell policy (DenseMap, CompactMap); compact rows never take the diagonal walk of k_lsm_rows_diag.
+template <int MODE, typename E, class Map>
+static hipError_t dispatch_lsm_map(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, Map map, int64_t rows, int V,
+                                   int blank, LsmBwd bw) {
     constexpr bool GATHER = MODE == LSM_GATHER;
     if (rows <= 0) return hipSuccess;
     const bool aligned = (reinterpret_cast<uintptr_t>(x) % (4 * sizeof(E)) == 0) &&
@@ -970,7 +769,7 @@ static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* 
                 const hipError_t e = hipGetLastError();
                 const int64_t done = ngroups * kr;              // (a group boundary: vector aligned)
                 if (e != hipSuccess || done == rows) return e;
-                return dispatch_lsm<MODE, E>(stream, x + done * V, out + done * V, labels, rows - done, V, T, U, blank, bw);
+                return dispatch_lsm_map<MODE, E>(stream, x + done * V, out + done * V, map, rows - done, V, blank, bw);
             }
         }
     }
@@ -985,7 +784,7 @@ static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* 
         if (aligned && !no_lgr && V % 4 == 0 && V > 128 && V <= 1024) {
             const int nvec = V >> 2, th = (nvec + 63) / 64 * 64;
             const unsigned grid = (unsigned)(rows < (1 << 22) ? rows : (1 << 22));
-#define LGR(TH, NV) { k_lsm_large<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw); return hipGetLastError(); }
+#define LGR(TH, NV) { launch_lsm_large<E, MODE, TH, NV>(grid, stream, x, out, map, rows, V, blank, bw); return hipGetLastError(); }
             if (nvec == 64) LGR(64, 1)
             if (nvec == 128) LGR(64, 2)
             if (nvec == 192) LGR(64, 3)
@@ -1023,18 +822,22 @@ static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* 
             int L = 8;
             while (L < 64 && L * 16 < V) L <<= 1;
             const int q = (V / 4 + L - 1) / L;         // 1 ... 4
-            const int64_t N = rows / ((int64_t)T * U), nub = (U + 15) / 16;
-            if (V <= 64 && V % 32 == 0 && T >= 16 && !no_diag && N <= 65535 && nub <= 65535) {
-                const dim3 grid((unsigned)((T + 3) / 4), (unsigned)nub, (unsigned)N);
-                if (q == 1) k_lsm_rows_diag<E, 1><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
-                else k_lsm_rows_diag<E, 2><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
-                return hipGetLastError();
+            if constexpr (!Map::COMPACT) {             // (the diagonal walk needs the dense (T,U) grid)
+                const int* labels = map.labels;
+                const int T = map.T, U = map.U;
+                const int64_t N = rows / ((int64_t)T * U), nub = (U + 15) / 16;
+                if (V <= 64 && V % 32 == 0 && T >= 16 && !no_diag && N <= 65535 && nub <= 65535) {
+                    const dim3 grid((unsigned)((T + 3) / 4), (unsigned)nub, (unsigned)N);
+                    if (q == 1) k_lsm_rows_diag<E, 1><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
+                    else k_lsm_rows_diag<E, 2><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
+                    return hipGetLastError();
+                }
             }
             const int64_t rpw = L <= 8 ? 2 * (WAVE / L) : WAVE / L;       // RowsShape<L>::RPW
             const int64_t grid = stream_grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
             if ((rows + 4 * rpw - 1) / (4 * rpw) < ((int64_t)1 << 31) - 8) {
 #define LSM_ROWS(LL, QQ) \
-    if (L == LL && q == QQ) k_lsm_rows<E, LL, QQ><<<(unsigned)grid, 256, 0, stream>>>(x, out, labels, rows, V, T, U, blank);
+    if (L == LL && q == QQ) launch_lsm_rows<E, LL, QQ>((unsigned)grid, stream, x, out, map, rows, V, blank);
 #define LSM_ROWS_L(LL) LSM_ROWS(LL, 1) LSM_ROWS(LL, 2) LSM_ROWS(LL, 3) LSM_ROWS(LL, 4)
                 LSM_ROWS_L(8) LSM_ROWS_L(16) LSM_ROWS_L(32) LSM_ROWS_L(64)
 #undef LSM_ROWS_L
@@ -1063,11 +866,9 @@ static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* 
 #define LSM_SMALL(LL)                                                                           \
     case LL:                                                                                    \
         if (wp && LL <= 16)                                                                     \
-            k_lsm_small<E, LL, MODE, (LL <= 16)><<<grid, SM_THREADS, lds, stream>>>(x, out, labels, rows, V, R, q, \
-                                                                                 T, U, blank, bw);             \
+            launch_lsm_small<E, LL, MODE, (LL <= 16)>(grid, lds, stream, x, out, map, rows, V, R, q, blank, bw); \
         else                                                                                    \
-            k_lsm_small<E, LL, MODE, false><<<grid, SM_THREADS, lds, stream>>>(x, out, labels, rows, V, R, q, T,   \
-                                                                            U, blank, bw);                     \
+            launch_lsm_small<E, LL, MODE, false>(grid, lds, stream, x, out, map, rows, V, R, q, blank, bw);     \
         break;
         switch (L) {
             LSM_SMALL(1) LSM_SMALL(2) LSM_SMALL(4) LSM_SMALL(8) LSM_SMALL(16) LSM_SMALL(32)
@@ -1106,18 +907,18 @@ static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* 
             // The thread count is a template parameter on purpose (the same kernel with blockDim.x read at run
             // time: 780 us at V=5000).
             const int nvec = V >> 2;
-#define LGN(TH, NV) case TH: k_lsm_large<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw); break;
+#define LGN(TH, NV) case TH: launch_lsm_large<E, MODE, TH, NV>(grid, stream, x, out, map, rows, V, blank, bw); break;
             if (nvec > 3072) {
-                k_lsm_large<E, MODE, 512, 8><<<grid, 512, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                launch_lsm_large<E, MODE, 512, 8>(grid, stream, x, out, map, rows, V, blank, bw);
             } else if (nvec > 2048) {
                 const int th = (nvec + 383) / 384 * 128;
                 switch (th) { LGN(768, 3) LGN(896, 3) LGN(1024, 3) }
             } else if (nvec > 1536) {
-                k_lsm_large<E, MODE, 1024, 2><<<grid, 1024, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                launch_lsm_large<E, MODE, 1024, 2>(grid, stream, x, out, map, rows, V, blank, bw);
             } else if (nvec > 1408) {
-                k_lsm_large<E, MODE, 768, 2><<<grid, 768, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                launch_lsm_large<E, MODE, 768, 2>(grid, stream, x, out, map, rows, V, blank, bw);
             } else if (nvec > 1024) {
-                k_lsm_large<E, MODE, 512, 3><<<grid, 512, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                launch_lsm_large<E, MODE, 512, 3>(grid, stream, x, out, map, rows, V, blank, bw);
             } else {
                 int th = (nvec + 255) / 256 * 128;
                 th = th < 256 ? 256 : th;
@@ -1127,17 +928,29 @@ static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* 
         } else {
             // read-mostly modes (fused gather, fused backward): the smallest cover, for the residency
             if (V <= 4096)
-                k_lsm_large<E, MODE, 256, 4><<<grid, 256, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                launch_lsm_large<E, MODE, 256, 4>(grid, stream, x, out, map, rows, V, blank, bw);
             else if (V <= 8192)
-                k_lsm_large<E, MODE, 256, 8><<<grid, 256, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                launch_lsm_large<E, MODE, 256, 8>(grid, stream, x, out, map, rows, V, blank, bw);
             else
-                k_lsm_large<E, MODE, 512, 8><<<grid, 512, 0, stream>>>(x, out, labels, rows, V, T, U, blank, bw);
+                launch_lsm_large<E, MODE, 512, 8>(grid, stream, x, out, map, rows, V, blank, bw);
         }
     } else {
-        k_lsm_generic<E, MODE><<<(unsigned)((rows + 3) / 4), 256, 0, stream>>>(x, out, labels, rows, V, T,
-                                                                             U, blank, bw);
+        launch_lsm_generic<E, MODE>((unsigned)((rows + 3) / 4), stream, x, out, map, rows, V, blank, bw);
     }
     return hipGetLastError();
+}
+
+template <int MODE, typename E = float>
+static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const int* labels,
+                               int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
+    return dispatch_lsm_map<MODE, E>(stream, x, out, DenseMap{labels, T, U}, rows, V, blank, bw);
+}
+// compact rows (kernels.h: PackedRows) in the two fused modes
+template <int MODE, typename E>
+static hipError_t dispatch_lsm_compact(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const PackedRows& cr,
+                                       int V, int blank, LsmBwd bw) {
+    static_assert(MODE != LSM_NORM, "the plain log-softmax has no map");
+    return dispatch_lsm_map<MODE, E>(stream, x, out, CompactMap<MODE == LSM_GATHER>{cr, 0, 0}, cr.rows, V, blank, bw);
 }
 
 #ifndef RNNT_PROLOGUE_LSM_ONLY      // (prologue_half.hip includes the log-softmax kernels above and nothing below)
@@ -1156,6 +969,17 @@ hipError_t launch_logits_backward(hipStream_t stream, const float* logits, const
                                   int U, int V, int blank) {
     return dispatch_lsm<LSM_BWD>(stream, logits, dlogits, labels, (int64_t)N * T * U, V, T, U, blank,
                                  LsmBwd{reinterpret_cast<const float2*>(g2_diagonal), scale});
+}
+
+hipError_t launch_lsm_gather_compact(hipStream_t stream, const float* logits, float* ws2, const PackedRows& cr, int V,
+                                     int blank) {
+    return dispatch_lsm_compact<LSM_GATHER>(stream, logits, ws2, cr, V, blank, LsmBwd{nullptr, nullptr});
+}
+
+hipError_t launch_logits_backward_compact(hipStream_t stream, const float* logits, const float* g2_rowmajor,
+                                          const float* scale, float* dlogits, const PackedRows& cr, int V, int blank) {
+    return dispatch_lsm_compact<LSM_BWD>(stream, logits, dlogits, cr, V, blank,
+                                         LsmBwd{reinterpret_cast<const float2*>(g2_rowmajor), scale});
 }
 
 // ---------------------------------------------------------------------------

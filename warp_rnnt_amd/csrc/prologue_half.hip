@@ -53,4 +53,33 @@ hipError_t launch_logits_backward_half(hipStream_t stream, int dtype, const void
     return hipErrorInvalidValue;
 }
 
+// compact (ragged packed) rows: the fused modes with CompactMap (prologue.hip)
+hipError_t launch_lsm_gather_compact_half(hipStream_t stream, int dtype, const void* logits, float* ws2,
+                                          const PackedRows& cr, int V, int blank) {
+    const LsmBwd none{nullptr, nullptr};
+    switch (dtype) {
+        case RNNT_DTYPE_BF16:
+            return dispatch_lsm_compact<LSM_GATHER, __bf16>(stream, static_cast<const __bf16*>(logits), ws2, cr, V, blank,
+                                                            none);
+        case RNNT_DTYPE_F16:
+            return dispatch_lsm_compact<LSM_GATHER, _Float16>(stream, static_cast<const _Float16*>(logits), ws2, cr, V,
+                                                              blank, none);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_logits_backward_compact_half(hipStream_t stream, int dtype, const void* logits, const float* g2_rowmajor,
+                                               const float* scale, void* dlogits, const PackedRows& cr, int V, int blank) {
+    const LsmBwd bw{reinterpret_cast<const float2*>(g2_rowmajor), scale};
+    switch (dtype) {
+        case RNNT_DTYPE_BF16:
+            return dispatch_lsm_compact<LSM_BWD, __bf16>(stream, static_cast<const __bf16*>(logits),
+                                                         static_cast<__bf16*>(dlogits), cr, V, blank, bw);
+        case RNNT_DTYPE_F16:
+            return dispatch_lsm_compact<LSM_BWD, _Float16>(stream, static_cast<const _Float16*>(logits),
+                                                           static_cast<_Float16*>(dlogits), cr, V, blank, bw);
+    }
+    return hipErrorInvalidValue;
+}
+
 }  // namespace rnnt

@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch
 
-from . import ops
+from . import _mismatch, ops
 from warp_rnnt import _C as _core
 
 
@@ -44,15 +44,68 @@ class RNNTLossFromLogits(torch.autograd.Function):
         return ops.logits_backward(logits, labels, grads, go, ctx.blank), None, None, None, None, None
 
 
+def check_compact_logits_inputs(xs, ys, xn, yn):
+    """The checks of ``rnnt_loss(compact=True)`` (warp_rnnt._C.rnnt_loss_compact), in its order and with its texts --
+    except that the logits may be fp32, bf16 or fp16."""
+    for x, name in ((xs, "xs"), (ys, "ys"), (xn, "xn"), (yn, "yn")):
+        _core._check_contiguous(x, name)
+    if xs.dtype not in ops.LOGITS_DTYPES:
+        raise RuntimeError(f"xs (logits) must be a float32, bfloat16 or float16 tensor, not {xs.dtype}")
+    for x, name in ((ys, "ys"), (xn, "xn"), (yn, "yn")):
+        _core._check_int(x, name)
+    for x, name in ((xs, "xs"), (ys, "ys"), (xn, "xn"), (yn, "yn")):
+        _core._check_cuda(x, name)
+    if xs.dim() != 2:
+        raise RuntimeError("xs must have 2 dimensions")
+    if xn.size(0) != yn.size(0):
+        raise RuntimeError("xn and yn shape must be equal (N,)")
+
+
+class RNNTLossCompactFromLogits(torch.autograd.Function):
+    """Packed logits (sum_n T_n*(U_n+1), V) -> costs; backward writes d/d logits in the logits' dtype, out of place."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0,
+                enable_grad: bool = True, max_frames=None, max_labels=None):
+        costs, grads, offs, loffs = ops.loss_compact_logits(logits, labels, frames_lengths, labels_lengths, blank,
+                                                            fastemit_lambda, enable_grad, max_frames, max_labels)
+        if enable_grad:
+            ctx.save_for_backward(logits, labels, frames_lengths, labels_lengths, offs, loffs, grads)
+        ctx.blank = blank
+        return costs
+
+    @staticmethod
+    def backward(ctx, grads_output):
+        logits, labels, xn, yn, offs, loffs, grads = ctx.saved_tensors
+        _mismatch.poll(grads.device)
+        go = grads_output.reshape(-1).to(torch.float32).contiguous()
+        dlogits = ops.compact_logits_backward(logits, labels, xn, yn, offs, loffs, grads, go, ctx.blank)
+        return (dlogits,) + (None,) * 8
+
+
 def rnnt_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, frames_lengths: torch.Tensor,
                           labels_lengths: torch.Tensor, average_frames: bool = False,
                           reduction: Optional[str] = "none", blank: int = 0,
-                          fastemit_lambda: float = 0.0) -> torch.Tensor:
+                          fastemit_lambda: float = 0.0, compact: bool = False,
+                          max_frames: Optional[int] = None, max_labels: Optional[int] = None) -> torch.Tensor:
     """Same value and gradients as ``warp_rnnt.rnnt_loss(F.log_softmax(logits, -1), ..., gather=True)``
-    (arguments as there), without materialising the log-probabilities."""
+    (arguments as there), without materialising the log-probabilities.
+
+    ``compact=True``: the ragged packed layout of ``rnnt_loss(compact=True)`` -- logits ``(sum_n T_n*(U_n+1), V)``,
+    labels ``(sum_n U_n,)`` -- with that call's checks and ``max_frames`` / ``max_labels`` (launch bounds: no host
+    synchronisation, capturable; a batch that does not fit comes back with NaN costs and zero gradients).  Without them
+    one host synchronisation.  The log-probabilities and their (STU,V) gradient never exist."""
     assert reduction is None or reduction in ("none", "mean", "sum")
     assert isinstance(blank, int)
-    costs = RNNTLossFromLogits.apply(logits, labels, frames_lengths, labels_lengths, blank, fastemit_lambda)
+    if not compact and (max_frames is not None or max_labels is not None):
+        raise ValueError("max_frames / max_labels are launch bounds of the compact layout: pass compact=True with them")
+    if compact:
+        check_compact_logits_inputs(logits, labels, frames_lengths, labels_lengths)
+        wants_grad = logits.requires_grad and torch.is_grad_enabled()
+        costs = RNNTLossCompactFromLogits.apply(logits, labels, frames_lengths, labels_lengths, blank, fastemit_lambda,
+                                                wants_grad, max_frames, max_labels)
+    else:
+        costs = RNNTLossFromLogits.apply(logits, labels, frames_lengths, labels_lengths, blank, fastemit_lambda)
     if average_frames:
         costs = costs / frames_lengths.to(costs)      # (fp32 costs: T_n rounded to bf16 would be 1499 -> 1496)
     if reduction == "none" or reduction is None:

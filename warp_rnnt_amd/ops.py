@@ -234,6 +234,84 @@ def loss_compact(xs, ys, xn, yn, blank=0, fastemit_lambda=0.0, required_grad=Tru
     return costs, grads, loc
 
 
+def loss_compact_logits(logits, ys, xn, yn, blank=0, fastemit_lambda=0.0, required_grad=True, max_frames=None,
+                        max_labels=None):
+    """The fused path on the compact layout: logits (STU,V) fp32 / bf16 / fp16, ys (sum yn,), xn/yn (N,).
+    Returns (costs (N,) fp32, grads (STU,2) row-major fp32 or None, cell_offsets (N+1,) int64, label_offsets (N+1,)
+    int32) -- the offsets are what :func:`compact_logits_backward` needs.  Host synchronisations as
+    :func:`loss_compact`: one without bounds, none with them (the offsets for the backward are then enqueued too)."""
+    L = _lib.load()
+    dev = logits.device
+    N = xn.shape[0]
+    STU, V = logits.shape
+    if (max_frames is None) != (max_labels is None):
+        raise ValueError("max_frames and max_labels go together")
+    if not 0 <= blank < V:
+        raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes or blank")
+    dtype = LOGITS_DTYPES[logits.dtype]
+    _mismatch.poll(dev)
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        grads = torch.empty((STU, 2), dtype=torch.float32, device=dev) if required_grad else None
+        offs = torch.empty((N + 1 + 4,), dtype=torch.int64, device=dev)    # offsets + the 4 stats
+        loffs = torch.empty((N + 1,), dtype=torch.int32, device=dev)
+        if N == 0:
+            return costs, grads, offs[:N + 1], loffs
+        if max_frames is not None:
+            tmax, umax = int(max_frames), int(max_labels) + 1
+            if tmax < 1 or umax < 1:
+                raise ValueError("max_frames >= 1 and max_labels >= 0 expected")
+            ws_bytes = L.rnnt_amd_workspace_size_compact_bounded(N, STU, tmax, umax)
+            if ws_bytes == 0:
+                raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes")
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            _check(L.rnnt_amd_loss_compact_logits_bounded(
+                _stream(dev), ws.data_ptr(), dtype, logits.data_ptr(), _ptr(ys), ys.numel(), xn.data_ptr(),
+                yn.data_ptr(), costs.data_ptr(), _ptr(grads), N, STU, tmax, umax, V, blank, float(fastemit_lambda)))
+            if required_grad:          # (enqueued only: the backward's offsets)
+                _check(L.rnnt_amd_compact_offsets(_stream(dev), xn.data_ptr(), yn.data_ptr(), N, offs.data_ptr(),
+                                                  loffs.data_ptr(), offs[N + 1:].data_ptr()))
+            return costs, grads, offs[:N + 1], loffs
+        _check(L.rnnt_amd_compact_offsets(_stream(dev), xn.data_ptr(), yn.data_ptr(), N, offs.data_ptr(),
+                                          loffs.data_ptr(), offs[N + 1:].data_ptr()))
+        stats = offs[N + 1:].tolist()                                       # the one host sync
+        stu_chk, su, tmax, umax = int(stats[0]), int(stats[1]), int(stats[2]), int(stats[3]) + 1
+        if ys.numel() != su:
+            raise RuntimeError("ys shape must be equal to (sum(yn), )")
+        if STU != stu_chk:
+            raise RuntimeError("xs shape mismatch with (\\sum{xn*(yn+1)}, )")
+        ws_bytes = L.rnnt_amd_workspace_size_compact(N, STU, tmax, umax)
+        if ws_bytes == 0:
+            raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes")
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        _check(L.rnnt_amd_loss_compact_logits(_stream(dev), ws.data_ptr(), dtype, logits.data_ptr(), _ptr(ys),
+                                              xn.data_ptr(), yn.data_ptr(), offs.data_ptr(), loffs.data_ptr(),
+                                              costs.data_ptr(), _ptr(grads), N, STU, tmax, umax, V, blank,
+                                              float(fastemit_lambda)))
+    return costs, grads, offs[:N + 1], loffs
+
+
+def compact_logits_backward(logits, ys, xn, yn, cell_offsets, label_offsets, grads, grad_costs, blank=0, out=None):
+    """d(sum_n grad_costs[n]*cost[n]) / d(logits) (STU,V) for the compact fused path, in the logits' dtype; grads and the
+    offsets are those :func:`loss_compact_logits` returned.  Rows that belong to no utterance come back zero."""
+    L = _lib.load()
+    STU, V = logits.shape
+    N = xn.shape[0]
+    dev = logits.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty_like(logits)
+        if out.dtype != logits.dtype or out.shape != logits.shape or not out.is_contiguous():
+            raise RuntimeError("compact_logits_backward: out must be a contiguous tensor like the logits")
+        if STU == 0:
+            return out
+        _check(L.rnnt_amd_compact_logits_backward(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
+                                                  _ptr(ys), ys.numel(), xn.data_ptr(), yn.data_ptr(),
+                                                  cell_offsets.data_ptr(), label_offsets.data_ptr(), grads.data_ptr(),
+                                                  _ptr(grad_costs), out.data_ptr(), N, STU, V, blank))
+    return out
+
+
 def compact_scatter_grads(grad_cost, grad_xs, cum_lens, loc, V, blank):
     """(STU,V) gradient rows from the (STU,2) pairs (reference: rnnt_loss_compact_backward)."""
     L = _lib.load()
