@@ -324,6 +324,38 @@ rnntStatus_t rnnt_amd_compact_logits_backward(rnntStream_t stream, int dtype, co
                                               const int64_t *cell_offsets, const int *label_offsets,
                                               const float *grads2, const float *grad_costs, void *dlogits, int N,
                                               int64_t STU, int V, int blank);
+/*
+ * The joint network fused into the loss (version 107, additive): the costs of rnnt_amd_loss_logits on
+ *   z[n,t,u,:] = weight @ act(f[n,t,:] + g[n,u,:]) + bias,    act = tanh (RNNT_ACT_TANH) or relu (RNNT_ACT_RELU),
+ * without ever storing act(f+g) (N,T,U,H) or z (N,T,U,V).  f (N,T,H), g (N,U,H) and weight (V,H) are of type `dtype`
+ * (RNNT_DTYPE_*), row-major, 16-byte aligned; bias (V,) is fp32 or NULL.  act(f+g) is computed in fp32 and rounded once to
+ * `dtype` as the MFMA operand (fp32: the exact f32 MFMA); z stays fp32.  Sizes: every size rnnt_amd_loss refuses,
+ * H % 32 != 0, H < 32, H > 1024, V < 2 and blank outside [0,V) are RNNT_STATUS_INVALID_ARGUMENT before any HIP call, as
+ * are NULL f / g / weight / xn / yn / costs / workspace, NULL labels while U > 1, a misaligned pointer, an unknown
+ * dtype or activation.
+ * rnnt_amd_joint_workspace_size: bytes of the workspace (256-byte aligned) either call needs; 0 for a refused size.
+ * rnnt_amd_joint_loss: costs (N,) always; with grads != NULL also lse (N,T,U) fp32, the log-normaliser of every cell, and
+ * grads (N,T,U,2) in the RNNT_GRADS_GATHERED_DIAGONAL layout (lse must then be non-NULL).
+ * rnnt_amd_joint_backward: d(sum_n grad_costs[n]*cost[n]) (grad_costs NULL = 1) with respect to f -> df (N,T,H), g ->
+ * dg (N,U,H) (both of type `dtype`, rounded once from fp32; rows t >= xn[n] / u > yn[n] are zero), weight -> dweight
+ * (V,H) fp32 and bias -> dbias (V,) fp32, from the lse and grads of the forward; any output may be NULL (not computed).
+ * Both calls only enqueue work: nothing is read back, both can be captured into a HIP graph.  Each bit of the results
+ * is a function of the inputs and the shape: df / dg rows and costs of an utterance do not depend on the batch around it.
+ */
+enum {
+    RNNT_ACT_TANH = 0,
+    RNNT_ACT_RELU = 1
+};
+size_t rnnt_amd_joint_workspace_size(int N, int T, int U, int H, int V);
+rnntStatus_t rnnt_amd_joint_loss(rnntStream_t stream, void *workspace, int dtype, int activation, const void *f,
+                                 const void *g, const void *weight, const float *bias, const int *labels, const int *xn,
+                                 const int *yn, float *costs, float *lse, float *grads, int N, int T, int U, int H, int V,
+                                 int blank, float fastemit_lambda);
+rnntStatus_t rnnt_amd_joint_backward(rnntStream_t stream, void *workspace, int dtype, int activation, const void *f,
+                                     const void *g, const void *weight, const float *bias, const int *labels,
+                                     const int *xn, const int *yn, const float *lse, const float *grads,
+                                     const float *grad_costs, void *df, void *dg, float *dweight, float *dbias, int N,
+                                     int T, int U, int H, int V, int blank);
 /* Row-wise log-softmax over the last axis; out may alias x. */
 rnntStatus_t rnnt_amd_log_softmax(rnntStream_t stream, const float *x, float *out, int64_t rows, int V);
 

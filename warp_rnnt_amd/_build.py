@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwarp_rnnt_amd.so")
 SOURCES = ["api.hip", "lattice.hip", "lattice_ws.hip", "lattice_wd.hip", "grads.hip", "prologue.hip", "prologue_half.hip",
-           "expand.hip"]
+           "expand.hip", "joint.hip"]
 HEADERS = ["common.h", "kernels.h", "lattice_step.h", "lattice_wd_body.h", "lattice_single.h", "grads_cell.h",
            "lsm_body_small.h", "lsm_body_large.h", "lsm_body_generic.h", "lsm_body_rows.h",
            os.path.join("..", "..", "include", "warp_rnnt_amd.h")]

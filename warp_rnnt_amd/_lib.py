@@ -23,6 +23,8 @@ IN_LOG_PROBS_DENSE, IN_LOG_PROBS_GATHERED, IN_LOGITS_DENSE = 0, 1, 2
 GRADS_GATHERED, GRADS_GATHERED_DIAGONAL, GRADS_DENSE, GRADS_NONE = 0, 1, 2, 3
 # element type of the logits for the typed entries (rnnt_amd_loss_logits, ..._typed)
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
+# activation of rnnt_amd_joint_loss / _backward
+ACT_TANH, ACT_RELU = 0, 1
 
 # every symbol include/warp_rnnt_amd.h declares: (restype, argtypes)
 _vp, _i, _f, _sz, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
@@ -52,6 +54,9 @@ SYMBOLS = {
     "rnnt_amd_loss_compact_logits": (_i, [_vp, _vp, _i] + [_vp] * 8 + [_i, _i64, _i, _i, _i, _i, _f]),
     "rnnt_amd_loss_compact_logits_bounded": (_i, [_vp, _vp, _i, _vp, _vp, _i64] + [_vp] * 4 + [_i, _i64, _i, _i, _i, _i, _f]),
     "rnnt_amd_compact_logits_backward": (_i, [_vp, _i, _vp, _vp, _i64] + [_vp] * 7 + [_i, _i64, _i, _i]),
+    "rnnt_amd_joint_workspace_size": (_sz, [_i] * 5),
+    "rnnt_amd_joint_loss": (_i, [_vp, _vp, _i, _i] + [_vp] * 10 + [_i] * 6 + [_f]),
+    "rnnt_amd_joint_backward": (_i, [_vp, _vp, _i, _i] + [_vp] * 14 + [_i] * 6),
     "rnnt_amd_compact_scatter_grads": (_i, [_vp] * 6 + [_i64, _i, _i, _i]),
     "rnnt_amd_compact_offsets": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "rnnt_amd_debug_lattice_only": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),

@@ -197,6 +197,17 @@ rnntStatus_t run_warp_rnnt_gather(rnntStream_t stream, unsigned int* counts, flo
     return RNNT_STATUS_SUCCESS;
 }
 
+// Step 3 of a loss call on the workspace's pair plane, after the sweeps: costs, guard and the gradient pairs, written by
+// `writer` into gout
+static rnntStatus_t pair_grads(rnntStream_t stream, const Workspace& w, const int* xn, const int* yn, float* costs,
+                               float* gout, int writer, int N, int T, int U, float fastemit_lambda) {
+    GradArgs ga{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, gout, costs, w.mismatch,
+                T, U, 2, 0, fastemit_lambda};
+    if (launch_grads(stream, ga, N, LOAD_SKEWED, writer) != hipSuccess)
+        return RNNT_STATUS_GRADS_BLANK_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
 // rnnt_amd_loss with the element type of the input (RNNT_DTYPE_*: anything but fp32 for RNNT_IN_LOGITS_DENSE only)
 static rnntStatus_t loss_of_type(rnntStream_t stream, void* workspace, int input_kind, int dtype, const void* input_any,
                                  const int* labels, const int* xn, const int* yn, float* costs, float* grads,
@@ -263,10 +274,8 @@ static rnntStatus_t loss_of_type(rnntStream_t stream, void* workspace, int input
         if (launch_grads_dense(stream, gd, grads, N) != hipSuccess) return RNNT_STATUS_GRADS_BLANK_FAILED;
         return RNNT_STATUS_SUCCESS;
     }
-    GradArgs ga{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, gout, costs, w.mismatch,
-                T, U, 2, 0, fastemit_lambda};
-    if (launch_grads(stream, ga, N, LOAD_SKEWED, writer) != hipSuccess)
-        return RNNT_STATUS_GRADS_BLANK_FAILED;
+    const rnntStatus_t st = pair_grads(stream, w, xn, yn, costs, gout, writer, N, T, U, fastemit_lambda);
+    if (st != RNNT_STATUS_SUCCESS) return st;
     if (grads_kind == RNNT_GRADS_DENSE) {
         if (launch_expand(stream, w.ws2, labels, xn, yn, nullptr, grads, N, T, U, V, blank, 1) != hipSuccess)
             return RNNT_STATUS_EXPAND_FAILED;
@@ -699,6 +708,84 @@ rnntStatus_t rnnt_amd_logits_backward_typed(rnntStream_t stream, int dtype, cons
     if (U > 1 && !labels) return RNNT_STATUS_INVALID_ARGUMENT;
     if (launch_logits_backward_half(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
         hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// The joint network fused into the loss (joint.hip).  Workspace: rnnt_amd_workspace_size's carve, then W^T (H,Vp) for
+// the backward, then the weight kernel's fp32 partials (splits x Vp x H and splits x Vp), splits sized for fp32 (the
+// most a dtype takes).
+namespace {
+struct JointWorkspace {
+    void* wt;
+    float* dw_part;
+    float* db_part;
+};
+size_t carve_joint(void* base, int N, int T, int U, int H, int V, JointWorkspace* jw) {
+    size_t off = carve(base, N, T, U, nullptr);
+    char* p = static_cast<char*>(base);
+    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return p ? p + o : nullptr; };
+    const size_t vp = (size_t)joint_vpad(V), splits = (size_t)joint_w_splits(N, T, U, H, V, RNNT_DTYPE_F32);
+    void* wt = take((size_t)H * vp * 4);
+    float* dw = reinterpret_cast<float*>(take(splits * vp * H * 4));
+    float* db = reinterpret_cast<float*>(take(splits * vp * 4));
+    if (jw) *jw = JointWorkspace{wt, dw, db};
+    return off;
+}
+bool joint_args_ok(int dtype, int activation, int N, int T, int U, int H, int V, int blank) {
+    return (dtype == RNNT_DTYPE_F32 || dtype == RNNT_DTYPE_BF16 || dtype == RNNT_DTYPE_F16) &&
+           (activation == RNNT_ACT_TANH || activation == RNNT_ACT_RELU) && dims_ok(N, T, U) && H >= 32 && H <= 1024 &&
+           H % 32 == 0 && V >= 2 && V <= (1 << 24) && blank >= 0 && blank < V;
+}
+inline bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+}  // namespace
+
+size_t rnnt_amd_joint_workspace_size(int N, int T, int U, int H, int V) {
+    if (!joint_args_ok(RNNT_DTYPE_F32, RNNT_ACT_TANH, N, T, U, H, V, 0)) return 0;
+    return carve_joint(nullptr, N, T, U, H, V, nullptr);
+}
+
+rnntStatus_t rnnt_amd_joint_loss(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                 const void* g, const void* weight, const float* bias, const int* labels, const int* xn,
+                                 const int* yn, float* costs, float* lse, float* grads, int N, int T, int U, int H, int V,
+                                 int blank, float fastemit_lambda) {
+    if (!joint_args_ok(dtype, activation, N, T, U, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace || !f || !g || !weight || !xn || !yn || !costs || (U > 1 && !labels) || (grads && !lse))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(workspace) % ALIGN || !al16(f) || !al16(g) || !al16(weight) ||
+        reinterpret_cast<uintptr_t>(bias) % 4)
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Workspace w;
+    carve(workspace, N, T, U, &w);
+    // 1. z tile by tile: the (blank,label) log-prob pairs into the pair plane (launch_log_softmax_gather_skewed's
+    //    layout), lse per cell
+    if (launch_joint_fwd(stream, dtype, activation, f, g, weight, bias, labels, xn, yn, w.ws2, grads ? lse : nullptr, N,
+                         T, U, H, V, blank) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    // 2. + 3. as rnnt_amd_loss_logits(RNNT_GRADS_GATHERED_DIAGONAL or RNNT_GRADS_NONE)
+    LatticeArgs la{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, T, U, 2, 0, nullptr, w.redo, w.redo + 2 * N, w.mail};
+    if (launch_lattice(stream, la, N, LOAD_SKEWED) != hipSuccess) return RNNT_STATUS_WARP_FAILED;
+    return pair_grads(stream, w, xn, yn, costs, grads ? grads : w.ws2, WRITE_SKEWED2, N, T, U, fastemit_lambda);
+}
+
+rnntStatus_t rnnt_amd_joint_backward(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                     const void* g, const void* weight, const float* bias, const int* labels,
+                                     const int* xn, const int* yn, const float* lse, const float* grads,
+                                     const float* grad_costs, void* df, void* dg, float* dweight, float* dbias, int N,
+                                     int T, int U, int H, int V, int blank) {
+    if (!joint_args_ok(dtype, activation, N, T, U, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace || !f || !g || !weight || !xn || !yn || !lse || !grads || (U > 1 && !labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(workspace) % ALIGN || !al16(f) || !al16(g) || !al16(weight) ||
+        reinterpret_cast<uintptr_t>(bias) % 4 || reinterpret_cast<uintptr_t>(grads) % 8)
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0 || (!df && !dg && !dweight && !dbias)) return RNNT_STATUS_SUCCESS;
+    JointWorkspace jw;
+    carve_joint(workspace, N, T, U, H, V, &jw);
+    if (launch_joint_bwd(stream, dtype, activation, f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs, jw.wt,
+                         jw.dw_part, jw.db_part, joint_w_splits(N, T, U, H, V, dtype), df, dg, dweight, dbias, N, T, U,
+                         H, V, blank) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
 }

@@ -160,6 +160,19 @@ hipError_t launch_gather_compact(hipStream_t stream, const float* xs, const int*
 hipError_t launch_scatter_compact(hipStream_t stream, const float* grad_cost, const float* grads2,
                                   const int64_t* loc, const int* cum_lens, float* out, int64_t STU, int N,
                                   int V, int blank);
+// the joint network fused into the loss (joint.hip): dtype RNNT_DTYPE_*, act RNNT_ACT_*; `pairs` = the workspace's
+// diagonal-major pair plane, lse (N,T,U) or nullptr
+int joint_vpad(int V);
+int joint_w_splits(int N, int T, int U, int H, int V, int dtype);
+hipError_t launch_joint_fwd(hipStream_t stream, int dtype, int act, const void* f, const void* g, const void* w,
+                            const float* bias, const int* labels, const int* xn, const int* yn, float* pairs,
+                            float* lse, int N, int T, int U, int H, int V, int blank);
+// wt: (H, joint_vpad(V)) elements of dtype; dw_part / db_part: splits x joint_vpad(V) x H and splits x joint_vpad(V) fp32
+hipError_t launch_joint_bwd(hipStream_t stream, int dtype, int act, const void* f, const void* g, const void* w,
+                            const float* bias, const int* labels, const int* xn, const int* yn, const float* lse,
+                            const float* grads, const float* grad_costs, void* wt, float* dw_part, float* db_part,
+                            int splits, void* df, void* dg, float* dweight, float* dbias, int N, int T, int U, int H,
+                            int V, int blank);
 hipError_t launch_log_softmax_gather_skewed(hipStream_t stream, const float* logits, const int* labels,
                                             float* ws2, int N, int T, int U, int V, int blank);
 hipError_t launch_logits_backward(hipStream_t stream, const float* logits, const int* labels,

@@ -1,0 +1,120 @@
+"""The joint network fused into the loss.
+
+A training step of a transducer puts a joint network in front of the loss, ``z = Linear(H, V)(act(f_t + g_u))``.  Run
+as written it materialises two (N,T,U,H) tensors -- ``f + g`` and its activation -- plus the (N,T,U,V) logits, and their
+gradients.  :func:`rnnt_loss_from_joint` takes the joint's inputs instead and forms z tile by tile in HIP kernels
+(MFMA), so none of those tensors ever exists: forward keeps one fp32 log-normaliser and one gradient pair per lattice
+cell, backward recomputes z.
+"""
+from typing import Optional
+
+import torch
+
+from . import _mismatch, ops
+from warp_rnnt import _C as _core
+
+
+def check_joint_inputs(f, g, weight, bias, labels, xn, yn, activation, blank):
+    """Shapes, dtypes and devices of :func:`rnnt_loss_from_joint`'s arguments, with the library's refusals."""
+    for x, name in ((f, "f"), (g, "g"), (weight, "weight"), (labels, "labels"), (xn, "frames_lengths"),
+                    (yn, "labels_lengths")):
+        if not isinstance(x, torch.Tensor):
+            raise RuntimeError(f"{name} must be a tensor")
+    if activation not in ops.ACTIVATIONS:
+        raise RuntimeError(f"activation must be one of {tuple(ops.ACTIVATIONS)}, not {activation!r}")
+    if f.dtype not in ops.LOGITS_DTYPES:
+        raise RuntimeError(f"f must be a float32, bfloat16 or float16 tensor, not {f.dtype}")
+    if g.dtype != f.dtype:
+        raise RuntimeError(f"f and g must share one dtype (f is {f.dtype}, g is {g.dtype})")
+    for x, name in ((weight, "weight"), (bias, "bias")):
+        if x is not None and x.dtype not in (torch.float32, f.dtype):
+            raise RuntimeError(f"{name} must be float32 or the activations' dtype {f.dtype}, not {x.dtype}")
+    for x, name in ((labels, "labels"), (xn, "frames_lengths"), (yn, "labels_lengths")):
+        _core._check_int(x, name)
+    if f.dim() != 3 or g.dim() != 3:
+        raise RuntimeError("f must be (N,T,H) and g (N,U+1,H)")
+    if weight.dim() != 2:
+        raise RuntimeError("weight must be (V,H), the nn.Linear layout")
+    N, T, H = f.shape
+    V = weight.size(0)
+    if g.size(0) != N or g.size(2) != H:
+        raise RuntimeError(f"g must be (N,U+1,H) = ({N},U+1,{H}), not {tuple(g.shape)}")
+    if weight.size(1) != H:
+        raise RuntimeError(f"weight must be (V,H) with H={H}, not {tuple(weight.shape)}")
+    if bias is not None and (bias.dim() != 1 or bias.size(0) != V):
+        raise RuntimeError(f"bias must be (V,) = ({V},), not {tuple(bias.shape)}")
+    if labels.dim() != 2 or labels.size(0) != N or labels.size(1) + 1 != g.size(1):
+        raise RuntimeError(f"labels must be (N,U) with g of U+1 rows: labels {tuple(labels.shape)}, g {tuple(g.shape)}")
+    if xn.dim() != 1 or yn.dim() != 1 or xn.size(0) != N or yn.size(0) != N:
+        raise RuntimeError("frames_lengths and labels_lengths must be (N,)")
+    if H % 32 != 0 or not 32 <= H <= 1024 or V < 2 or not 0 <= blank < V:
+        raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the fused joint takes H % 32 == 0, "
+                           f"32 <= H <= 1024, V >= 2 and 0 <= blank < V (H={H}, V={V}, blank={blank})")
+    for x, name in ((f, "f"), (g, "g"), (weight, "weight"), (bias, "bias"), (labels, "labels"),
+                    (xn, "frames_lengths"), (yn, "labels_lengths")):
+        if x is not None:
+            _core._check_cuda(x, name)
+            if x.device != f.device:
+                raise RuntimeError(f"{name} must be on the device of f ({f.device}), not {x.device}")
+
+
+class RNNTLossFromJoint(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, f, g, weight, bias, labels, frames_lengths, labels_lengths, activation, blank, fastemit_lambda,
+                with_grads):
+        fc, gc = f.contiguous(), g.contiguous()
+        w = weight.to(fc.dtype).contiguous()                     # W staged in the activations' dtype
+        b = bias.to(torch.float32).contiguous() if bias is not None else None
+        labels, xn, yn = labels.contiguous(), frames_lengths.contiguous(), labels_lengths.contiguous()
+        costs, lse, grads = ops.joint_loss(fc, gc, w, b, labels, xn, yn, activation, blank, fastemit_lambda,
+                                           with_grads)
+        if with_grads:
+            ctx.save_for_backward(fc, gc, w, b, labels, xn, yn, lse, grads)
+        ctx.activation, ctx.blank = activation, blank
+        ctx.weight_dtype = weight.dtype
+        ctx.bias_dtype = bias.dtype if bias is not None else None
+        return costs
+
+    @staticmethod
+    def backward(ctx, grads_output):
+        f, g, w, b, labels, xn, yn, lse, grads = ctx.saved_tensors
+        _mismatch.poll(f.device)
+        go = grads_output.reshape(-1).to(torch.float32).contiguous()
+        need = ctx.needs_input_grad
+        df, dg, dw, db = ops.joint_backward(f, g, w, b, labels, xn, yn, lse, grads, go, ctx.activation, ctx.blank,
+                                            need[0], need[1], need[2], need[3] and b is not None)
+        if dw is not None:
+            dw = dw.to(ctx.weight_dtype)
+        if db is not None:
+            db = db.to(ctx.bias_dtype)
+        return (df, dg, dw, db) + (None,) * 7
+
+
+def rnnt_loss_from_joint(f: torch.Tensor, g: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                         labels: torch.Tensor, frames_lengths: torch.Tensor, labels_lengths: torch.Tensor,
+                         activation: str = "tanh", average_frames: bool = False, reduction: Optional[str] = "none",
+                         blank: int = 0, fastemit_lambda: float = 0.0) -> torch.Tensor:
+    """The value of ``rnnt_loss_from_logits(z, labels, frames_lengths, labels_lengths, ...)`` with
+    ``z[n,t,u] = weight @ act(f[n,t] + g[n,u]) + bias`` -- f (N,T,H), g (N,U+1,H), weight (V,H) (``nn.Linear.weight``),
+    bias (V,) or None, act ``"tanh"`` or ``"relu"`` -- and gradients to f, g, weight and bias, without materialising an
+    (N,T,U+1,H) or (N,T,U+1,V) tensor.
+
+    f and g share one dtype (fp32, bf16 or fp16); weight and bias may be fp32 or that dtype (fp32 master weights under
+    autocast).  act(f+g) is computed in fp32 and rounded to the activations' dtype as the matrix-core operand; the logits
+    stay fp32.  Costs are fp32; d f and d g come back in the activations' dtype, d weight and d bias in their parameters'.
+    Supported: H % 32 == 0, 32 <= H <= 1024, V >= 2.  Nothing is read back to the host: the call can be captured into a
+    CUDA graph."""
+    assert reduction is None or reduction in ("none", "mean", "sum")
+    assert isinstance(blank, int)
+    check_joint_inputs(f, g, weight, bias, labels, frames_lengths, labels_lengths, activation, blank)
+    with_grads = torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (f, g, weight, bias))
+    costs = RNNTLossFromJoint.apply(f, g, weight, bias, labels, frames_lengths, labels_lengths, activation, blank,
+                                    fastemit_lambda, with_grads)
+    if average_frames:
+        costs = costs / frames_lengths.to(costs)
+    if reduction == "none" or reduction is None:
+        return costs
+    if reduction == "sum":
+        return costs.sum()
+    return costs.mean()

@@ -365,3 +365,66 @@ def log_softmax_backward(grad_out, out, grad_in=None):
         _check(L.rnnt_amd_log_softmax_backward(_stream(out.device), grad_out.data_ptr(), out.data_ptr(),
                                                grad_in.data_ptr(), rows, V))
     return grad_in
+
+
+ACTIVATIONS = {"tanh": _lib.ACT_TANH, "relu": _lib.ACT_RELU}
+
+
+def _joint_workspace(L, N, T, U, H, V, dev):
+    ws_bytes = L.rnnt_amd_joint_workspace_size(N, T, U, H, V)
+    if ws_bytes == 0:
+        raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes "
+                           f"N={N} T={T} U={U} H={H} V={V}")
+    return torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+
+
+def joint_loss(f, g, weight, bias, labels, xn, yn, activation="tanh", blank=0, fastemit_lambda=0.0, with_grads=True):
+    """The joint network fused into the loss: f (N,T,H), g (N,U,H), weight (V,H) of one dtype (fp32 / bf16 / fp16),
+    bias (V,) fp32 or None; validated by the caller.  Returns costs (N,) fp32 and, with_grads, lse (N,T,U) fp32 and the
+    gradient pairs (N,T,U,2) in the diagonal-major layout -- what :func:`joint_backward` reads (else None, None)."""
+    L = _lib.load()
+    N, T, H = f.shape
+    U = g.shape[1]
+    V = weight.shape[0]
+    dev = f.device
+    _mismatch.poll(dev)
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        lse = torch.empty((N, T, U), dtype=torch.float32, device=dev) if with_grads else None
+        grads = torch.empty((N, T, U, 2), dtype=torch.float32, device=dev) if with_grads else None
+        if N == 0:
+            return costs, lse, grads
+        ws = _joint_workspace(L, N, T, U, H, V, dev)
+        _check(L.rnnt_amd_joint_loss(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[f.dtype], ACTIVATIONS[activation],
+                                     f.data_ptr(), g.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(labels),
+                                     xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(lse), _ptr(grads),
+                                     N, T, U, H, V, blank, float(fastemit_lambda)))
+    return costs, lse, grads
+
+
+def joint_backward(f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs, activation="tanh", blank=0,
+                   need_f=True, need_g=True, need_weight=True, need_bias=True):
+    """d(sum_n grad_costs[n]*cost[n]) / d(f, g, weight, bias) of :func:`joint_loss`: df / dg in f's dtype, dweight /
+    dbias fp32; None for what is not asked for."""
+    L = _lib.load()
+    N, T, H = f.shape
+    U = g.shape[1]
+    V = weight.shape[0]
+    dev = f.device
+    with torch.cuda.device(dev):
+        df = torch.empty_like(f) if need_f else None
+        dg = torch.empty_like(g) if need_g else None
+        dw = torch.empty((V, H), dtype=torch.float32, device=dev) if need_weight else None
+        db = torch.empty((V,), dtype=torch.float32, device=dev) if (need_bias and bias is not None) else None
+        if N == 0:
+            for t in (df, dg, dw, db):
+                if t is not None:
+                    t.zero_()
+            return df, dg, dw, db
+        ws = _joint_workspace(L, N, T, U, H, V, dev)
+        _check(L.rnnt_amd_joint_backward(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[f.dtype], ACTIVATIONS[activation],
+                                         f.data_ptr(), g.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(labels),
+                                         xn.data_ptr(), yn.data_ptr(), lse.data_ptr(), grads.data_ptr(),
+                                         _ptr(grad_costs), _ptr(df), _ptr(dg), _ptr(dw), _ptr(db), N, T, U, H, V,
+                                         blank))
+    return df, dg, dw, db
