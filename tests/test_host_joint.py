@@ -117,3 +117,44 @@ def test_joint_front_end_refuses_sizes_and_activation():
         rnnt_loss_from_joint(*_args(), activation="gelu")
     with pytest.raises(RuntimeError, match="CUDA"):          # well-formed, but no GPU tensors
         rnnt_loss_from_joint(*_args())
+
+
+@pytest.mark.parametrize("case", [
+    # N, T, U (labels), V, H, act, blank, bias, lam
+    (3, 5, 3, 7, 32, "relu", 0, True, 0.0),
+    (2, 4, 2, 18, 64, "relu", 16, False, 0.05),
+    (3, 5, 3, 7, 32, "tanh", 6, False, 0.05),
+    (2, 4, 2, 18, 64, "tanh", 16, True, 0.0),
+], ids=lambda c: f"V{c[3]}_H{c[4]}_{c[5]}_bias{int(c[7])}_lam{c[8]}")
+def test_joint_reference_matches_autograd_fp64(case):
+    """tests/joint_reference.py (the fp64 comparator of tests/test_gpu_joint_edges.py) against the autograd fp64 joint of
+    tests/test_gpu_joint.py, without a GPU.  relu on inputs whose sums are exact in fp32 runs the reference as the
+    kernels do (E = fp32, act in fp32); tanh runs it in float64 throughout (act in fp32 would differ by its rounding)."""
+    from joint_reference import joint_reference
+    from test_gpu_joint import reference as autograd_reference
+    N, T, U, V, H, act, blank, with_bias, lam = case
+    gen = torch.Generator().manual_seed(N * 1000 + V)
+    # values on a grid of 1/64 below 4 in magnitude: f + g and relu(f + g) are exact in fp32
+    f = torch.randint(-128, 129, (N, T, H), generator=gen).double() / 64
+    g = torch.randint(-128, 129, (N, U + 1, H), generator=gen).double() / 64
+    w = torch.randn(V, H, generator=gen, dtype=torch.float64) / H ** 0.5
+    b = torch.randn(V, generator=gen, dtype=torch.float64) * 0.1 if with_bias else torch.zeros(V, dtype=torch.float64)
+    labels = ((blank + 1 + torch.randint(0, V - 1, (N, U), generator=gen)) % V).to(torch.int32)
+    labels[0, 0] = V - 1 if blank != V - 1 else 0
+    xn = torch.tensor([T] + [T - 1 - i % 2 for i in range(N - 1)], dtype=torch.int32)
+    yn = torch.tensor([U] + [i % (U + 1) for i in range(N - 1)], dtype=torch.int32)
+    up = torch.linspace(0.5, 2.0, N, dtype=torch.float64)
+    if act == "relu":
+        # the reference stages W in E = fp32: the autograd joint gets the same fp32-valued weight and bias
+        w, b = w.float().double(), b.float().double()
+        ins = dict(f=f.float(), g=g.float(), weight=w.float(), bias=b.float() if with_bias else None)
+        kw = {}
+    else:
+        ins = dict(f=f, g=g, weight=w, bias=b if with_bias else None)
+        kw = dict(act_dtype=torch.float64)
+    rc, rf, rg, rw, rb = autograd_reference(f, g, w, b, labels, xn, yn, act, blank, lam, up)
+    c, df, dg, dw, db = joint_reference(**ins, labels=labels, xn=xn, yn=yn, act=act, blank=blank,
+                                        fastemit_lambda=lam, upstream=up, **kw)
+    for got, ref, name in ((c, rc, "costs"), (df, rf, "f"), (dg, rg, "g"), (dw, rw, "weight"), (db, rb, "bias")):
+        err = float((got - ref).abs().max() / ref.abs().max())
+        assert err < 1e-10, (name, err)

@@ -58,13 +58,21 @@ def check_joint_inputs(f, g, weight, bias, labels, xn, yn, activation, blank):
                 raise RuntimeError(f"{name} must be on the device of f ({f.device}), not {x.device}")
 
 
+def _aligned(x):
+    """x contiguous at a 16-byte aligned address, as the C entries require of f, g and weight (their kernels read
+    16-byte fragments): a contiguous view at another offset (``buf[1:].view(...)``, a slice of a packed parameter) is
+    cloned."""
+    x = x.contiguous()
+    return x if x.data_ptr() % 16 == 0 else x.clone()
+
+
 class RNNTLossFromJoint(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, f, g, weight, bias, labels, frames_lengths, labels_lengths, activation, blank, fastemit_lambda,
                 with_grads):
-        fc, gc = f.contiguous(), g.contiguous()
-        w = weight.to(fc.dtype).contiguous()                     # W staged in the activations' dtype
+        fc, gc = _aligned(f), _aligned(g)
+        w = _aligned(weight.to(fc.dtype))                        # W staged in the activations' dtype
         b = bias.to(torch.float32).contiguous() if bias is not None else None
         labels, xn, yn = labels.contiguous(), frames_lengths.contiguous(), labels_lengths.contiguous()
         costs, lse, grads = ops.joint_loss(fc, gc, w, b, labels, xn, yn, activation, blank, fastemit_lambda,
