@@ -40,8 +40,9 @@ struct Workspace {
     unsigned long long* mail;   // boundary-column rings of k_lattice_wd (kernels.h)
 };
 
-size_t carve(void* base, int N, int T, int U, Workspace* w) {
-    const size_t cells = (size_t)N * T * U;
+// One layout for the padded and the compact form: `cells` lattice cells (N*T*U / STU), rings for sweeps of shape (T, U)
+// (the compact form: its launch bounds), `pad` bytes behind everything (the compact form's ALIGN).
+size_t carve(void* base, size_t cells, int N, int T, int U, size_t pad, Workspace* w) {
     size_t off = 0;
     char* p = static_cast<char*>(base);
     auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return p ? p + o : nullptr; };
@@ -54,7 +55,20 @@ size_t carve(void* base, int N, int T, int U, Workspace* w) {
     // (reserved by SHAPE, never by the current route: the size of a workspace must not depend on a setting)
     unsigned long long* mail = reinterpret_cast<unsigned long long*>(take(lattice_mail_bytes(N, T, U)));
     if (w) *w = Workspace{alphas, betas, ws2, ll, mismatch, redo, mail};
-    return off;
+    return off + pad;
+}
+size_t carve(void* base, int N, int T, int U, Workspace* w) { return carve(base, (size_t)N * T * U, N, T, U, 0, w); }
+
+inline bool vocab_ok(int V, int blank) { return V >= 1 && blank >= 0 && blank < V; }
+inline bool dtype_ok(int dtype) { return dtype == RNNT_DTYPE_F32 || dtype == RNNT_DTYPE_BF16 || dtype == RNNT_DTYPE_F16; }
+inline bool aligned(const void* p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to == 0; }
+inline bool workspace_ok(const void* workspace) { return workspace && aligned(workspace, ALIGN); }
+// what launch_split_pairs / launch_unskew / launch_expand_split ask of a pair plane and the two planes it is parked in
+inline bool split_aligned(const float* pairs, const float* a, const float* b) {
+    return aligned(pairs, 16) && aligned(a, 8) && aligned(b, 8);
+}
+inline hipError_t fill_nan(float* costs, size_t N, hipStream_t stream) {
+    return hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(costs), 0x7fc00000, N, stream);
 }
 
 bool dims_ok(int N, int T, int U) {
@@ -63,6 +77,42 @@ bool dims_ok(int N, int T, int U) {
     if ((int64_t)T * U >= (int64_t)1 << 29) return false;      // per-utterance plane < 4 GiB of float2 (buffer descriptors)
     if ((int64_t)N * T * U >= (int64_t)1 << 32) return false;  // flat cell index is 32-bit
     return true;
+}
+bool compact_dims_ok(int N, int64_t STU, int Tmax, int Umax) {
+    return dims_ok(N, Tmax > 0 ? Tmax : 1, Umax > 0 ? Umax : 1) && STU >= 0 && STU < ((int64_t)1 << 32);
+}
+
+LatticeArgs sweep_args(const Workspace& w, const int* xn, const int* yn, int N, int T, int U, const int64_t* offs) {
+    return LatticeArgs{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, T, U, 2, 0, offs, w.redo, w.redo + 2 * N, w.mail};
+}
+
+// Steps 2 and 3 of a loss call on a carved workspace whose pair plane is filled: the alpha / beta sweeps of shape (T, U),
+// then costs, guard and the gradient pairs, written by `writer` into gout (nullptr: the sweeps only).  offs: the compact
+// layout's cell offsets, nullptr for padded planes; prepared: LatticeArgs::prepared (the producer of the pairs carried
+// the ring kernel's RingPrep).
+rnntStatus_t sweeps_and_pair_grads(rnntStream_t stream, const Workspace& w, const int* xn, const int* yn, float* costs,
+                                   float* gout, int writer, int N, int T, int U, const int64_t* offs,
+                                   float fastemit_lambda, int prepared = 0) {
+    LatticeArgs la = sweep_args(w, xn, yn, N, T, U, offs);
+    la.prepared = prepared;
+    if (launch_lattice(stream, la, N, LOAD_SKEWED) != hipSuccess) return RNNT_STATUS_WARP_FAILED;
+    if (!gout) return RNNT_STATUS_SUCCESS;
+    GradArgs ga{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, gout, costs, w.mismatch,
+                T, U, 2, 0, fastemit_lambda, offs};
+    if (launch_grads(stream, ga, N, LOAD_SKEWED, writer) != hipSuccess) return RNNT_STATUS_GRADS_BLANK_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// The staged forms of run_warp_rnnt / run_warp_rnnt_gather behind their sweeps: gradient pairs in place of the log-prob
+// pairs staged in `grads`, then parked as two planes in the caller's alphas / betas (dead by then)
+rnntStatus_t grads_in_place_then_split(rnntStream_t stream, float* grads, const int* xn, const int* yn, float* alphas,
+                                       float* betas, const float* ll, float* costs, int N, int T, int U,
+                                       float fastemit_lambda) {
+    GradArgs gs{grads, nullptr, xn, yn, alphas, betas, ll, grads, costs, nullptr, T, U, 2, 0, fastemit_lambda};
+    if (launch_grads(stream, gs, N, LOAD_SKEWED, WRITE_SKEWED2) != hipSuccess) return RNNT_STATUS_GRADS_BLANK_FAILED;
+    if (launch_split_pairs(stream, grads, alphas, betas, (size_t)N * T * U) != hipSuccess)
+        return RNNT_STATUS_GRADS_LABEL_FAILED;
+    return RNNT_STATUS_SUCCESS;
 }
 
 }  // namespace
@@ -110,7 +160,7 @@ rnntStatus_t run_warp_rnnt(rnntStream_t stream, unsigned int* counts, float* alp
                            const int* labels, const float* log_probs, float* grads, float* costs,
                            const int* xn, const int* yn, int N, int T, int U, int V, int blank,
                            float fastemit_lambda) {
-    if (!dims_ok(N, T, U) || V < 1 || blank < 0 || blank >= V) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dims_ok(N, T, U) || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (N == 0) return RNNT_STATUS_SUCCESS;
     float* ll = reinterpret_cast<float*>(counts);   // (N,2U) uint32 scratch: first N words reused
     const size_t cells = (size_t)N * T * U;
@@ -125,7 +175,7 @@ rnntStatus_t run_warp_rnnt(rnntStream_t stream, unsigned int* counts, float* alp
         int* redo = nullptr;
         unsigned long long* mail = nullptr;
         const size_t flag_bytes = align_up(((size_t)N * 2 + 2) * sizeof(int)), ring_bytes = lattice_mail_bytes(N, T, U);
-        if (reinterpret_cast<uintptr_t>(base) % ALIGN == 0 && off + flag_bytes + align_up(ring_bytes) <= avail) {
+        if (aligned(base, ALIGN) && off + flag_bytes + align_up(ring_bytes) <= avail) {
             redo = reinterpret_cast<int*>(base + off);
             off += flag_bytes;
             mail = reinterpret_cast<unsigned long long*>(base + off);
@@ -141,12 +191,10 @@ rnntStatus_t run_warp_rnnt(rnntStream_t stream, unsigned int* counts, float* alp
         // dead by then -- and expanded from there into whole dense rows, zeros included: the staging area is
         // overwritten with the rest, and nothing depends on the caller's zero-fill any more (the slot writes of the
         // direct form below cost 0.8 ms at N=16, T=1500, U=300, V=50, this 0.37)
-        const bool split_ok = reinterpret_cast<uintptr_t>(grads) % 16 == 0 && reinterpret_cast<uintptr_t>(alphas) % 8 == 0 &&
-                              reinterpret_cast<uintptr_t>(betas) % 8 == 0;
-        if (split_ok) {
-            GradArgs gs{grads, nullptr, xn, yn, alphas, betas, ll, grads, costs, nullptr, T, U, 2, 0, fastemit_lambda};
-            if (launch_grads(stream, gs, N, LOAD_SKEWED, WRITE_SKEWED2) != hipSuccess) return RNNT_STATUS_GRADS_BLANK_FAILED;
-            if (launch_split_pairs(stream, grads, alphas, betas, cells) != hipSuccess) return RNNT_STATUS_GRADS_LABEL_FAILED;
+        if (split_aligned(grads, alphas, betas)) {
+            const rnntStatus_t st = grads_in_place_then_split(stream, grads, xn, yn, alphas, betas, ll, costs, N, T, U,
+                                                              fastemit_lambda);
+            if (st != RNNT_STATUS_SUCCESS) return st;
             if (launch_expand_split(stream, alphas, betas, labels, xn, yn, grads, N, T, U, V, blank) != hipSuccess)
                 return RNNT_STATUS_GRADS_LABEL_FAILED;
             return RNNT_STATUS_SUCCESS;
@@ -171,9 +219,7 @@ rnntStatus_t run_warp_rnnt_gather(rnntStream_t stream, unsigned int* counts, flo
     if (N == 0) return RNNT_STATUS_SUCCESS;
     float* ll = reinterpret_cast<float*>(counts);
     const size_t cells = (size_t)N * T * U;
-    const bool staged = cells >= STAGED_FROM_CELLS && reinterpret_cast<uintptr_t>(grads) % 16 == 0 &&
-                        reinterpret_cast<uintptr_t>(alphas) % 8 == 0 && reinterpret_cast<uintptr_t>(betas) % 8 == 0;
-    if (staged) {
+    if (cells >= STAGED_FROM_CELLS && split_aligned(grads, alphas, betas)) {
         // (N,T,U,2) grads = one pair plane: staging area first, result afterwards.  No room for hand-over rings here:
         // the sweeps run on the single-workgroup log-domain kernel.
         if (launch_reskew(stream, log_probs, grads, N, T, U) != hipSuccess) return RNNT_STATUS_WARP_FAILED;
@@ -182,9 +228,9 @@ rnntStatus_t run_warp_rnnt_gather(rnntStream_t stream, unsigned int* counts, flo
         // gradient pairs in place of the log-prob pairs, parked in alphas / betas (dead by then), turned back into the
         // row-major layout through LDS tiles: three coalesced passes (33 + 35 + 30 us at N=16, T=1500, U=300) instead
         // of one whose row-major reads and writes are scattered over the diagonal-major thread order (158 us)
-        GradArgs gs{grads, nullptr, xn, yn, alphas, betas, ll, grads, costs, nullptr, T, U, 2, 0, fastemit_lambda};
-        if (launch_grads(stream, gs, N, LOAD_SKEWED, WRITE_SKEWED2) != hipSuccess) return RNNT_STATUS_GRADS_BLANK_FAILED;
-        if (launch_split_pairs(stream, grads, alphas, betas, cells) != hipSuccess) return RNNT_STATUS_GRADS_LABEL_FAILED;
+        const rnntStatus_t st = grads_in_place_then_split(stream, grads, xn, yn, alphas, betas, ll, costs, N, T, U,
+                                                          fastemit_lambda);
+        if (st != RNNT_STATUS_SUCCESS) return st;
         if (launch_unskew(stream, alphas, betas, grads, N, T, U) != hipSuccess) return RNNT_STATUS_GRADS_LABEL_FAILED;
         return RNNT_STATUS_SUCCESS;
     }
@@ -197,31 +243,16 @@ rnntStatus_t run_warp_rnnt_gather(rnntStream_t stream, unsigned int* counts, flo
     return RNNT_STATUS_SUCCESS;
 }
 
-// Step 3 of a loss call on the workspace's pair plane, after the sweeps: costs, guard and the gradient pairs, written by
-// `writer` into gout
-static rnntStatus_t pair_grads(rnntStream_t stream, const Workspace& w, const int* xn, const int* yn, float* costs,
-                               float* gout, int writer, int N, int T, int U, float fastemit_lambda) {
-    GradArgs ga{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, gout, costs, w.mismatch,
-                T, U, 2, 0, fastemit_lambda};
-    if (launch_grads(stream, ga, N, LOAD_SKEWED, writer) != hipSuccess)
-        return RNNT_STATUS_GRADS_BLANK_FAILED;
-    return RNNT_STATUS_SUCCESS;
-}
-
 // rnnt_amd_loss with the element type of the input (RNNT_DTYPE_*: anything but fp32 for RNNT_IN_LOGITS_DENSE only)
 static rnntStatus_t loss_of_type(rnntStream_t stream, void* workspace, int input_kind, int dtype, const void* input_any,
                                  const int* labels, const int* xn, const int* yn, float* costs, float* grads,
                                  int grads_kind, int N, int T, int U, int V, int blank, float fastemit_lambda) {
-    if (dtype != RNNT_DTYPE_F32 && (input_kind != RNNT_IN_LOGITS_DENSE || (dtype != RNNT_DTYPE_BF16 && dtype != RNNT_DTYPE_F16)))
+    if (!dtype_ok(dtype) || (dtype != RNNT_DTYPE_F32 && input_kind != RNNT_IN_LOGITS_DENSE))
         return RNNT_STATUS_INVALID_ARGUMENT;
     const float* input = static_cast<const float*>(input_any);      // (fp32 input kinds only)
-    if (!dims_ok(N, T, U) || !workspace) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (reinterpret_cast<uintptr_t>(workspace) % ALIGN) return RNNT_STATUS_INVALID_ARGUMENT;
-    const bool gathered_in = input_kind == RNNT_IN_LOG_PROBS_GATHERED;
-    if (!gathered_in) {
-        if (V < 1 || blank < 0 || blank >= V) return RNNT_STATUS_INVALID_ARGUMENT;
-        if (U > 1 && !labels) return RNNT_STATUS_INVALID_ARGUMENT;
-    }
+    if (!dims_ok(N, T, U) || !workspace_ok(workspace)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (input_kind != RNNT_IN_LOG_PROBS_GATHERED && (!vocab_ok(V, blank) || (U > 1 && !labels)))
+        return RNNT_STATUS_INVALID_ARGUMENT;
     if (grads_kind == RNNT_GRADS_DENSE && input_kind != RNNT_IN_LOG_PROBS_DENSE)
         return RNNT_STATUS_INVALID_ARGUMENT;
     if (grads_kind < RNNT_GRADS_GATHERED || grads_kind > RNNT_GRADS_NONE)
@@ -234,7 +265,7 @@ static rnntStatus_t loss_of_type(rnntStream_t stream, void* workspace, int input
 
     // 1. bring the (blank,label) log-prob pairs into the diagonal-major workspace -- and, where the sweeps are going to run on
     //    the ring kernel, let that launch prepare its flags and rings on the way (kernels.h: RingPrep)
-    LatticeArgs la{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, T, U, 2, 0, nullptr, w.redo, w.redo + 2 * N, w.mail};
+    LatticeArgs la = sweep_args(w, xn, yn, N, T, U, nullptr);
     RingPrep prep{nullptr, 0, nullptr, nullptr, 0};
     hipError_t e;
     switch (input_kind) {
@@ -245,19 +276,13 @@ static rnntStatus_t loss_of_type(rnntStream_t stream, void* workspace, int input
             la.prepared = lattice_ring_prep(stream, la, N, LOAD_SKEWED, &prep) ? 1 : 0;
             e = launch_reskew(stream, input, w.ws2, N, T, U, &prep); break;
         case RNNT_IN_LOGITS_DENSE:
-            e = dtype == RNNT_DTYPE_F32
-                    ? launch_log_softmax_gather_skewed(stream, input, labels, w.ws2, N, T, U, V, blank)
-                    : launch_log_softmax_gather_skewed_half(stream, dtype, input_any, labels, w.ws2, N, T, U, V, blank);
-            break;
+            e = launch_log_softmax_gather_skewed_typed(stream, dtype, input_any, labels, w.ws2, N, T, U, V, blank); break;
         default:
             return RNNT_STATUS_INVALID_ARGUMENT;
     }
     if (e != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
 
-    // 2. alpha / beta sweeps
-    if (launch_lattice(stream, la, N, LOAD_SKEWED) != hipSuccess) return RNNT_STATUS_WARP_FAILED;
-
-    // 3. gradients + costs (+ guard).  For a dense result the pairs are produced in place in the
+    // 2. alpha / beta sweeps, 3. gradients + costs (+ guard).  For a dense result the pairs are produced in place in the
     //    workspace and expanded to full rows (zeros included) in one coalesced pass.
     float* gout = grads;
     int writer = WRITE_SKEWED2;
@@ -266,16 +291,18 @@ static rnntStatus_t loss_of_type(rnntStream_t stream, void* workspace, int input
     const bool unskew_gathered = grads_kind == RNNT_GRADS_GATHERED && (size_t)N * T * U >= STAGED_FROM_CELLS;
     if (grads_kind == RNNT_GRADS_GATHERED && !unskew_gathered) writer = WRITE_ROWMAJOR2;   // (launch-bound sizes: direct)
     else if (grads_kind != RNNT_GRADS_GATHERED_DIAGONAL) gout = w.ws2;
-    if (grads_kind == RNNT_GRADS_DENSE && (size_t)N * T * U <= dense_in_one_launch_cells()) {
-        // launch-bound sizes: the gradient kernel and the expansion as one launch (c2 in bench.py: 0.0371 -> 0.0348 ms per
-        // step); the row writer reads its cells' values from the planes itself
+    // launch-bound sizes: the gradient kernel and the expansion as one launch (c2 in bench.py: 0.0371 -> 0.0348 ms per
+    // step); the row writer reads its cells' values from the planes itself
+    const bool dense_in_one = grads_kind == RNNT_GRADS_DENSE && (size_t)N * T * U <= dense_in_one_launch_cells();
+    const rnntStatus_t st = sweeps_and_pair_grads(stream, w, xn, yn, costs, dense_in_one ? nullptr : gout, writer, N, T, U,
+                                                  nullptr, fastemit_lambda, la.prepared);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (dense_in_one) {
         GradArgs gd{w.ws2, labels, xn, yn, w.alphas, w.betas, w.ll, nullptr, costs, w.mismatch, T, U, V, blank,
                     fastemit_lambda};
         if (launch_grads_dense(stream, gd, grads, N) != hipSuccess) return RNNT_STATUS_GRADS_BLANK_FAILED;
         return RNNT_STATUS_SUCCESS;
     }
-    const rnntStatus_t st = pair_grads(stream, w, xn, yn, costs, gout, writer, N, T, U, fastemit_lambda);
-    if (st != RNNT_STATUS_SUCCESS) return st;
     if (grads_kind == RNNT_GRADS_DENSE) {
         if (launch_expand(stream, w.ws2, labels, xn, yn, nullptr, grads, N, T, U, V, blank, 1) != hipSuccess)
             return RNNT_STATUS_EXPAND_FAILED;
@@ -297,7 +324,6 @@ rnntStatus_t rnnt_amd_loss(rnntStream_t stream, void* workspace, int input_kind,
 rnntStatus_t rnnt_amd_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits, const int* labels,
                                   const int* xn, const int* yn, float* costs, float* grads, int grads_kind, int N, int T,
                                   int U, int V, int blank, float fastemit_lambda) {
-    if (dtype != RNNT_DTYPE_F32 && dtype != RNNT_DTYPE_BF16 && dtype != RNNT_DTYPE_F16) return RNNT_STATUS_INVALID_ARGUMENT;
     return loss_of_type(stream, workspace, RNNT_IN_LOGITS_DENSE, dtype, logits, labels, xn, yn, costs, grads, grads_kind, N,
                         T, U, V, blank, fastemit_lambda);
 }
@@ -309,45 +335,14 @@ rnntStatus_t rnnt_amd_debug_lattice_only(rnntStream_t stream, void* workspace, c
     if (!dims_ok(N, T, U) || !workspace) return RNNT_STATUS_INVALID_ARGUMENT;
     Workspace w;
     carve(workspace, N, T, U, &w);
-    LatticeArgs la{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, T, U, 2, 0, nullptr, w.redo, w.redo + 2 * N, w.mail};
-    if (launch_lattice(stream, la, N, LOAD_SKEWED) != hipSuccess) return RNNT_STATUS_WARP_FAILED;
-    return RNNT_STATUS_SUCCESS;
+    return sweeps_and_pair_grads(stream, w, xn, yn, nullptr, nullptr, 0, N, T, U, nullptr, 0.f);
 }
-
-namespace {
-struct CompactWorkspace {
-    float* alphas;
-    float* betas;
-    float* ws2;
-    float* ll;
-    int* mismatch;
-    int* redo;                  // as Workspace::redo
-    unsigned long long* mail;   // as Workspace::mail, sized by the launch bounds (Tmax, Umax)
-};
-size_t carve_compact(void* base, int N, int64_t STU, int Tmax, int Umax, CompactWorkspace* w) {
-    size_t off = 0;
-    char* p = static_cast<char*>(base);
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return p ? p + o : nullptr; };
-    float* alphas = reinterpret_cast<float*>(take((size_t)STU * 4));
-    float* betas = reinterpret_cast<float*>(take((size_t)STU * 4));
-    float* ws2 = reinterpret_cast<float*>(take((size_t)STU * 8));
-    float* ll = reinterpret_cast<float*>(take((size_t)N * 4));
-    int* mismatch = reinterpret_cast<int*>(take((size_t)N * 4));
-    int* redo = reinterpret_cast<int*>(take(((size_t)N * 2 + 2) * sizeof(int)));
-    unsigned long long* mail = reinterpret_cast<unsigned long long*>(take(lattice_mail_bytes(N, Tmax, Umax)));
-    if (w) *w = CompactWorkspace{alphas, betas, ws2, ll, mismatch, redo, mail};
-    return off + ALIGN;
-}
-bool compact_dims_ok(int N, int64_t STU, int Tmax, int Umax) {
-    return dims_ok(N, Tmax > 0 ? Tmax : 1, Umax > 0 ? Umax : 1) && STU >= 0 && STU < ((int64_t)1 << 32);
-}
-}  // namespace
 
 // Diagnostics (bench.py: the gather kernel's own roofline entry): only step 1 of rnnt_amd_loss for dense log-probs,
 // i.e. k_to_diagonal<true> into the workspace's pair plane.
 rnntStatus_t rnnt_amd_debug_gather_only(rnntStream_t stream, void* workspace, const float* log_probs,
                                         const int* labels, int N, int T, int U, int V, int blank) {
-    if (!dims_ok(N, T, U) || !workspace || V < 1 || blank < 0 || blank >= V) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dims_ok(N, T, U) || !workspace || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (U > 1 && !labels) return RNNT_STATUS_INVALID_ARGUMENT;
     Workspace w;
     carve(workspace, N, T, U, &w);
@@ -358,7 +353,7 @@ rnntStatus_t rnnt_amd_debug_gather_only(rnntStream_t stream, void* workspace, co
 
 size_t rnnt_amd_workspace_size_compact(int N, int64_t STU, int Tmax, int Umax) {
     if (!compact_dims_ok(N, STU, Tmax, Umax)) return 0;
-    return carve_compact(nullptr, N, STU, Tmax > 0 ? Tmax : 1, Umax > 0 ? Umax : 1, nullptr);
+    return carve(nullptr, (size_t)STU, N, Tmax > 0 ? Tmax : 1, Umax > 0 ? Umax : 1, ALIGN, nullptr);
 }
 
 // Device-side preparation of a compact batch (offsets + launch bounds), one launch.
@@ -371,39 +366,43 @@ rnntStatus_t rnnt_amd_compact_offsets(rnntStream_t stream, const int* xn, const 
     return RNNT_STATUS_SUCCESS;
 }
 
-// Compact (ragged packed) layout: replaces run_gather_for_compact + run_warp_rnnt_compact
-// (core.h:41-54, core_compact.cu:360-436) with the conventions of the rest of this ABI
-// (status codes, caller's stream, no exit(), no host synchronisation).
-rnntStatus_t rnnt_amd_loss_compact(rnntStream_t stream, void* workspace, const float* xs, const int* ys,
-                                   const int* xn, const int* yn, const int64_t* cell_offsets,
-                                   const int* label_offsets, float* costs, float* grads2, int64_t* loc,
-                                   int N, int64_t STU, int Tmax, int Umax, int V, int blank,
-                                   float fastemit_lambda) {
-    if (!compact_dims_ok(N, STU, Tmax, Umax) || !workspace || V < 1 || blank < 0 || blank >= V)
-        return RNNT_STATUS_INVALID_ARGUMENT;
-    if (reinterpret_cast<uintptr_t>(workspace) % ALIGN) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (N == 0 || STU == 0) return RNNT_STATUS_SUCCESS;
-    CompactWorkspace w;
-    carve_compact(workspace, N, STU, Tmax > 0 ? Tmax : 1, Umax > 0 ? Umax : 1, &w);
-    float *alphas = w.alphas, *betas = w.betas, *ws2 = w.ws2, *ll = w.ll;
-    int* mismatch = w.mismatch;
-    if (launch_gather_compact(stream, xs, ys, xn, yn, cell_offsets, label_offsets, ws2, loc, N, Tmax, Umax, V,
-                              blank, STU) != hipSuccess)
-        return RNNT_STATUS_PROLOGUE_FAILED;
-    LatticeArgs la{ws2, nullptr, xn, yn, alphas, betas, ll, Tmax, Umax, 2, 0, cell_offsets, w.redo, w.redo + 2 * N, w.mail};
-    if (launch_lattice(stream, la, N, LOAD_SKEWED) != hipSuccess) return RNNT_STATUS_WARP_FAILED;
-    GradArgs ga{ws2, nullptr, xn, yn, alphas, betas, ll, grads2 ? grads2 : ws2, costs, mismatch,
-                Tmax, Umax, 2, 0, fastemit_lambda, cell_offsets};
-    if (launch_grads(stream, ga, N, LOAD_SKEWED, grads2 ? WRITE_ROWMAJOR2 : WRITE_SKEWED2) != hipSuccess)
-        return RNNT_STATUS_GRADS_BLANK_FAILED;
-    return RNNT_STATUS_SUCCESS;
+namespace {
+// What step 1 of a compact loss call reads: fp32 log-probs (STU,V) -- the gather also writes each row's label index to
+// loc -- or logits of `dtype`, through the fused log-softmax + gather over the packed rows (prologue.hip: CompactMap).
+struct CompactInput {
+    bool logits;
+    int dtype;
+    const void* rows;
+    int64_t* loc;
+};
+
+// The compact loss behind its entry's checks: step 1 by the kind of input, steps 2 and 3 with the cell offsets.
+// n_labels: what ys holds (< 0: label_offsets[N] labels, the kernels read no further).
+rnntStatus_t compact_core(rnntStream_t stream, void* workspace, const CompactInput& in, const int* ys, int64_t n_labels,
+                          const int* xn, const int* yn, const int64_t* cell_offsets, const int* label_offsets,
+                          float* costs, float* grads2, int N, int64_t STU, int Tmax, int Umax, int V, int blank,
+                          float fastemit_lambda) {
+    // (rnnt_amd_loss_compact_bounded looks at the vocabulary only here, behind its offsets: N == 0 and STU == 0 come first)
+    if (!vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    Workspace w;
+    carve(workspace, (size_t)STU, N, Tmax > 0 ? Tmax : 1, Umax > 0 ? Umax : 1, ALIGN, &w);
+    hipError_t e;
+    if (in.logits) {
+        const PackedRows cr{cell_offsets, label_offsets, xn, yn, ys, n_labels, STU, N};
+        e = launch_lsm_gather_compact_typed(stream, in.dtype, in.rows, w.ws2, cr, V, blank);
+    } else {
+        e = launch_gather_compact(stream, static_cast<const float*>(in.rows), ys, xn, yn, cell_offsets, label_offsets, w.ws2,
+                                  in.loc, N, Tmax, Umax, V, blank, STU);
+    }
+    if (e != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
+    return sweeps_and_pair_grads(stream, w, xn, yn, costs, grads2 ? grads2 : w.ws2, grads2 ? WRITE_ROWMAJOR2 : WRITE_SKEWED2,
+                                 N, Tmax, Umax, cell_offsets, fastemit_lambda);
 }
 
 // The same with the launch bounds supplied by the caller: the offsets are computed here, on the device, and what the
 // host would have checked after reading the maxima back is checked there too (prologue.hip: k_compact_offsets) -- no
 // host synchronisation anywhere, so the call can be captured into a HIP graph.  A batch whose lengths do not fit the
 // bounds, or whose totals are not STU / n_labels, gets NaN costs and zero gradients.
-namespace {
 struct BoundedExtra {
     int64_t* cell_offsets;   // (N+1,)
     int64_t* stats;          // (5,): the four of rnnt_amd_compact_offsets + "refused"
@@ -419,7 +418,44 @@ size_t carve_bounded(char* base, size_t off, int N, BoundedExtra* e) {
     if (e) *e = BoundedExtra{co, st, lo, xc};
     return off;
 }
+rnntStatus_t compact_bounded(rnntStream_t stream, void* workspace, const CompactInput& in, const int* ys, int64_t n_labels,
+                             const int* xn, const int* yn, float* costs, float* grads2, int N, int64_t STU, int Tmax,
+                             int Umax, int V, int blank, float fastemit_lambda) {
+    if (!compact_dims_ok(N, STU, Tmax, Umax) || !workspace_ok(workspace) || Tmax < 1 || Umax < 1 || n_labels < 0)
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    if (STU == 0) {
+        // utterances but no cells: no length >= 1 frame can add up to that, so the batch is one this entry always
+        // refuses -- and the kernels behind it return before they write anything.  Say so the way a refusal does.
+        return fill_nan(costs, (size_t)N, stream) == hipSuccess ? RNNT_STATUS_SUCCESS : RNNT_STATUS_COSTS_FAILED;
+    }
+    BoundedExtra e;
+    carve_bounded(static_cast<char*>(workspace), rnnt_amd_workspace_size_compact(N, STU, Tmax, Umax), N, &e);
+    const CompactBounds b{e.xn_checked, STU, n_labels, Tmax, Umax};
+    if (launch_compact_offsets(stream, xn, yn, N, e.cell_offsets, e.label_offsets, e.stats, &b) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    const rnntStatus_t st = compact_core(stream, workspace, in, ys, n_labels, e.xn_checked, yn, e.cell_offsets,
+                                         e.label_offsets, costs, grads2, N, STU, Tmax, Umax, V, blank, fastemit_lambda);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (launch_zero_if_refused(stream, e.stats + 4, grads2, (size_t)STU) != hipSuccess) return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
 }  // namespace
+
+// Compact (ragged packed) layout: replaces run_gather_for_compact + run_warp_rnnt_compact
+// (core.h:41-54, core_compact.cu:360-436) with the conventions of the rest of this ABI
+// (status codes, caller's stream, no exit(), no host synchronisation).
+rnntStatus_t rnnt_amd_loss_compact(rnntStream_t stream, void* workspace, const float* xs, const int* ys,
+                                   const int* xn, const int* yn, const int64_t* cell_offsets,
+                                   const int* label_offsets, float* costs, float* grads2, int64_t* loc,
+                                   int N, int64_t STU, int Tmax, int Umax, int V, int blank,
+                                   float fastemit_lambda) {
+    if (!compact_dims_ok(N, STU, Tmax, Umax) || !workspace_ok(workspace) || !vocab_ok(V, blank))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0 || STU == 0) return RNNT_STATUS_SUCCESS;
+    return compact_core(stream, workspace, CompactInput{false, RNNT_DTYPE_F32, xs, loc}, ys, -1, xn, yn, cell_offsets,
+                        label_offsets, costs, grads2, N, STU, Tmax, Umax, V, blank, fastemit_lambda);
+}
 
 size_t rnnt_amd_workspace_size_compact_bounded(int N, int64_t STU, int Tmax, int Umax) {
     const size_t base = rnnt_amd_workspace_size_compact(N, STU, Tmax, Umax);
@@ -431,98 +467,31 @@ rnntStatus_t rnnt_amd_loss_compact_bounded(rnntStream_t stream, void* workspace,
                                            int64_t n_labels, const int* xn, const int* yn, float* costs, float* grads2,
                                            int64_t* loc, int N, int64_t STU, int Tmax, int Umax, int V, int blank,
                                            float fastemit_lambda) {
-    if (!compact_dims_ok(N, STU, Tmax, Umax) || !workspace || Tmax < 1 || Umax < 1 || n_labels < 0)
-        return RNNT_STATUS_INVALID_ARGUMENT;
-    if (reinterpret_cast<uintptr_t>(workspace) % ALIGN) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (N == 0) return RNNT_STATUS_SUCCESS;
-    if (STU == 0) {
-        // utterances but no cells: no length >= 1 frame can add up to that, so the batch is one this entry always
-        // refuses -- and the kernels behind it return before they write anything.  Say so the way a refusal does.
-        if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(costs), 0x7fc00000, (size_t)N, stream) != hipSuccess)
-            return RNNT_STATUS_COSTS_FAILED;
-        return RNNT_STATUS_SUCCESS;
-    }
-    BoundedExtra e;
-    carve_bounded(static_cast<char*>(workspace), rnnt_amd_workspace_size_compact(N, STU, Tmax, Umax), N, &e);
-    const CompactBounds b{e.xn_checked, STU, n_labels, Tmax, Umax};
-    if (launch_compact_offsets(stream, xn, yn, N, e.cell_offsets, e.label_offsets, e.stats, &b) != hipSuccess)
-        return RNNT_STATUS_PROLOGUE_FAILED;
-    const rnntStatus_t st = rnnt_amd_loss_compact(stream, workspace, xs, ys, e.xn_checked, yn, e.cell_offsets,
-                                                  e.label_offsets, costs, grads2, loc, N, STU, Tmax, Umax, V, blank,
-                                                  fastemit_lambda);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    if (launch_zero_if_refused(stream, e.stats + 4, grads2, (size_t)STU) != hipSuccess) return RNNT_STATUS_EXPAND_FAILED;
-    return RNNT_STATUS_SUCCESS;
+    return compact_bounded(stream, workspace, CompactInput{false, RNNT_DTYPE_F32, xs, loc}, ys, n_labels, xn, yn, costs,
+                           grads2, N, STU, Tmax, Umax, V, blank, fastemit_lambda);
 }
 
-// The compact layout with LOGITS (fp32 / bf16 / fp16) in place of log-probs: the fused log-softmax + gather over the packed
-// rows (prologue.hip: CompactMap) replaces the gather, everything behind it is rnnt_amd_loss_compact's.
-namespace {
-bool compact_logits_args_ok(int dtype, int N, int64_t STU, int Tmax, int Umax, int V, int blank) {
-    return (dtype == RNNT_DTYPE_F32 || dtype == RNNT_DTYPE_BF16 || dtype == RNNT_DTYPE_F16) &&
-           compact_dims_ok(N, STU, Tmax, Umax) && V >= 1 && blank >= 0 && blank < V;
-}
-rnntStatus_t compact_logits_core(rnntStream_t stream, void* workspace, int dtype, const void* logits, const int* ys,
-                                 int64_t n_labels, const int* xn, const int* yn, const int64_t* cell_offsets,
-                                 const int* label_offsets, float* costs, float* grads2, int N, int64_t STU, int Tmax,
-                                 int Umax, int V, int blank, float fastemit_lambda) {
-    CompactWorkspace w;
-    carve_compact(workspace, N, STU, Tmax > 0 ? Tmax : 1, Umax > 0 ? Umax : 1, &w);
-    const PackedRows cr{cell_offsets, label_offsets, xn, yn, ys, n_labels, STU, N};
-    const hipError_t e = dtype == RNNT_DTYPE_F32
-                             ? launch_lsm_gather_compact(stream, static_cast<const float*>(logits), w.ws2, cr, V, blank)
-                             : launch_lsm_gather_compact_half(stream, dtype, logits, w.ws2, cr, V, blank);
-    if (e != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
-    LatticeArgs la{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, Tmax, Umax, 2, 0, cell_offsets, w.redo,
-                   w.redo + 2 * N, w.mail};
-    if (launch_lattice(stream, la, N, LOAD_SKEWED) != hipSuccess) return RNNT_STATUS_WARP_FAILED;
-    GradArgs ga{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, grads2 ? grads2 : w.ws2, costs, w.mismatch,
-                Tmax, Umax, 2, 0, fastemit_lambda, cell_offsets};
-    if (launch_grads(stream, ga, N, LOAD_SKEWED, grads2 ? WRITE_ROWMAJOR2 : WRITE_SKEWED2) != hipSuccess)
-        return RNNT_STATUS_GRADS_BLANK_FAILED;
-    return RNNT_STATUS_SUCCESS;
-}
-}  // namespace
-
+// The compact layout with LOGITS (fp32 / bf16 / fp16) in place of log-probs: the fused log-softmax + gather replaces the
+// gather, everything behind it is rnnt_amd_loss_compact's.
 rnntStatus_t rnnt_amd_loss_compact_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits,
                                           const int* ys, const int* xn, const int* yn, const int64_t* cell_offsets,
                                           const int* label_offsets, float* costs, float* grads2, int N, int64_t STU,
                                           int Tmax, int Umax, int V, int blank, float fastemit_lambda) {
-    if (!compact_logits_args_ok(dtype, N, STU, Tmax, Umax, V, blank) || !workspace) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (reinterpret_cast<uintptr_t>(workspace) % ALIGN) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dtype_ok(dtype) || !compact_dims_ok(N, STU, Tmax, Umax) || !vocab_ok(V, blank) || !workspace_ok(workspace))
+        return RNNT_STATUS_INVALID_ARGUMENT;
     if (Umax > 1 && !ys) return RNNT_STATUS_INVALID_ARGUMENT;
     if (N == 0 || STU == 0) return RNNT_STATUS_SUCCESS;
-    // (ys holds label_offsets[N] labels: the kernels read no further)
-    return compact_logits_core(stream, workspace, dtype, logits, ys, -1, xn, yn, cell_offsets, label_offsets, costs, grads2,
-                               N, STU, Tmax, Umax, V, blank, fastemit_lambda);
+    return compact_core(stream, workspace, CompactInput{true, dtype, logits, nullptr}, ys, -1, xn, yn, cell_offsets,
+                        label_offsets, costs, grads2, N, STU, Tmax, Umax, V, blank, fastemit_lambda);
 }
 
 rnntStatus_t rnnt_amd_loss_compact_logits_bounded(rnntStream_t stream, void* workspace, int dtype, const void* logits,
                                                   const int* ys, int64_t n_labels, const int* xn, const int* yn,
                                                   float* costs, float* grads2, int N, int64_t STU, int Tmax, int Umax,
                                                   int V, int blank, float fastemit_lambda) {
-    if (!compact_logits_args_ok(dtype, N, STU, Tmax, Umax, V, blank) || !workspace || Tmax < 1 || Umax < 1 ||
-        n_labels < 0)
-        return RNNT_STATUS_INVALID_ARGUMENT;
-    if (reinterpret_cast<uintptr_t>(workspace) % ALIGN) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (n_labels > 0 && !ys) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (N == 0) return RNNT_STATUS_SUCCESS;
-    if (STU == 0) {      // (as rnnt_amd_loss_compact_bounded: a batch this entry always refuses)
-        if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(costs), 0x7fc00000, (size_t)N, stream) != hipSuccess)
-            return RNNT_STATUS_COSTS_FAILED;
-        return RNNT_STATUS_SUCCESS;
-    }
-    BoundedExtra e;
-    carve_bounded(static_cast<char*>(workspace), rnnt_amd_workspace_size_compact(N, STU, Tmax, Umax), N, &e);
-    const CompactBounds b{e.xn_checked, STU, n_labels, Tmax, Umax};
-    if (launch_compact_offsets(stream, xn, yn, N, e.cell_offsets, e.label_offsets, e.stats, &b) != hipSuccess)
-        return RNNT_STATUS_PROLOGUE_FAILED;
-    const rnntStatus_t st = compact_logits_core(stream, workspace, dtype, logits, ys, n_labels, e.xn_checked, yn,
-                                                e.cell_offsets, e.label_offsets, costs, grads2, N, STU, Tmax, Umax, V,
-                                                blank, fastemit_lambda);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    if (launch_zero_if_refused(stream, e.stats + 4, grads2, (size_t)STU) != hipSuccess) return RNNT_STATUS_EXPAND_FAILED;
-    return RNNT_STATUS_SUCCESS;
+    if (!dtype_ok(dtype) || !vocab_ok(V, blank) || (n_labels > 0 && !ys)) return RNNT_STATUS_INVALID_ARGUMENT;
+    return compact_bounded(stream, workspace, CompactInput{true, dtype, logits, nullptr}, ys, n_labels, xn, yn, costs,
+                           grads2, N, STU, Tmax, Umax, V, blank, fastemit_lambda);
 }
 
 rnntStatus_t rnnt_amd_compact_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* ys,
@@ -530,16 +499,14 @@ rnntStatus_t rnnt_amd_compact_logits_backward(rnntStream_t stream, int dtype, co
                                               const int64_t* cell_offsets, const int* label_offsets,
                                               const float* grads2, const float* grad_costs, void* dlogits, int N,
                                               int64_t STU, int V, int blank) {
-    if (!compact_logits_args_ok(dtype, N, STU, 1, 1, V, blank) || n_labels < 0) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dtype_ok(dtype) || !compact_dims_ok(N, STU, 1, 1) || !vocab_ok(V, blank) || n_labels < 0)
+        return RNNT_STATUS_INVALID_ARGUMENT;
     if (n_labels > 0 && !ys) return RNNT_STATUS_INVALID_ARGUMENT;
     if (STU == 0) return RNNT_STATUS_SUCCESS;
     const PackedRows cr{cell_offsets, label_offsets, xn, yn, ys, n_labels, STU, N};
-    const hipError_t e =
-        dtype == RNNT_DTYPE_F32
-            ? launch_logits_backward_compact(stream, static_cast<const float*>(logits), grads2, grad_costs,
-                                             static_cast<float*>(dlogits), cr, V, blank)
-            : launch_logits_backward_compact_half(stream, dtype, logits, grads2, grad_costs, dlogits, cr, V, blank);
-    return e == hipSuccess ? RNNT_STATUS_SUCCESS : RNNT_STATUS_EXPAND_FAILED;
+    if (launch_logits_backward_compact_typed(stream, dtype, logits, grads2, grad_costs, dlogits, cr, V, blank) != hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
 }
 
 // Replaces run_scatter_grad_for_compact (core.h:56-60, core_compact.cu:456-500): dense (STU,V)
@@ -548,7 +515,7 @@ rnntStatus_t rnnt_amd_compact_logits_backward(rnntStream_t stream, int dtype, co
 rnntStatus_t rnnt_amd_compact_scatter_grads(rnntStream_t stream, const float* grad_costs,
                                             const float* grads2, const int64_t* loc, const int* cum_lens,
                                             float* dense_grads, int64_t STU, int N, int V, int blank) {
-    if (N < 0 || STU < 0 || V < 1 || blank < 0 || blank >= V) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N < 0 || STU < 0 || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (launch_scatter_compact(stream, grad_costs, grads2, loc, cum_lens, dense_grads, STU, N, V, blank) !=
         hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
@@ -575,7 +542,7 @@ static void compact_fail(rnntStatus_t st, const char* what, float* costs, unsign
     fprintf(stderr, "%s failed: rnnt status %d (%s)\n", what, (int)st,
             st == RNNT_STATUS_INVALID_ARGUMENT ? "invalid argument or unsupported size" : hipGetErrorString(err));
     if (costs && N) {
-        const hipError_t m = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(costs), 0x7fc00000, N, nullptr);
+        const hipError_t m = fill_nan(costs, N, nullptr);
         if (m != hipSuccess)
             fprintf(stderr, "%s: costs could not be set to NaN either (%s)\n", what, hipGetErrorString(m));
     }
@@ -621,8 +588,7 @@ void run_warp_rnnt_compact(unsigned int* counts, float* alphas, float* betas, co
     // back.  Five coalesced passes instead of two whose loads and stores are scattered over the diagonal-major thread
     // order.  Not for required_grad = false (alphas and grads alias betas there, binding.cpp:192-195) and not below
     // 2^20 cells of launch bound (launch-bound sizes keep the two-launch form).
-    const bool staged = required_grad && (size_t)N * T * U >= STAGED_FROM_CELLS && reinterpret_cast<uintptr_t>(grads) % 16 == 0 &&
-                        reinterpret_cast<uintptr_t>(alphas) % 8 == 0 && reinterpret_cast<uintptr_t>(betas) % 8 == 0 &&
+    const bool staged = required_grad && (size_t)N * T * U >= STAGED_FROM_CELLS && split_aligned(grads, alphas, betas) &&
                         grads != betas && alphas != betas;
     // (the staged form's first launch -- nothing of the caller's has been overwritten yet -- may be refused where the direct
     //  form is not, e.g. on its 2^31-workgroup grid limit: then the direct form runs)
@@ -676,7 +642,7 @@ rnntStatus_t rnnt_amd_expand_grads(rnntStream_t stream, const float* grads_diago
                                    const int* xn, const int* yn, const float* grad_costs,
                                    float* dense_grads, int N, int T, int U, int V, int blank,
                                    int overwrite) {
-    if (!dims_ok(N, T, U) || V < 1 || blank < 0 || blank >= V) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dims_ok(N, T, U) || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
     if ((int64_t)U * V >= (int64_t)1 << 31) return RNNT_STATUS_INVALID_ARGUMENT;
     if ((int64_t)N * T >= (int64_t)1 << 31) return RNNT_STATUS_INVALID_ARGUMENT;
     if (launch_expand(stream, grads_diagonal, labels, xn, yn, grad_costs, dense_grads, N, T, U, V, blank,
@@ -686,30 +652,22 @@ rnntStatus_t rnnt_amd_expand_grads(rnntStream_t stream, const float* grads_diago
 }
 
 // Backward of the fused RNNT_IN_LOGITS_DENSE path: d(sum_n grad_costs[n]*cost[n]) / d(logits).
-rnntStatus_t rnnt_amd_logits_backward(rnntStream_t stream, const float* logits, const int* labels,
-                                      const float* grads_diagonal, const float* grad_costs, float* dlogits,
-                                      int N, int T, int U, int V, int blank) {
-    if (!dims_ok(N, T, U) || V < 1 || blank < 0 || blank >= V) return RNNT_STATUS_INVALID_ARGUMENT;
+rnntStatus_t rnnt_amd_logits_backward_typed(rnntStream_t stream, int dtype, const void* logits, const int* labels,
+                                            const float* grads_diagonal, const float* grad_costs, void* dlogits,
+                                            int N, int T, int U, int V, int blank) {
+    if (!dtype_ok(dtype) || !dims_ok(N, T, U) || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (U > 1 && !labels) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (launch_logits_backward(stream, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
+    if (launch_logits_backward_typed(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
         hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
 
-rnntStatus_t rnnt_amd_logits_backward_typed(rnntStream_t stream, int dtype, const void* logits, const int* labels,
-                                            const float* grads_diagonal, const float* grad_costs, void* dlogits,
-                                            int N, int T, int U, int V, int blank) {
-    if (dtype == RNNT_DTYPE_F32)
-        return rnnt_amd_logits_backward(stream, static_cast<const float*>(logits), labels, grads_diagonal, grad_costs,
-                                        static_cast<float*>(dlogits), N, T, U, V, blank);
-    if (dtype != RNNT_DTYPE_BF16 && dtype != RNNT_DTYPE_F16) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (!dims_ok(N, T, U) || V < 1 || blank < 0 || blank >= V) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (U > 1 && !labels) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (launch_logits_backward_half(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
-        hipSuccess)
-        return RNNT_STATUS_EXPAND_FAILED;
-    return RNNT_STATUS_SUCCESS;
+rnntStatus_t rnnt_amd_logits_backward(rnntStream_t stream, const float* logits, const int* labels,
+                                      const float* grads_diagonal, const float* grad_costs, float* dlogits,
+                                      int N, int T, int U, int V, int blank) {
+    return rnnt_amd_logits_backward_typed(stream, RNNT_DTYPE_F32, logits, labels, grads_diagonal, grad_costs, dlogits, N, T,
+                                          U, V, blank);
 }
 
 // The joint network fused into the loss (joint.hip).  Workspace: rnnt_amd_workspace_size's carve, then W^T (H,Vp) for
@@ -733,11 +691,13 @@ size_t carve_joint(void* base, int N, int T, int U, int H, int V, JointWorkspace
     return off;
 }
 bool joint_args_ok(int dtype, int activation, int N, int T, int U, int H, int V, int blank) {
-    return (dtype == RNNT_DTYPE_F32 || dtype == RNNT_DTYPE_BF16 || dtype == RNNT_DTYPE_F16) &&
-           (activation == RNNT_ACT_TANH || activation == RNNT_ACT_RELU) && dims_ok(N, T, U) && H >= 32 && H <= 1024 &&
-           H % 32 == 0 && V >= 2 && V <= (1 << 24) && blank >= 0 && blank < V;
+    return dtype_ok(dtype) && (activation == RNNT_ACT_TANH || activation == RNNT_ACT_RELU) && dims_ok(N, T, U) &&
+           H >= 32 && H <= 1024 && H % 32 == 0 && V >= 2 && V <= (1 << 24) && vocab_ok(V, blank);
 }
-inline bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+// f, g and the weight are read in 16-byte words, the bias (optional) as floats
+inline bool joint_inputs_aligned(const void* f, const void* g, const void* weight, const float* bias) {
+    return aligned(f, 16) && aligned(g, 16) && aligned(weight, 16) && aligned(bias, 4);
+}
 }  // namespace
 
 size_t rnnt_amd_joint_workspace_size(int N, int T, int U, int H, int V) {
@@ -750,11 +710,9 @@ rnntStatus_t rnnt_amd_joint_loss(rnntStream_t stream, void* workspace, int dtype
                                  const int* yn, float* costs, float* lse, float* grads, int N, int T, int U, int H, int V,
                                  int blank, float fastemit_lambda) {
     if (!joint_args_ok(dtype, activation, N, T, U, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (!workspace || !f || !g || !weight || !xn || !yn || !costs || (U > 1 && !labels) || (grads && !lse))
+    if (!workspace_ok(workspace) || !f || !g || !weight || !xn || !yn || !costs || (U > 1 && !labels) || (grads && !lse))
         return RNNT_STATUS_INVALID_ARGUMENT;
-    if (reinterpret_cast<uintptr_t>(workspace) % ALIGN || !al16(f) || !al16(g) || !al16(weight) ||
-        reinterpret_cast<uintptr_t>(bias) % 4)
-        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!joint_inputs_aligned(f, g, weight, bias)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (N == 0) return RNNT_STATUS_SUCCESS;
     Workspace w;
     carve(workspace, N, T, U, &w);
@@ -764,9 +722,8 @@ rnntStatus_t rnnt_amd_joint_loss(rnntStream_t stream, void* workspace, int dtype
                          T, U, H, V, blank) != hipSuccess)
         return RNNT_STATUS_PROLOGUE_FAILED;
     // 2. + 3. as rnnt_amd_loss_logits(RNNT_GRADS_GATHERED_DIAGONAL or RNNT_GRADS_NONE)
-    LatticeArgs la{w.ws2, nullptr, xn, yn, w.alphas, w.betas, w.ll, T, U, 2, 0, nullptr, w.redo, w.redo + 2 * N, w.mail};
-    if (launch_lattice(stream, la, N, LOAD_SKEWED) != hipSuccess) return RNNT_STATUS_WARP_FAILED;
-    return pair_grads(stream, w, xn, yn, costs, grads ? grads : w.ws2, WRITE_SKEWED2, N, T, U, fastemit_lambda);
+    return sweeps_and_pair_grads(stream, w, xn, yn, costs, grads ? grads : w.ws2, WRITE_SKEWED2, N, T, U, nullptr,
+                                 fastemit_lambda);
 }
 
 rnntStatus_t rnnt_amd_joint_backward(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
@@ -775,11 +732,9 @@ rnntStatus_t rnnt_amd_joint_backward(rnntStream_t stream, void* workspace, int d
                                      const float* grad_costs, void* df, void* dg, float* dweight, float* dbias, int N,
                                      int T, int U, int H, int V, int blank) {
     if (!joint_args_ok(dtype, activation, N, T, U, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (!workspace || !f || !g || !weight || !xn || !yn || !lse || !grads || (U > 1 && !labels))
+    if (!workspace_ok(workspace) || !f || !g || !weight || !xn || !yn || !lse || !grads || (U > 1 && !labels))
         return RNNT_STATUS_INVALID_ARGUMENT;
-    if (reinterpret_cast<uintptr_t>(workspace) % ALIGN || !al16(f) || !al16(g) || !al16(weight) ||
-        reinterpret_cast<uintptr_t>(bias) % 4 || reinterpret_cast<uintptr_t>(grads) % 8)
-        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!joint_inputs_aligned(f, g, weight, bias) || !aligned(grads, 8)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (N == 0 || (!df && !dg && !dweight && !dbias)) return RNNT_STATUS_SUCCESS;
     JointWorkspace jw;
     carve_joint(workspace, N, T, U, H, V, &jw);
@@ -791,17 +746,13 @@ rnntStatus_t rnnt_amd_joint_backward(rnntStream_t stream, void* workspace, int d
 }
 
 rnntStatus_t rnnt_amd_log_softmax_typed(rnntStream_t stream, int dtype, const void* x, float* out, int64_t rows, int V) {
-    if (dtype == RNNT_DTYPE_F32) return rnnt_amd_log_softmax(stream, static_cast<const float*>(x), out, rows, V);
-    if (dtype != RNNT_DTYPE_BF16 && dtype != RNNT_DTYPE_F16) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (rows < 0 || V < 1) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (launch_log_softmax_half(stream, dtype, x, out, rows, V) != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
+    if (!dtype_ok(dtype) || rows < 0 || V < 1) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (launch_log_softmax_typed(stream, dtype, x, out, rows, V) != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
 
 rnntStatus_t rnnt_amd_log_softmax(rnntStream_t stream, const float* x, float* out, int64_t rows, int V) {
-    if (rows < 0 || V < 1) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (launch_log_softmax(stream, x, out, rows, V) != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
-    return RNNT_STATUS_SUCCESS;
+    return rnnt_amd_log_softmax_typed(stream, RNNT_DTYPE_F32, x, out, rows, V);
 }
 
 rnntStatus_t rnnt_amd_log_softmax_backward(rnntStream_t stream, const float* grad_out, const float* out,
@@ -814,7 +765,7 @@ rnntStatus_t rnnt_amd_log_softmax_backward(rnntStream_t stream, const float* gra
 
 rnntStatus_t rnnt_amd_gather(rnntStream_t stream, const float* log_probs, const int* labels,
                              float* gathered, int N, int T, int U, int V, int blank) {
-    if (!dims_ok(N, T, U) || V < 1 || blank < 0 || blank >= V) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dims_ok(N, T, U) || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (launch_gather(stream, log_probs, labels, gathered, N, T, U, V, blank, false) != hipSuccess)
         return RNNT_STATUS_PROLOGUE_FAILED;
     return RNNT_STATUS_SUCCESS;

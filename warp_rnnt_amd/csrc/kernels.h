@@ -178,14 +178,14 @@ hipError_t launch_log_softmax_gather_skewed(hipStream_t stream, const float* log
 hipError_t launch_logits_backward(hipStream_t stream, const float* logits, const int* labels,
                                   const float* g2_diagonal, const float* scale, float* dlogits, int N, int T,
                                   int U, int V, int blank);
-// the same three for half-precision logits (prologue_half.hip), dtype RNNT_DTYPE_BF16 or RNNT_DTYPE_F16: fp32 arithmetic
+// the same three for logits of any RNNT_DTYPE_* (prologue_half.hip; fp32 forwards to the launchers above): fp32 arithmetic
 // from the load on, pairs and log-probs in fp32, d/d logits in the logits' type (hipErrorInvalidValue for another dtype)
-hipError_t launch_log_softmax_half(hipStream_t stream, int dtype, const void* x, float* out, int64_t rows, int V);
-hipError_t launch_log_softmax_gather_skewed_half(hipStream_t stream, int dtype, const void* logits, const int* labels,
-                                                 float* ws2, int N, int T, int U, int V, int blank);
-hipError_t launch_logits_backward_half(hipStream_t stream, int dtype, const void* logits, const int* labels,
-                                       const float* g2_diagonal, const float* scale, void* dlogits, int N, int T,
-                                       int U, int V, int blank);
+hipError_t launch_log_softmax_typed(hipStream_t stream, int dtype, const void* x, float* out, int64_t rows, int V);
+hipError_t launch_log_softmax_gather_skewed_typed(hipStream_t stream, int dtype, const void* logits, const int* labels,
+                                                  float* ws2, int N, int T, int U, int V, int blank);
+hipError_t launch_logits_backward_typed(hipStream_t stream, int dtype, const void* logits, const int* labels,
+                                        const float* g2_diagonal, const float* scale, void* dlogits, int N, int T,
+                                        int U, int V, int blank);
 // The fused log-softmax modes over compact (ragged packed) logits (STU,V): row c belongs to utterance n = the first n with
 // offs[n+1] > c, as the (t,u) cell of its row-major (T_n, U_n = yn[n]+1) block.  A row that belongs to nobody -- outside
 // its owner's range, an owner whose range is not T_n*U_n rows or ends past STU, T_n < 1, a label index at or past nlab --
@@ -200,17 +200,17 @@ struct PackedRows {
     int64_t rows;          // STU
     int N;
 };
-// dtype RNNT_DTYPE_F32 here (prologue.hip), RNNT_DTYPE_BF16 / _F16 in the _half forms (prologue_half.hip):
+// fp32 (prologue.hip), and for any RNNT_DTYPE_* the _typed forms (prologue_half.hip; fp32 forwards):
 //   gather: the (blank,label) log-prob pair of every row into its utterance's skewed plane of the compact workspace;
 //   backward: d/d logits from the row-major (STU,2) pairs, scaled by scale[n] (nullptr: 1), in the logits' type
 hipError_t launch_lsm_gather_compact(hipStream_t stream, const float* logits, float* ws2, const PackedRows& cr, int V,
                                      int blank);
 hipError_t launch_logits_backward_compact(hipStream_t stream, const float* logits, const float* g2_rowmajor,
                                           const float* scale, float* dlogits, const PackedRows& cr, int V, int blank);
-hipError_t launch_lsm_gather_compact_half(hipStream_t stream, int dtype, const void* logits, float* ws2,
-                                          const PackedRows& cr, int V, int blank);
-hipError_t launch_logits_backward_compact_half(hipStream_t stream, int dtype, const void* logits, const float* g2_rowmajor,
-                                               const float* scale, void* dlogits, const PackedRows& cr, int V, int blank);
+hipError_t launch_lsm_gather_compact_typed(hipStream_t stream, int dtype, const void* logits, float* ws2,
+                                           const PackedRows& cr, int V, int blank);
+hipError_t launch_logits_backward_compact_typed(hipStream_t stream, int dtype, const void* logits, const float* g2_rowmajor,
+                                                const float* scale, void* dlogits, const PackedRows& cr, int V, int blank);
 hipError_t launch_expand(hipStream_t stream, const float* g2_skewed, const int* labels,
                          const int* xn, const int* yn, const float* scale, float* dense, int N,
                          int T, int U, int V, int blank, int overwrite_mode);

@@ -32,6 +32,16 @@ def _check(status):
                            " (" + STATUS_NAMES.get(status, "?") + ")")
 
 
+def _workspace(dev, size_fn, names, *dims):
+    """The uint8 workspace of ``size_fn(*dims)`` bytes; 0 = sizes the library does not take (``names``: the dims the
+    message spells out)."""
+    ws_bytes = size_fn(*dims)
+    if ws_bytes == 0:
+        raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes" +
+                           "".join(f" {k}={v}" for k, v in zip(names.split(), dims)))
+    return torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+
+
 def _mismatch_policy():
     """WARP_RNNT_AMD_CHECK_MISMATCH = warn | raise: read the guard flags back after every loss call
     (one host synchronisation: exact and immediate).  Unset (default): no read-back; the counterpart of the
@@ -67,11 +77,7 @@ def loss(input, labels, xn, yn, input_kind, grads_kind, blank=0, fastemit_lambda
             if return_mismatch:
                 return costs, grads, torch.zeros((0,), dtype=torch.int32, device=dev)
             return costs, grads
-        ws_bytes = L.rnnt_amd_workspace_size(N, T, U)
-        if ws_bytes == 0:
-            raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes "
-                               f"N={N} T={T} U={U}")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        ws = _workspace(dev, L.rnnt_amd_workspace_size, "N T U", N, T, U)
         _mismatch.poll(dev)          # (what an EARLIER call's kernels reported; sets the device's words up at first use)
         if input_kind == IN_LOGITS_DENSE and _half(input):
             st = L.rnnt_amd_loss_logits(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[input.dtype], input.data_ptr(),
@@ -178,6 +184,39 @@ def gather(log_probs, labels, blank=0):
     return out
 
 
+def _bounds_given(max_frames, max_labels):
+    if (max_frames is None) != (max_labels is None):
+        raise ValueError("max_frames and max_labels go together")
+    return max_frames is not None
+
+
+def _bounded_workspace(L, dev, N, STU, max_frames, max_labels):
+    """(workspace, Tmax, Umax) of a compact call with the caller's bounds."""
+    tmax, umax = int(max_frames), int(max_labels) + 1
+    if tmax < 1 or umax < 1:
+        raise ValueError("max_frames >= 1 and max_labels >= 0 expected")
+    return _workspace(dev, L.rnnt_amd_workspace_size_compact_bounded, "", N, STU, tmax, umax), tmax, umax
+
+
+def _compact_offsets(L, dev, xn, yn, N, offs, loffs):
+    """Enqueues the offsets of a compact batch into offs (N+1 offsets + the 4 stats) and loffs."""
+    _check(L.rnnt_amd_compact_offsets(_stream(dev), xn.data_ptr(), yn.data_ptr(), N, offs.data_ptr(),
+                                      loffs.data_ptr(), offs[N + 1:].data_ptr()))
+
+
+def _sized_workspace(L, dev, ys, xn, yn, N, STU, offs, loffs):
+    """(workspace, Tmax, Umax) of a compact call without bounds: the offsets, the one host synchronisation for the
+    maxima and sums, the shape checks of the reference's binding."""
+    _compact_offsets(L, dev, xn, yn, N, offs, loffs)
+    stats = offs[N + 1:].tolist()                                       # the one host sync
+    stu_chk, su, tmax, umax = int(stats[0]), int(stats[1]), int(stats[2]), int(stats[3]) + 1
+    if ys.numel() != su:
+        raise RuntimeError("ys shape must be equal to (sum(yn), )")
+    if STU != stu_chk:
+        raise RuntimeError("xs shape mismatch with (\\sum{xn*(yn+1)}, )")
+    return _workspace(dev, L.rnnt_amd_workspace_size_compact, "", N, STU, tmax, umax), tmax, umax
+
+
 def loss_compact(xs, ys, xn, yn, blank=0, fastemit_lambda=0.0, required_grad=True, max_frames=None, max_labels=None):
     """Compact (ragged packed) layout: xs (STU,V), ys (sum yn,), xn/yn (N,).
     Returns (costs (N,), grads (STU,2) or None, loc (STU,) int64).
@@ -191,8 +230,7 @@ def loss_compact(xs, ys, xn, yn, blank=0, fastemit_lambda=0.0, required_grad=Tru
     dev = xs.device
     N = xn.shape[0]
     STU, V = xs.shape
-    if (max_frames is None) != (max_labels is None):
-        raise ValueError("max_frames and max_labels go together")
+    bounded = _bounds_given(max_frames, max_labels)
     _mismatch.poll(dev)
     with torch.cuda.device(dev):
         costs = torch.empty((N,), dtype=torch.float32, device=dev)
@@ -200,37 +238,19 @@ def loss_compact(xs, ys, xn, yn, blank=0, fastemit_lambda=0.0, required_grad=Tru
         grads = torch.empty((STU, 2), dtype=torch.float32, device=dev) if required_grad else None
         if N == 0:
             return costs, grads, loc
-        if max_frames is not None:
-            tmax, umax = int(max_frames), int(max_labels) + 1
-            if tmax < 1 or umax < 1:
-                raise ValueError("max_frames >= 1 and max_labels >= 0 expected")
-            ws_bytes = L.rnnt_amd_workspace_size_compact_bounded(N, STU, tmax, umax)
-            if ws_bytes == 0:
-                raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes")
-            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        if bounded:
+            ws, tmax, umax = _bounded_workspace(L, dev, N, STU, max_frames, max_labels)
             _check(L.rnnt_amd_loss_compact_bounded(_stream(dev), ws.data_ptr(), xs.data_ptr(), _ptr(ys), ys.numel(),
                                                    xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(grads),
                                                    loc.data_ptr(), N, STU, tmax, umax, V, blank, float(fastemit_lambda)))
             return costs, grads, loc
         offs = torch.empty((N + 1 + 4,), dtype=torch.int64, device=dev)    # offsets + the 4 stats
         loffs = torch.empty((N + 1,), dtype=torch.int32, device=dev)
-        _check(L.rnnt_amd_compact_offsets(_stream(dev), xn.data_ptr(), yn.data_ptr(), N, offs.data_ptr(),
-                                          loffs.data_ptr(), offs[N + 1:].data_ptr()))
-        stats = offs[N + 1:].tolist()                                       # the one host sync
-        stu_chk, su, tmax, umax = int(stats[0]), int(stats[1]), int(stats[2]), int(stats[3]) + 1
-        if ys.numel() != su:
-            raise RuntimeError("ys shape must be equal to (sum(yn), )")
-        if STU != stu_chk:
-            raise RuntimeError("xs shape mismatch with (\\sum{xn*(yn+1)}, )")
-        ws_bytes = L.rnnt_amd_workspace_size_compact(N, STU, tmax, umax)
-        if ws_bytes == 0:
-            raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        st = L.rnnt_amd_loss_compact(_stream(dev), ws.data_ptr(), xs.data_ptr(), _ptr(ys), xn.data_ptr(),
-                                     yn.data_ptr(), offs.data_ptr(), loffs.data_ptr(), costs.data_ptr(),
-                                     _ptr(grads), loc.data_ptr(), N, STU, tmax, umax, V, blank,
-                                     float(fastemit_lambda))
-        _check(st)
+        ws, tmax, umax = _sized_workspace(L, dev, ys, xn, yn, N, STU, offs, loffs)
+        _check(L.rnnt_amd_loss_compact(_stream(dev), ws.data_ptr(), xs.data_ptr(), _ptr(ys), xn.data_ptr(),
+                                       yn.data_ptr(), offs.data_ptr(), loffs.data_ptr(), costs.data_ptr(),
+                                       _ptr(grads), loc.data_ptr(), N, STU, tmax, umax, V, blank,
+                                       float(fastemit_lambda)))
     return costs, grads, loc
 
 
@@ -244,8 +264,7 @@ def loss_compact_logits(logits, ys, xn, yn, blank=0, fastemit_lambda=0.0, requir
     dev = logits.device
     N = xn.shape[0]
     STU, V = logits.shape
-    if (max_frames is None) != (max_labels is None):
-        raise ValueError("max_frames and max_labels go together")
+    bounded = _bounds_given(max_frames, max_labels)
     if not 0 <= blank < V:
         raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes or blank")
     dtype = LOGITS_DTYPES[logits.dtype]
@@ -257,33 +276,15 @@ def loss_compact_logits(logits, ys, xn, yn, blank=0, fastemit_lambda=0.0, requir
         loffs = torch.empty((N + 1,), dtype=torch.int32, device=dev)
         if N == 0:
             return costs, grads, offs[:N + 1], loffs
-        if max_frames is not None:
-            tmax, umax = int(max_frames), int(max_labels) + 1
-            if tmax < 1 or umax < 1:
-                raise ValueError("max_frames >= 1 and max_labels >= 0 expected")
-            ws_bytes = L.rnnt_amd_workspace_size_compact_bounded(N, STU, tmax, umax)
-            if ws_bytes == 0:
-                raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes")
-            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        if bounded:
+            ws, tmax, umax = _bounded_workspace(L, dev, N, STU, max_frames, max_labels)
             _check(L.rnnt_amd_loss_compact_logits_bounded(
                 _stream(dev), ws.data_ptr(), dtype, logits.data_ptr(), _ptr(ys), ys.numel(), xn.data_ptr(),
                 yn.data_ptr(), costs.data_ptr(), _ptr(grads), N, STU, tmax, umax, V, blank, float(fastemit_lambda)))
             if required_grad:          # (enqueued only: the backward's offsets)
-                _check(L.rnnt_amd_compact_offsets(_stream(dev), xn.data_ptr(), yn.data_ptr(), N, offs.data_ptr(),
-                                                  loffs.data_ptr(), offs[N + 1:].data_ptr()))
+                _compact_offsets(L, dev, xn, yn, N, offs, loffs)
             return costs, grads, offs[:N + 1], loffs
-        _check(L.rnnt_amd_compact_offsets(_stream(dev), xn.data_ptr(), yn.data_ptr(), N, offs.data_ptr(),
-                                          loffs.data_ptr(), offs[N + 1:].data_ptr()))
-        stats = offs[N + 1:].tolist()                                       # the one host sync
-        stu_chk, su, tmax, umax = int(stats[0]), int(stats[1]), int(stats[2]), int(stats[3]) + 1
-        if ys.numel() != su:
-            raise RuntimeError("ys shape must be equal to (sum(yn), )")
-        if STU != stu_chk:
-            raise RuntimeError("xs shape mismatch with (\\sum{xn*(yn+1)}, )")
-        ws_bytes = L.rnnt_amd_workspace_size_compact(N, STU, tmax, umax)
-        if ws_bytes == 0:
-            raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes")
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        ws, tmax, umax = _sized_workspace(L, dev, ys, xn, yn, N, STU, offs, loffs)
         _check(L.rnnt_amd_loss_compact_logits(_stream(dev), ws.data_ptr(), dtype, logits.data_ptr(), _ptr(ys),
                                               xn.data_ptr(), yn.data_ptr(), offs.data_ptr(), loffs.data_ptr(),
                                               costs.data_ptr(), _ptr(grads), N, STU, tmax, umax, V, blank,
@@ -370,14 +371,6 @@ def log_softmax_backward(grad_out, out, grad_in=None):
 ACTIVATIONS = {"tanh": _lib.ACT_TANH, "relu": _lib.ACT_RELU}
 
 
-def _joint_workspace(L, N, T, U, H, V, dev):
-    ws_bytes = L.rnnt_amd_joint_workspace_size(N, T, U, H, V)
-    if ws_bytes == 0:
-        raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes "
-                           f"N={N} T={T} U={U} H={H} V={V}")
-    return torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-
-
 def joint_loss(f, g, weight, bias, labels, xn, yn, activation="tanh", blank=0, fastemit_lambda=0.0, with_grads=True):
     """The joint network fused into the loss: f (N,T,H), g (N,U,H), weight (V,H) of one dtype (fp32 / bf16 / fp16),
     bias (V,) fp32 or None; validated by the caller.  Returns costs (N,) fp32 and, with_grads, lse (N,T,U) fp32 and the
@@ -394,7 +387,7 @@ def joint_loss(f, g, weight, bias, labels, xn, yn, activation="tanh", blank=0, f
         grads = torch.empty((N, T, U, 2), dtype=torch.float32, device=dev) if with_grads else None
         if N == 0:
             return costs, lse, grads
-        ws = _joint_workspace(L, N, T, U, H, V, dev)
+        ws = _workspace(dev, L.rnnt_amd_joint_workspace_size, "N T U H V", N, T, U, H, V)
         _check(L.rnnt_amd_joint_loss(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[f.dtype], ACTIVATIONS[activation],
                                      f.data_ptr(), g.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(labels),
                                      xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(lse), _ptr(grads),
@@ -421,7 +414,7 @@ def joint_backward(f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs, a
                 if t is not None:
                     t.zero_()
             return df, dg, dw, db
-        ws = _joint_workspace(L, N, T, U, H, V, dev)
+        ws = _workspace(dev, L.rnnt_amd_joint_workspace_size, "N T U H V", N, T, U, H, V)
         _check(L.rnnt_amd_joint_backward(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[f.dtype], ACTIVATIONS[activation],
                                          f.data_ptr(), g.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(labels),
                                          xn.data_ptr(), yn.data_ptr(), lse.data_ptr(), grads.data_ptr(),
