@@ -226,7 +226,7 @@ def test_calls_stress():
 # 4. prologue kernels
 # ----------------------------------------------------------------------------
 # (1024 / 2048 / 3072 / 4096 / 5632 / 6144 / 8192 / 12288 / 16384: where the launcher changes kernel or workgroup
-#  shape, prologue.hip: dispatch_lsm, each with its neighbour on the other side;
+#  shape, lsm.h: dispatch_lsm, each with its neighbour on the other side;
 #  32 ... 128: the rows-in-registers kernel with 1, 2, 3 and 4 rows per group -- 50 is c4 -- and its neighbours that
 #  fall back to the LDS-staged one (below 32 -- c2's 28 -- always: its straight-line row pass for 9 ... 16 columns per
 #  lane, the run-time loops below that); 1003 rows: a tail that is no whole group;

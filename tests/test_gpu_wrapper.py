@@ -221,7 +221,7 @@ def test_non_default_stream_and_device_guard():
     np.testing.assert_allclose(tot.item(), ref["costs"].sum(), rtol=1e-5)
 
 
-# V = 32, 64, 128, 256 and V % 4 == 0 from 448 on: the rows-in-registers fused gather (prologue.hip: k_lsm_rows, 8 ... 64
+# V = 32, 64, 128, 256 and V % 4 == 0 from 448 on: the rows-in-registers fused gather (lsm.h: k_lsm_rows, 8 ... 64
 # lanes per row, ragged last float4; k_lsm_rows_diag for V = 32, 64 and its T < 16 fallback); the others stay on the LDS
 # tiles (straight-line row pass for 9 ... 16 columns per lane: 34 ... 258 here; run-time loops below: V=7)
 @pytest.mark.parametrize("N,Tm,Um,V", [(3, 30, 12, 50), (2, 9, 5, 5000), (2, 11, 70, 7), (2, 6, 4, 1030),

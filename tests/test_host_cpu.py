@@ -451,11 +451,11 @@ def test_the_build_refuses_a_planted_reload_violation(monkeypatch):
 
 def test_compile_time_switches_are_the_kept_builds_only():
     """Every RNNT_* macro the native sources test in a preprocessor conditional belongs to a build that has a user: the
-    four _build.VARIANTS, the diagnostics build of tools/wd_trace.py (RNNT_WD_STATS) and the half-precision translation
-    unit (RNNT_PROLOGUE_LSM_ONLY).  A new experiment switch is added here on purpose or goes through ab_getenv (common.h)."""
+    four _build.VARIANTS and the diagnostics build of tools/wd_trace.py (RNNT_WD_STATS).  A new experiment switch is added
+    here on purpose or goes through ab_getenv (common.h)."""
     from warp_rnnt_amd import _build
     allowed = {"RNNT_AB_KNOBS", "RNNT_WD_SPIN_LIMIT", "RNNT_LATTICE_LEGACY", "RNNT_PRECISE_LIBM",
-               "RNNT_PLANT_RELOAD_VIOLATION", "RNNT_WD_STATS", "RNNT_PROLOGUE_LSM_ONLY"}
+               "RNNT_PLANT_RELOAD_VIOLATION", "RNNT_WD_STATS"}
     found = {}
     for d in (_build.CSRC, os.path.join(ROOT, "include")):
         for name in sorted(os.listdir(d)):
@@ -548,12 +548,28 @@ def test_the_isa_walk_sees_the_wait_state_hazards_around_inline_assembly(tmp_pat
     nk, ni, rest = _isa_check.require_no_asm_hazards(isa("\tv_exp_f32_e32 v5, v1\n\tv_add_f32_e32 v6, v5, v5\n"))
     assert (nk, ni, len(rest)) == (1, 3, 1)
     assert set(_build.HAZARD_CHECKED) <= set(_build.SOURCES) and "lattice_wd.hip" in _build.HAZARD_CHECKED
-    # every source that holds inline assembly is on the list
+    # every source that holds inline assembly -- in its own code or in a header it includes, directly or through another
+    # header; a comment that says "asm" is not code -- is on the list, and no source includes another source
+    # (only // comments are dropped, so a /* */ one that says "asm" still counts; includes with a path -- the C ABI header
+    # under include/, which has no code -- are not followed)
     import re
+
+    def code(name):
+        with open(os.path.join(_build.CSRC, name)) as f:
+            return re.sub(r"//[^\n]*", "", f.read())
+
+    def reach(name, seen):
+        if name not in seen:
+            seen.add(name)
+            for inc in re.findall(r'#include "(\w+\.\w+)"', code(name)):
+                assert inc.endswith(".h"), (name, inc)
+                reach(inc, seen)
+        return seen
+
     for src in _build.SOURCES:
-        text = open(os.path.join(_build.CSRC, src)).read()
-        incs = re.findall(r'#include "(\w+\.h)"', text)
-        holds = any(re.search(r"\basm\b", open(os.path.join(_build.CSRC, f)).read()) for f in [src] + incs)
+        files = reach(src, set())
+        assert files - {src} <= set(_build.HEADERS), (src, files)       # (what the fingerprint and the source rules cover)
+        holds = any(re.search(r"\basm\b", code(f)) for f in files)
         assert holds == (src in _build.HAZARD_CHECKED), src
 
 

@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(256) k_probe(const float* __restrict__ a, floa
     if (s == 123.456f) sink[0] = s;
 }
 
-// ---------------------------------------------------------------- shipped kernel (prologue.hip k_to_diagonal<true>)
+// ---------------------------------------------------------------- shipped kernel (to_diagonal.hip k_to_diagonal<true>)
 template <int TT, bool NT>
 __global__ void __launch_bounds__(256)
 k_tile(const float* __restrict__ src, const int* __restrict__ labels, float2* __restrict__ ws2, int T, int U, int V,

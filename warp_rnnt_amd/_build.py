@@ -13,10 +13,10 @@ from . import _isa_check
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwarp_rnnt_amd.so")
-SOURCES = ["api.hip", "lattice.hip", "lattice_ws.hip", "lattice_wd.hip", "grads.hip", "prologue.hip", "prologue_half.hip",
-           "expand.hip", "joint.hip"]
+SOURCES = ["api.hip", "lattice.hip", "lattice_ws.hip", "lattice_wd.hip", "grads.hip", "lsm_f32.hip", "lsm_bf16.hip",
+           "lsm_f16.hip", "lsm_backward.hip", "to_diagonal.hip", "compact.hip", "expand.hip", "joint.hip"]
 HEADERS = ["common.h", "kernels.h", "lattice_step.h", "lattice_wd_body.h", "lattice_single.h", "grads_cell.h",
-           "lsm_body_small.h", "lsm_body_large.h", "lsm_body_generic.h", "lsm_body_rows.h",
+           "streaming.h", "lsm.h", "lsm_body_small.h", "lsm_body_large.h", "lsm_body_generic.h", "lsm_body_rows.h",
            os.path.join("..", "..", "include", "warp_rnnt_amd.h")]
 ARCH = "gfx950"
 # Sources whose kernels refill live registers with inline-assembly LDS loads the compiler does not count (lattice_step.h):
@@ -26,9 +26,10 @@ ARCH = "gfx950"
 RELOAD_CHECKED = {"lattice_wd.hip": (8, 600)}
 # Sources with inline assembly of any kind: their ISA is walked for the wait-state hazards the compiler's recognizer does
 # not resolve around an `asm` statement (_isa_check: third rule -- DPP behind a VALU write, a transcendental's result in
-# the next slot, a VALU write behind a wide store).  Value: kernels the file is known to hold at least.
-HAZARD_CHECKED = {"lattice_wd.hip": 8, "lattice.hip": 4, "lattice_ws.hip": 2, "prologue.hip": 60,
-                  "prologue_half.hip": 160}
+# the next slot, a VALU write behind a wide store).  Value: kernels the file is known to hold at least (for the
+# log-softmax units and to_diagonal.hip that is what they hold today).
+HAZARD_CHECKED = {"lattice_wd.hip": 8, "lattice.hip": 4, "lattice_ws.hip": 2, "lsm_f32.hip": 132, "lsm_bf16.hip": 132,
+                  "lsm_f16.hip": 132, "to_diagonal.hip": 8}
 
 
 def _hipcc():

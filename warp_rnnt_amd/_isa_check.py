@@ -143,7 +143,7 @@ def require_clean(path, min_kernels=1, min_reloads=1):
 # compiler pads its own stores (GCNHazardRecognizer); it does not look inside an `asm` statement, so an inline
 # `global_store_dwordx4 ... sc1` followed by the compiler's next VALU instruction is a coin toss.  Found in round 6 by a
 # micro-benchmark's bit check (tools/ubench/lsm_store_policy.hip: 0.18 % of the float4 of one lane group wrong, every
-# cache policy, only the inline-assembly forms); the library's one inline store is a dwordx2 (prologue.hip: the dense
+# cache policy, only the inline-assembly forms); the library's one inline store is a dwordx2 (to_diagonal.hip: the dense
 # gather's write-through pairs), which has no such window.  This rule keeps it that way; the one form it lets through is the
 # store with an `s_nop 1` of its own behind it in the same assembly string.
 WIDE_ASM_STORE = re.compile(r"\b(global|buffer|flat|scratch)_store_(dwordx[34]|b96|b128)\b")

@@ -276,7 +276,7 @@ static rnntStatus_t loss_of_type(rnntStream_t stream, void* workspace, int input
             la.prepared = lattice_ring_prep(stream, la, N, LOAD_SKEWED, &prep) ? 1 : 0;
             e = launch_reskew(stream, input, w.ws2, N, T, U, &prep); break;
         case RNNT_IN_LOGITS_DENSE:
-            e = launch_log_softmax_gather_skewed_typed(stream, dtype, input_any, labels, w.ws2, N, T, U, V, blank); break;
+            e = launch_log_softmax_gather_skewed(stream, dtype, input_any, labels, w.ws2, N, T, U, V, blank); break;
         default:
             return RNNT_STATUS_INVALID_ARGUMENT;
     }
@@ -368,7 +368,7 @@ rnntStatus_t rnnt_amd_compact_offsets(rnntStream_t stream, const int* xn, const 
 
 namespace {
 // What step 1 of a compact loss call reads: fp32 log-probs (STU,V) -- the gather also writes each row's label index to
-// loc -- or logits of `dtype`, through the fused log-softmax + gather over the packed rows (prologue.hip: CompactMap).
+// loc -- or logits of `dtype`, through the fused log-softmax + gather over the packed rows (lsm.h: CompactMap).
 struct CompactInput {
     bool logits;
     int dtype;
@@ -389,7 +389,7 @@ rnntStatus_t compact_core(rnntStream_t stream, void* workspace, const CompactInp
     hipError_t e;
     if (in.logits) {
         const PackedRows cr{cell_offsets, label_offsets, xn, yn, ys, n_labels, STU, N};
-        e = launch_lsm_gather_compact_typed(stream, in.dtype, in.rows, w.ws2, cr, V, blank);
+        e = launch_lsm_gather_compact(stream, in.dtype, in.rows, w.ws2, cr, V, blank);
     } else {
         e = launch_gather_compact(stream, static_cast<const float*>(in.rows), ys, xn, yn, cell_offsets, label_offsets, w.ws2,
                                   in.loc, N, Tmax, Umax, V, blank, STU);
@@ -400,7 +400,7 @@ rnntStatus_t compact_core(rnntStream_t stream, void* workspace, const CompactInp
 }
 
 // The same with the launch bounds supplied by the caller: the offsets are computed here, on the device, and what the
-// host would have checked after reading the maxima back is checked there too (prologue.hip: k_compact_offsets) -- no
+// host would have checked after reading the maxima back is checked there too (compact.hip: k_compact_offsets) -- no
 // host synchronisation anywhere, so the call can be captured into a HIP graph.  A batch whose lengths do not fit the
 // bounds, or whose totals are not STU / n_labels, gets NaN costs and zero gradients.
 struct BoundedExtra {
@@ -504,7 +504,7 @@ rnntStatus_t rnnt_amd_compact_logits_backward(rnntStream_t stream, int dtype, co
     if (n_labels > 0 && !ys) return RNNT_STATUS_INVALID_ARGUMENT;
     if (STU == 0) return RNNT_STATUS_SUCCESS;
     const PackedRows cr{cell_offsets, label_offsets, xn, yn, ys, n_labels, STU, N};
-    if (launch_logits_backward_compact_typed(stream, dtype, logits, grads2, grad_costs, dlogits, cr, V, blank) != hipSuccess)
+    if (launch_logits_backward_compact(stream, dtype, logits, grads2, grad_costs, dlogits, cr, V, blank) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
@@ -657,7 +657,7 @@ rnntStatus_t rnnt_amd_logits_backward_typed(rnntStream_t stream, int dtype, cons
                                             int N, int T, int U, int V, int blank) {
     if (!dtype_ok(dtype) || !dims_ok(N, T, U) || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (U > 1 && !labels) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (launch_logits_backward_typed(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
+    if (launch_logits_backward(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
         hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
@@ -747,7 +747,7 @@ rnntStatus_t rnnt_amd_joint_backward(rnntStream_t stream, void* workspace, int d
 
 rnntStatus_t rnnt_amd_log_softmax_typed(rnntStream_t stream, int dtype, const void* x, float* out, int64_t rows, int V) {
     if (!dtype_ok(dtype) || rows < 0 || V < 1) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (launch_log_softmax_typed(stream, dtype, x, out, rows, V) != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
+    if (launch_log_softmax(stream, dtype, x, out, rows, V) != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
 

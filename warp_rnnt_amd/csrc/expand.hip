@@ -261,7 +261,7 @@ hipError_t launch_expand_split(hipStream_t stream, const float* ga_skewed, const
     return launch_rows(stream, rows, dense, (unsigned)cells64, V, blank);
 }
 
-// (STU,V) gradient rows of the compact layout; replaces the first version in prologue.hip
+// (STU,V) gradient rows of the compact layout; replaces the first version next to the compact gather
 hipError_t launch_scatter_compact(hipStream_t stream, const float* grad_cost, const float* grads2,
                                   const int64_t* loc, const int* cum_lens, float* out, int64_t STU, int N,
                                   int V, int blank) {

@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_fwd(JointArgs a) {
     }
 }
 
-// dz of the 16x16 block `z` (rows v0 + 4q + i, column = this lane's cell): the LSM_BWD formula of prologue.hip.
+// dz of the 16x16 block `z` (rows v0 + 4q + i, column = this lane's cell): the LSM_BWD formula of lsm.h.
 __device__ __forceinline__ jf4 dz_block(const JointArgs& a, jf4 z, int v0, int q, bool live, float lse, float gB,
                                         float gL, int lab) {
     jf4 d;

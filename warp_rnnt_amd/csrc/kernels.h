@@ -113,8 +113,8 @@ int lattice_kernel_override();
 int set_lattice_kernel_override(int k);  // returns the previous setting, or -1 for an unknown value (nothing changes)
 hipError_t launch_grads(hipStream_t stream, const GradArgs& a, int N, int loader, int writer);
 
-// prologue / epilogue streaming kernels
-hipError_t launch_log_softmax(hipStream_t stream, const float* x, float* out, int64_t rows, int V);
+// streaming kernels in front of and behind the lattice: log-softmax backward (lsm_backward.hip), dense layout turns
+// (to_diagonal.hip), expand (expand.hip)
 hipError_t launch_log_softmax_backward(hipStream_t stream, const float* dy, const float* y, float* dx,
                                        int64_t rows, int V);
 hipError_t launch_gather(hipStream_t stream, const float* log_probs, const int* labels, float* out2,
@@ -126,7 +126,7 @@ hipError_t launch_unskew(hipStream_t stream, const float* a, const float* b, flo
 hipError_t launch_split_pairs(hipStream_t stream, const float* pairs, float* a, float* b, size_t cells);
 hipError_t launch_expand_split(hipStream_t stream, const float* ga_skewed, const float* gb_skewed, const int* labels,
                                const int* xn, const int* yn, float* dense, int N, int T, int U, int V, int blank);
-// compact (ragged packed) layout, core_compact.cu:403-436,456-484
+// compact (ragged packed) layout (compact.hip), core_compact.cu:403-436,456-484
 // reference-layout compact helpers (core.h:41-60 shims): row-major packed pairs + loc; costs from betas alone
 hipError_t launch_gather_compact_rowmajor(hipStream_t stream, const float* xs, const int* ys, const unsigned* xn,
                                           const unsigned* yn, float* gather_xs, int64_t* loc, const unsigned* mem_pref,
@@ -173,20 +173,16 @@ hipError_t launch_joint_bwd(hipStream_t stream, int dtype, int act, const void* 
                             const float* grads, const float* grad_costs, void* wt, float* dw_part, float* db_part,
                             int splits, void* df, void* dg, float* dweight, float* dbias, int N, int T, int U, int H,
                             int V, int blank);
-hipError_t launch_log_softmax_gather_skewed(hipStream_t stream, const float* logits, const int* labels,
+// The forward log-softmax family (lsm.h; lsm_f32.hip holds these five launchers) for logits of any RNNT_DTYPE_*
+// (hipErrorInvalidValue for another dtype): fp32 arithmetic from the load on, pairs and log-probs in fp32, d/d logits in
+// the logits' type.  Plain log-softmax, fused gather into the diagonal-major pair plane, fused d/d logits:
+hipError_t launch_log_softmax(hipStream_t stream, int dtype, const void* x, float* out, int64_t rows, int V);
+hipError_t launch_log_softmax_gather_skewed(hipStream_t stream, int dtype, const void* logits, const int* labels,
                                             float* ws2, int N, int T, int U, int V, int blank);
-hipError_t launch_logits_backward(hipStream_t stream, const float* logits, const int* labels,
-                                  const float* g2_diagonal, const float* scale, float* dlogits, int N, int T,
-                                  int U, int V, int blank);
-// the same three for logits of any RNNT_DTYPE_* (prologue_half.hip; fp32 forwards to the launchers above): fp32 arithmetic
-// from the load on, pairs and log-probs in fp32, d/d logits in the logits' type (hipErrorInvalidValue for another dtype)
-hipError_t launch_log_softmax_typed(hipStream_t stream, int dtype, const void* x, float* out, int64_t rows, int V);
-hipError_t launch_log_softmax_gather_skewed_typed(hipStream_t stream, int dtype, const void* logits, const int* labels,
-                                                  float* ws2, int N, int T, int U, int V, int blank);
-hipError_t launch_logits_backward_typed(hipStream_t stream, int dtype, const void* logits, const int* labels,
-                                        const float* g2_diagonal, const float* scale, void* dlogits, int N, int T,
-                                        int U, int V, int blank);
-// The fused log-softmax modes over compact (ragged packed) logits (STU,V): row c belongs to utterance n = the first n with
+hipError_t launch_logits_backward(hipStream_t stream, int dtype, const void* logits, const int* labels,
+                                  const float* g2_diagonal, const float* scale, void* dlogits, int N, int T, int U, int V,
+                                  int blank);
+// The fused modes over compact (ragged packed) logits (STU,V): row c belongs to utterance n = the first n with
 // offs[n+1] > c, as the (t,u) cell of its row-major (T_n, U_n = yn[n]+1) block.  A row that belongs to nobody -- outside
 // its owner's range, an owner whose range is not T_n*U_n rows or ends past STU, T_n < 1, a label index at or past nlab --
 // gets no pair in the gather and a zero row in the backward.
@@ -200,17 +196,12 @@ struct PackedRows {
     int64_t rows;          // STU
     int N;
 };
-// fp32 (prologue.hip), and for any RNNT_DTYPE_* the _typed forms (prologue_half.hip; fp32 forwards):
 //   gather: the (blank,label) log-prob pair of every row into its utterance's skewed plane of the compact workspace;
 //   backward: d/d logits from the row-major (STU,2) pairs, scaled by scale[n] (nullptr: 1), in the logits' type
-hipError_t launch_lsm_gather_compact(hipStream_t stream, const float* logits, float* ws2, const PackedRows& cr, int V,
-                                     int blank);
-hipError_t launch_logits_backward_compact(hipStream_t stream, const float* logits, const float* g2_rowmajor,
-                                          const float* scale, float* dlogits, const PackedRows& cr, int V, int blank);
-hipError_t launch_lsm_gather_compact_typed(hipStream_t stream, int dtype, const void* logits, float* ws2,
-                                           const PackedRows& cr, int V, int blank);
-hipError_t launch_logits_backward_compact_typed(hipStream_t stream, int dtype, const void* logits, const float* g2_rowmajor,
-                                                const float* scale, void* dlogits, const PackedRows& cr, int V, int blank);
+hipError_t launch_lsm_gather_compact(hipStream_t stream, int dtype, const void* logits, float* ws2, const PackedRows& cr,
+                                     int V, int blank);
+hipError_t launch_logits_backward_compact(hipStream_t stream, int dtype, const void* logits, const float* g2_rowmajor,
+                                          const float* scale, void* dlogits, const PackedRows& cr, int V, int blank);
 hipError_t launch_expand(hipStream_t stream, const float* g2_skewed, const int* labels,
                          const int* xn, const int* yn, const float* scale, float* dense, int N,
                          int T, int U, int V, int blank, int overwrite_mode);

@@ -1,0 +1,908 @@
+// The forward log-softmax kernels over the vocabulary axis -- plain, fused with the gather of the (blank, label)
+// log-prob pair per lattice cell, and fused into d/d logits -- as templates over the storage type E of the logits;
+// lsm_f32.hip, lsm_bf16.hip and lsm_f16.hip instantiate them.  These are the HBM-bound part of the op (the dense
+// (N,T,U,V) tensor is 25x..5000x larger than everything the lattice kernels touch).
+//
+// Reference counterparts:
+//   log-softmax  : caller side, pytorch_binding/benchmark.py:65,70 (F.log_softmax)
+//   gather       : warp_rnnt/__init__.py:118-128 (torch.full int64 index + slice-assign +
+//                  torch.gather; 16 B of index per cell) and core_compact.cu:403-436
+//   The fused form reads the logits once and never materialises log-probs; it writes the diagonal-major workspace (common.h).
+#pragma once
+#include <cstdlib>
+#include <type_traits>
+
+#include "streaming.h"
+
+namespace rnnt {
+
+// The row -> cell map of the fused log-softmax kernels is a policy, passed by value and chosen by a template parameter.
+// chunk(first, last) is called by every wave of a kernel, wave-uniformly, before at() is asked for rows in [first, last];
+// pair() and scale() read the backward's gradient pair and upstream scale of a mapped row, put() stores the gather's pair.
+//   DenseMap: the (N,T,U,V) tensor, map_cell -- what the dense kernels have always done.
+struct DenseMap {
+    static constexpr bool COMPACT = false;
+    const int* labels;
+    int T, U;
+    __device__ __forceinline__ void chunk(int64_t, int64_t) {}
+    __device__ __forceinline__ CellMap at(size_t cell, int V, int blank) const {
+        return map_cell(cell, labels, T, U, V, blank);
+    }
+    template <class B> __device__ __forceinline__ float2 pair(const B& bw, const CellMap m) const { return bw.g2[m.sk]; }
+    template <class B> __device__ __forceinline__ float scale(const B& bw, const CellMap m) const {
+        return bw.scale ? bw.scale[m.n] : 1.0f;
+    }
+    __device__ __forceinline__ void put(float* out, const CellMap m, float2 p) const {
+        reinterpret_cast<float2*>(out)[m.sk] = p;
+    }
+};
+
+// The owner of packed row c -- the first n with offs[n+1] > c, N when there is none -- searched by a whole wave: its lanes
+// probe 64 evenly spaced utterances at once and the first that already ends past c narrows the range 64-fold, so N <= 64
+// costs one round of loads and N <= 4096 two (a binary search costs log2 N dependent loads, ~0.5 us each from L2).
+// Lanes 0-31 search for `first`, lanes 32-63 for `last`, 32 probes per round each.  For offsets that are not
+// non-decreasing the search still ends on one utterance of [0, N]; CompactMap::at checks the row against its range.
+__device__ __forceinline__ void compact_owner_range(const int64_t* __restrict__ offs, int N, int64_t first, int64_t last,
+                                                    int& n0, int& n1) {
+    const int lane = threadIdx.x & (WAVE - 1), half = lane >> 5, j = lane & 31;
+    const int64_t c = half ? last : first;
+    int lo = 0, hi = N;                                // answer in [lo, hi]; hi = N stands for "no utterance"
+    for (;;) {
+        const bool more = lo < hi;
+        const uint64_t act = __ballot(more);
+        if (act == 0) break;
+        const int step = (hi - lo + 31) >> 5;
+        const int m = lo + j * step;
+        const bool p = more && (m >= hi || offs[m + 1] > c);
+        const uint64_t b = __ballot(p);
+        const unsigned mine = (unsigned)(b >> (32 * half));   // this half's probes
+        if (more) {
+            if (mine) {
+                const int f = __builtin_ctz(mine);
+                hi = min(hi, lo + f * step);
+                lo = f ? lo + (f - 1) * step + 1 : lo;
+            } else {
+                lo = lo + 31 * step + 1;
+            }
+            lo = min(lo, hi);
+        }
+    }
+    n0 = __shfl(lo, 0, WAVE);
+    n1 = __shfl(lo, 32, WAVE);
+}
+
+//   CompactMap: ragged packed rows (kernels.h: PackedRows).  The pair slot in the forward is the skewed one of the compact
+//   workspace, offs[n] + ((t+u) mod T_n)*U_n + u; in the backward the row-major (STU,2) pairs are read at the row itself.
+//   at() finds the owner inside the chunk's [n0, n1] only; m.n = -1 marks a row that belongs to nobody.
+template <bool SKEW>
+struct CompactMap {
+    static constexpr bool COMPACT = true;
+    PackedRows r;
+    int n0, n1;
+    __device__ __forceinline__ void chunk(int64_t first, int64_t last) {
+        compact_owner_range(r.offs, r.N, first, last, n0, n1);
+        n1 = min(n1, r.N - 1);
+    }
+    __device__ __forceinline__ CellMap at(size_t cell, int V, int blank) const {
+        CellMap m = {0, blank, -1};
+        const int64_t c = (int64_t)cell;
+        int n = n0, hi = n1;
+        while (n < hi) {
+            const int mid = (n + hi) >> 1;
+            if (r.offs[mid + 1] > c) hi = mid; else n = mid + 1;
+        }
+        if (n >= r.N || c >= r.rows) return m;
+        const int64_t o = r.offs[n], e = r.offs[n + 1];
+        const int T = r.xn[n], U = r.yn[n] + 1;
+        // the owner's range must be exactly its T_n*U_n rows inside the tensor, or none of them is mapped
+        if (c < o || c >= e || o < 0 || e > r.rows || T < 1 || U < 1 || e - o != (int64_t)T * U) return m;
+        const unsigned local = (unsigned)(c - o);      // (< T_n*U_n < 2^32)
+        const unsigned t = local / (unsigned)U;
+        const int u = (int)(local - t * (unsigned)U);
+        int lab = blank;
+        if (u < U - 1) {
+            const int64_t li = (int64_t)r.loffs[n] + u;
+            const int64_t lim = r.nlab >= 0 ? r.nlab : (int64_t)r.loffs[r.N];
+            if (li < 0 || li >= lim) return m;
+            lab = safe_label(r.ys[li], V, blank);
+        }
+        if (SKEW) {
+            int d = (int)t + u;
+            d = d >= T ? d % T : d;
+            m.sk = (size_t)o + (size_t)d * U + u;
+        } else {
+            m.sk = cell;
+        }
+        m.label = lab;
+        m.n = n;
+        return m;
+    }
+    template <class B> __device__ __forceinline__ float2 pair(const B& bw, const CellMap& m) const {
+        return m.n >= 0 ? bw.g2[m.sk] : make_float2(0.0f, 0.0f);
+    }
+    template <class B> __device__ __forceinline__ float scale(const B& bw, const CellMap& m) const {
+        return (bw.scale && m.n >= 0) ? bw.scale[m.n] : 1.0f;
+    }
+    __device__ __forceinline__ void put(float* out, const CellMap& m, float2 p) const {
+        if (m.n >= 0) reinterpret_cast<float2*>(out)[m.sk] = p;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// Small vocabularies (V <= 1024): a workgroup stages R whole rows in LDS with
+// 16-byte coalesced loads (ds_write_b128, rows kept at their natural stride V so
+// the tile is a byte copy of the global chunk), L lanes cooperate on a row, and
+// results leave with ds_read_b128 + 16-byte coalesced stores (or as one float2
+// per row for the fused gather).  The first version of this kernel was
+// VALU-bound, not HBM-bound (rocprofv3: 871 VALU instructions per wave, i.e.
+// ~70 per element: libm expf, per-element index division for padded LDS rows,
+// per-lane loop control); this one spends ~12.
+//   exp(x - max) is evaluated as exp2(x*log2e - max*log2e) on the hardware
+//   v_exp_f32 unit, log(sum) as v_log_f32 * ln2 (sum in [1,V]); both are within
+//   ~2 ulp, the result is within 4e-6 of torch.log_softmax (tests).
+// ---------------------------------------------------------------------------
+// Cache policy of the LDS-staged kernel's 16-byte global loads and stores: non-temporal in the fused modes (gather:
+// a read-only stream of the logits; backward: logits in, d/d logits out -- fused forward 0.472 -> 0.464 ms, fused
+// training step 1.00 -> 0.975 ms at c4, profiles/r03_bwd_nt_ab.txt), plain for the log-softmax itself, where the
+// hints measured nothing to worse in rounds 1-2 (HISTORY.md).
+// Written-through stores (sc1 / sc1 nt; round 6, after the dense gather gained from them): nothing at c4 in any mode of this
+// kernel, c3's row-per-workgroup kernel 0.658 -> 0.73-0.76 ms, the register kernel 480 -> 520-580 us -- they pay only where
+// every store instruction covers whole 128-byte lines (profiles/r06_lsm_store_policy.txt).
+#define RNNT_LSM_NT_MODE(MODE) ((MODE) != LSM_NORM)
+#define RNNT_LSM_LOAD(p) rnnt_load4<RNNT_LSM_NT_MODE(MODE)>(p)
+#define RNNT_LSM_STORE(p, v) rnnt_store4<RNNT_LSM_NT_MODE(MODE)>(p, v)
+
+// What the log-softmax kernels emit.
+enum LsmMode : int {
+    LSM_NORM = 0,    // log-softmax rows
+    LSM_GATHER = 1,  // diagonal-major (blank,label) log-prob pairs; log-probs never materialise
+    LSM_BWD = 2      // d(loss)/d(logits) rows from the gathered gradients:
+                     //   dz[v] = s*( [v==blank]gB + [v==label]gL - softmax(z)[v]*(gB+gL) )
+};
+// Storage type E of the logits: float, or __bf16 / _Float16 (RNNT_DTYPE_BF16 / _F16; one unit each).  Half-precision
+// logits are converted to fp32 as they are loaded -- everything behind the load is the fp32 code -- and d/d logits (LSM_BWD)
+// are converted back ONCE, round to nearest even (the compiler's cast: v_cvt_pk_bf16_f32 / v_cvt_f16_f32), as they are
+// stored.  The kernels move rows in vectors of four elements (16 bytes of fp32, 8 of half) and every alignment predicate of
+// dispatch_lsm is stated in those vectors, so a V reaches the same kernel, the same lanes per row and the same reduction
+// tree at every E: the bits of a half-precision row are those of its fp32 upcast.
+template <typename E> struct LsmVec { typedef E type __attribute__((ext_vector_type(4))); };
+template <typename E> using lsm_vec_t = typename LsmVec<E>::type;
+template <int MODE, typename E> using LsmOut = std::conditional_t<MODE == LSM_BWD, E, float>;   // what `out` holds
+template <bool NT, typename E, typename I> __device__ __forceinline__ float4 lsm_ld4(const E* base, I i) {
+    if constexpr (std::is_same_v<E, float>) {
+        return rnnt_load4<NT>(reinterpret_cast<const float4*>(base) + i);
+    } else {
+        const lsm_vec_t<E>* p = reinterpret_cast<const lsm_vec_t<E>*>(base) + i;
+        lsm_vec_t<E> h;
+        if constexpr (NT) h = __builtin_nontemporal_load(p); else h = *p;
+        const rnnt_f4 v = __builtin_convertvector(h, rnnt_f4);
+        return make_float4(v.x, v.y, v.z, v.w);
+    }
+}
+template <bool NT, typename E, typename I> __device__ __forceinline__ void lsm_st4(E* base, I i, float4 v) {
+    if constexpr (std::is_same_v<E, float>) {
+        rnnt_store4<NT>(reinterpret_cast<float4*>(base) + i, v);
+    } else {
+        const rnnt_f4 w = {v.x, v.y, v.z, v.w};
+        const lsm_vec_t<E> h = __builtin_convertvector(w, lsm_vec_t<E>);
+        lsm_vec_t<E>* p = reinterpret_cast<lsm_vec_t<E>*>(base) + i;
+        if constexpr (NT) __builtin_nontemporal_store(h, p); else *p = h;
+    }
+}
+template <typename E> __device__ __forceinline__ float lsm_ld1(const E* p) { return (float)*p; }
+template <typename E> __device__ __forceinline__ void lsm_st1(E* p, float v) { *p = (E)v; }
+
+struct LsmBwd {
+    const float2* g2;    // diagonal-major gathered gradients (RNNT_GRADS_GATHERED_DIAGONAL)
+    const float* scale;  // (N,) upstream gradient per utterance, or nullptr
+    int xcd;             // row-per-workgroup kernel: 1 = every XCD streams a contiguous eighth of the rows
+};
+
+constexpr int SM_THREADS = 256;
+constexpr int SM_FLOATS = 3200;   // LDS tile budget in floats: one pass of the 256 threads over a 12.5 KiB tile.  (512 threads x 25 KiB: 2 % faster in the isolated probe, slower in bench.py and in the fused gather mode; two passes per tile or 50 KiB tiles are clearly worse.)
+// In the fused gather the shared tile of half-precision logits holds twice the rows: 12.8 KB of HBM per tile, as for fp32
+// (c4, bf16: 178 -> 172 us; the fused backward, which also writes the tile back, 287 -> 290 us with it and keeps the
+// fp32 row count).  Rows per tile do not touch the bits: the lanes of a row and its reduction tree stay the same.
+template <typename E, int MODE> constexpr int sm_floats() {
+    return MODE == LSM_GATHER ? SM_FLOATS * (int)(sizeof(float) / sizeof(E)) : SM_FLOATS;
+}
+
+// WP ("wave private", L <= 16 and one pass per tile): every wave stages, normalises and stores its own
+// WAVE/L consecutive rows (a multiple of 4, so its chunk is 16-byte aligned) and the workgroup never
+// synchronises -- 32 independent streams per CU instead of 8 workgroups that each wait for their slowest wave.
+__device__ __forceinline__ void wave_sync_lds() {
+    // LDS operations of one wave retire in order; this only stops the compiler from moving them
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <typename E, int L, int MODE, bool WP>
+__global__ void __launch_bounds__(SM_THREADS)
+k_lsm_small(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
+            int64_t rows, int V, int R, int q, int T, int U, int blank, LsmBwd bw) {
+    DenseMap map{labels, T, U};
+#include "lsm_body_small.h"
+}
+template <typename E, int L, int MODE, bool WP>
+__global__ void __launch_bounds__(SM_THREADS)
+k_lsm_small_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int R, int q, int blank,
+                    LsmBwd bw) {
+    CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
+#include "lsm_body_small.h"
+}
+
+// ---------------------------------------------------------------------------
+// Large vocabularies (1024 < V <= 16384, V % 4 == 0): one workgroup per row,
+// the row lives in registers (up to 16 float4 per lane), one HBM read and one
+// HBM write per element.
+// ---------------------------------------------------------------------------
+// Shape of the row-per-workgroup kernel: THREADS x NV float4 must cover a row.  The registers that hold
+// the row set the residency (NV=16 x 256 threads: 84 VGPRs, 5 waves/SIMD; NV=8: 8 waves/SIMD).  The launcher
+// picks 1.25-2.5 float4 per thread for the plain log-softmax and the smallest cover for the read-mostly fused modes
+// (dispatch_lsm).
+// cache policy of the plain (LSM_NORM) row-per-workgroup stream: non-temporal loads and non-temporal stores.
+// Both (round 3; round 1 had tried them on the LDS-staged small-V kernel only, where they do nothing): c5 (V=10000, in
+// place, 288 GB of traffic) 57.4 -> 51.3 ms per step, c3 (V=5000) 0.708 -> 0.695 ms; loads alone are WORSE (c3 0.733),
+// stores alone neutral (profiles/r03_lg_nt_ab.txt).  The same policy in the fused gather / backward modes: c3 fused forward
+// 0.336 -> 0.325 ms, fused training step 1.051 -> 1.018 ms (profiles/r03_lg_fused_nt_ab.txt)
+template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
+__global__ void __launch_bounds__(LG_THREADS)
+k_lsm_large(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
+            int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
+    DenseMap map{labels, T, U};
+#include "lsm_body_large.h"
+}
+template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
+__global__ void __launch_bounds__(LG_THREADS)
+k_lsm_large_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
+    CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
+#include "lsm_body_large.h"
+}
+
+// ---------------------------------------------------------------------------
+// Generic fallback (any V, any alignment): one wave per row, three passes.
+// ---------------------------------------------------------------------------
+template <typename E, int MODE>
+__global__ void __launch_bounds__(256)
+k_lsm_generic(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
+              int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
+    DenseMap map{labels, T, U};
+#include "lsm_body_generic.h"
+}
+template <typename E, int MODE>
+__global__ void __launch_bounds__(256)
+k_lsm_generic_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
+    CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
+#include "lsm_body_generic.h"
+}
+
+// ---------------------------------------------------------------------------
+// Small vocabularies, plain log-softmax, rows in REGISTERS (round 3).  KR whole rows (KR <= 4, KR*V a multiple of 4,
+// KR*V/4 <= 32 float4) form a 16-byte aligned group; a wave holds one group in lanes 0.. of each 32-lane half, one
+// float4 per lane (V = 50: two rows = 25 lanes of 32 busy, the 800 bytes of a wave's two groups contiguous), and
+// reduces the row maxima and sums with DPP butterflies inside the half (quad_perm xor 1 / xor 2, row_ror 4 / 8) plus
+// one ds_swizzle across its two DPP rows -- no LDS memory, no barrier, one float4 load and one store per lane and
+// group, non-temporal both ways.  This is the shape of the fastest plain copy on the part, and it runs at that
+// copy's rate: 462 us for the c4 tensor (6.24 TB/s read + write) where the LDS-staged kernel below takes 498
+// (tools/ubench/lsm_regs.hip, profiles/r03_ubench_lsm_regs.txt; without the non-temporal hint 484).
+// ---------------------------------------------------------------------------
+template <int CTRL> __device__ __forceinline__ float lsm_dpp(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float lsm_swz16(float v) {   // lane ^ 16 inside each 32-lane half
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));
+}
+__device__ __forceinline__ float half_sum32(float v) {
+    v += lsm_dpp<0xB1>(v); v += lsm_dpp<0x4E>(v); v += lsm_dpp<0x124>(v); v += lsm_dpp<0x128>(v);
+    return v + lsm_swz16(v);
+}
+// The KR row maxima of a group in ONE hand-written statement (round 6).  fmaxf() on a DPP result compiles to three
+// instructions per butterfly step -- v_mov_b32_dpp, a v_max x,x that quiets a possible signalling NaN, the v_max -- where
+// one v_max_f32_dpp does the work; with two rows per group that is 48 of the kernel's 311 vector instructions per wave, and
+// the kernel sits AT the vector-issue bound (311 x 900 k waves / (1024 SIMDs x 0.6 G instructions/s) = 456 us of its 462).
+// The KR chains are interleaved, so a step's result is two wait states old when the next step reads it through DPP
+// (KR = 1, 2: topped up with s_nop); the leading s_nop 1 covers the compiler's instruction that produced the inputs
+// (_isa_check.py walks the generated ISA for exactly these).  v_max_f32 returns the other operand for a quiet NaN as
+// fmaxf does; a signalling NaN makes the row's maximum NaN and with it the row, which it would be anyway.
+// The results leave through a per-wave LDS strip in ADDRESS order (round 6).  A group's segment (V = 50: 400 bytes) starts
+// and ends inside 64-byte granules, and what that costs is the STORES: a copy whose stores sit 16 or 32 bytes off the
+// 64-byte grid loses 5-19 %, one whose loads do loses nothing (tools/ubench/copy_shape.hip).  Two ds_write_b128 + two
+// ds_read_b128 per lane turn the wave's four segments into one store instruction of 1024 contiguous bytes and one of the
+// rest, all whole granules: the V=50 micro-benchmark 465 -> 457-460 us, same bits (tools/ubench/lsm_store_policy.hip).
+// In the step (bench.py, c4, interleaved processes, profiles/r06_lsm_regs_ab.txt): 0.7997 -> 0.7924 ms on one box, 0.8418 ->
+// 0.8323 on another; and with the stores then also written through AND streaming (sc1 nt: whole granules that nothing
+// else will add to -- the case in which write-through pays) 0.8323 -> 0.8267.  Blocks of four groups per
+// half lose 20 us.
+#define RNNT_DPPMAX(R, CTRL) "v_max_f32_dpp " R ", " R ", " R " " CTRL " row_mask:0xf bank_mask:0xf\n\t"
+#define RNNT_DPPMAX_STEPS(BODY, GAP)                                                                     \
+    "s_nop 1\n\t" BODY("quad_perm:[1,0,3,2]") GAP BODY("quad_perm:[2,3,0,1]") GAP BODY("row_ror:4") GAP BODY("row_ror:8")
+template <int KR> __device__ __forceinline__ void half_max32_rows(float (&M)[KR]) {
+    static_assert(KR >= 1 && KR <= 4, "one to four rows per group");
+    float t0, t1, t2, t3;
+    if constexpr (KR == 1) {
+#define RNNT_B1(C) RNNT_DPPMAX("%0", C)
+        asm volatile(RNNT_DPPMAX_STEPS(RNNT_B1, "s_nop 1\n\t")
+                     "ds_swizzle_b32 %1, %0 offset:swizzle(SWAP,16)\n\ts_waitcnt lgkmcnt(0)\n\tv_max_f32 %0, %0, %1"
+                     : "+v"(M[0]), "=&v"(t0));
+#undef RNNT_B1
+    } else if constexpr (KR == 2) {
+#define RNNT_B2(C) RNNT_DPPMAX("%0", C) RNNT_DPPMAX("%1", C)
+        asm volatile(RNNT_DPPMAX_STEPS(RNNT_B2, "s_nop 0\n\t")
+                     "ds_swizzle_b32 %2, %0 offset:swizzle(SWAP,16)\n\tds_swizzle_b32 %3, %1 offset:swizzle(SWAP,16)\n\t"
+                     "s_waitcnt lgkmcnt(0)\n\tv_max_f32 %0, %0, %2\n\tv_max_f32 %1, %1, %3"
+                     : "+v"(M[0]), "+v"(M[1]), "=&v"(t0), "=&v"(t1));
+#undef RNNT_B2
+    } else if constexpr (KR == 3) {
+#define RNNT_B3(C) RNNT_DPPMAX("%0", C) RNNT_DPPMAX("%1", C) RNNT_DPPMAX("%2", C)
+        asm volatile(RNNT_DPPMAX_STEPS(RNNT_B3, "")
+                     "ds_swizzle_b32 %3, %0 offset:swizzle(SWAP,16)\n\tds_swizzle_b32 %4, %1 offset:swizzle(SWAP,16)\n\t"
+                     "ds_swizzle_b32 %5, %2 offset:swizzle(SWAP,16)\n\t"
+                     "s_waitcnt lgkmcnt(0)\n\tv_max_f32 %0, %0, %3\n\tv_max_f32 %1, %1, %4\n\tv_max_f32 %2, %2, %5"
+                     : "+v"(M[0]), "+v"(M[1]), "+v"(M[2]), "=&v"(t0), "=&v"(t1), "=&v"(t2));
+#undef RNNT_B3
+    } else {
+#define RNNT_B4(C) RNNT_DPPMAX("%0", C) RNNT_DPPMAX("%1", C) RNNT_DPPMAX("%2", C) RNNT_DPPMAX("%3", C)
+        asm volatile(RNNT_DPPMAX_STEPS(RNNT_B4, "")
+                     "ds_swizzle_b32 %4, %0 offset:swizzle(SWAP,16)\n\tds_swizzle_b32 %5, %1 offset:swizzle(SWAP,16)\n\t"
+                     "ds_swizzle_b32 %6, %2 offset:swizzle(SWAP,16)\n\tds_swizzle_b32 %7, %3 offset:swizzle(SWAP,16)\n\t"
+                     "s_waitcnt lgkmcnt(0)\n\tv_max_f32 %0, %0, %4\n\tv_max_f32 %1, %1, %5\n\tv_max_f32 %2, %2, %6\n\t"
+                     "v_max_f32 %3, %3, %7"
+                     : "+v"(M[0]), "+v"(M[1]), "+v"(M[2]), "+v"(M[3]), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3));
+#undef RNNT_B4
+    }
+}
+#undef RNNT_DPPMAX_STEPS
+#undef RNNT_DPPMAX
+constexpr int RG_UN = 2;   // groups per half and wave, loads first (1: 500 us, 2: 462-484, 4: 482-498)
+
+// NT: bit 0 = non-temporal loads, bit 1 = non-temporal stores (both: 462 us for the c4 tensor, neither: 484); the launch
+// passes 3, and the stores leave through the strip written through and streaming
+template <typename E, int KR, int NT>
+__global__ void __launch_bounds__(256) k_lsm_regs(const E* __restrict__ x, float* __restrict__ out,
+                                                  const int64_t ngroups, const int V, const int xcd) {
+    const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
+    const int g4 = (KR * V) >> 2;                  // float4 per group
+    const bool act = j < g4;
+    __shared__ rnnt_f4 strip[4][64 * RG_UN];        // per wave: its 2 * RG_UN groups of <= 32 float4 in address order
+    const int wv = threadIdx.x >> 6;
+    // xcd: the eight XCDs (blockIdx mod 8; the grid is a multiple of 8) each stream a contiguous eighth of the groups
+    const unsigned wg = xcd ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int64_t w = (int64_t)wg * 4 + (threadIdx.x >> 6);
+    const rnnt_f4* __restrict__ xin = reinterpret_cast<const rnnt_f4*>(x);
+    rnnt_f4* __restrict__ xout = reinterpret_cast<rnnt_f4*>(out);
+    // the lane's four elements: the first `ns` of them belong to row r0 of the group, the rest to row r0 + 1
+    const int e0 = 4 * j;
+    const int r0 = e0 / V;
+    const int ns = min(4, (r0 + 1) * V - e0);
+    rnnt_f4 v[RG_UN];
+#pragma unroll
+    for (int i = 0; i < RG_UN; ++i) {
+        const int64_t g = (w * RG_UN + i) * 2 + half;
+        const float ninf = -__builtin_inff();
+        v[i] = rnnt_f4{ninf, ninf, ninf, ninf};
+        if constexpr (std::is_same_v<E, float>) {
+            if (act && g < ngroups) v[i] = (NT & 1) ? __builtin_nontemporal_load(xin + g * g4 + j) : xin[g * g4 + j];
+        } else {
+            if (act && g < ngroups) { const float4 t = lsm_ld4<(NT & 1) != 0>(x, g * g4 + j); v[i] = rnnt_f4{t.x, t.y, t.z, t.w}; }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < RG_UN; ++i) {
+        const rnnt_f4 t = v[i];
+        const float ninf = -__builtin_inff();
+        // maxima of the lane's two parts, then of every row of the group over the half
+        const float a0 = t.x, a1 = ns > 1 ? t.y : ninf, a2 = ns > 2 ? t.z : ninf, a3 = ns > 3 ? t.w : ninf;
+        const float b1 = ns > 1 ? ninf : t.y, b2 = ns > 2 ? ninf : t.z, b3 = ns > 3 ? ninf : t.w;
+        const float mf = fmaxf(fmaxf(a0, a1), fmaxf(a2, a3)), ms = fmaxf(b1, fmaxf(b2, b3));
+        float M[KR];
+#pragma unroll
+        for (int r = 0; r < KR; ++r) M[r] = act ? (r0 == r ? mf : (r0 + 1 == r ? ms : ninf)) : ninf;
+        half_max32_rows<KR>(M);
+        float m_first = M[0], m_second = M[KR - 1];
+#pragma unroll
+        for (int r = 1; r < KR; ++r) m_first = r0 == r ? M[r] : m_first;
+#pragma unroll
+        for (int r = KR - 2; r >= 0; --r) m_second = r0 + 1 == r ? M[r] : m_second;
+        const float kf = m_first * LOG2E, ks = m_second * LOG2E;
+        const float e0x = __builtin_amdgcn_exp2f(__builtin_fmaf(t.x, LOG2E, -kf));
+        const float e1x = __builtin_amdgcn_exp2f(__builtin_fmaf(t.y, LOG2E, ns > 1 ? -kf : -ks));
+        const float e2x = __builtin_amdgcn_exp2f(__builtin_fmaf(t.z, LOG2E, ns > 2 ? -kf : -ks));
+        const float e3x = __builtin_amdgcn_exp2f(__builtin_fmaf(t.w, LOG2E, ns > 3 ? -kf : -ks));
+        const float sf = e0x + (ns > 1 ? e1x : 0.f) + (ns > 2 ? e2x : 0.f) + (ns > 3 ? e3x : 0.f);
+        const float ss = (ns > 1 ? 0.f : e1x) + (ns > 2 ? 0.f : e2x) + (ns > 3 ? 0.f : e3x);
+        // log-sum of every row; the result is (x - max) - log-sum, the association of the LDS-staged kernel (and of
+        // torch): subtracting a rounded max + log-sum instead loses an ulp of |max| per element, which the lattice
+        // amplifies to 1e-4 on the gradients at c2's size
+        float Lg[KR];
+#pragma unroll
+        for (int r = 0; r < KR; ++r)
+            Lg[r] = __builtin_amdgcn_logf(half_sum32(act ? (r0 == r ? sf : (r0 + 1 == r ? ss : 0.f)) : 0.f)) * LN2;
+        float l_first = Lg[0], l_second = Lg[KR - 1];
+#pragma unroll
+        for (int r = 1; r < KR; ++r) l_first = r0 == r ? Lg[r] : l_first;
+#pragma unroll
+        for (int r = KR - 2; r >= 0; --r) l_second = r0 + 1 == r ? Lg[r] : l_second;
+        const rnnt_f4 res = rnnt_f4{(t.x - m_first) - l_first,
+                                  ns > 1 ? (t.y - m_first) - l_first : (t.y - m_second) - l_second,
+                                  ns > 2 ? (t.z - m_first) - l_first : (t.z - m_second) - l_second,
+                                  ns > 3 ? (t.w - m_first) - l_first : (t.w - m_second) - l_second};
+        if (act) strip[wv][(2 * i + half) * g4 + j] = res;
+    }
+    // the wave's 2 * RG_UN groups are 64 * g4 contiguous bytes: out of the strip in address order, one store instruction of
+    // 1024 bytes and one of the rest -- every instruction whole 64-byte granules (the strip is the wave's own: no barrier)
+    wave_sync_lds();
+    const int64_t f0 = w * (2 * RG_UN) * g4, nf = ngroups * g4;
+    const int nw = 2 * RG_UN * g4;                  // float4 of this wave (<= 64 * RG_UN)
+#pragma unroll
+    for (int k = 0; k < RG_UN; ++k) {
+        const int f = k * 64 + lane;
+        if (f < nw && f0 + f < nf) {
+            const rnnt_f4 r = strip[wv][f];
+            // written through and streaming (the s_nop: _isa_check.py, second rule)
+            asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(xout + f0 + f), "v"(r) : "memory");
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Rows in registers, L lanes per row (round 4; fused gather, V a multiple of 4).  Every row is 16-byte aligned, so
+// its L lanes load Q4 float4 each straight from HBM (a row instruction reads L*16 contiguous bytes: whole 128-byte lines
+// from L = 8 on), reduce with L-wide butterflies and never touch LDS; a wave carries UN passes of 64/L rows, all loads
+// issued before the first use.  The LDS-staged kernel spends 333 VALU instructions per wave on the same work at V = 128
+// (run-time column loops, two LDS reads per element; SQ counters: the vector ALUs 67 % busy at 4.7 TB/s,
+// profiles/r04_lsm_rows_ab.txt), this one about 150.  Fused gather only: as the plain log-softmax it runs at the rate of
+// the kernels that serve it now (V = 160 ... 600: 5.5-5.7 TB/s either way), so that mode is not instantiated.
+//   One lane per row (all rows of the wave in one go: the index arithmetic of map_cell is paid once per
+//   wave) fetches the row's blank and label logits again -- the wave has just read those lines -- and stores the pair.
+// ---------------------------------------------------------------------------
+// all-reduce over aligned groups of L lanes on DPP (quad permutes, then the mirrors: once every lane of a quad holds the
+// quad's value, reversing 8 / 16 lanes swaps whole quads / halves), lane ^ 16 on ds_swizzle, lane ^ 32 on a permute
+template <int L, bool MAX> __device__ __forceinline__ float lsm_group_reduce(float v) {
+#define LSM_STEP(w) v = MAX ? fmaxf(v, (w)) : v + (w)
+    if constexpr (L >= 2) LSM_STEP(lsm_dpp<0xB1>(v));
+    if constexpr (L >= 4) LSM_STEP(lsm_dpp<0x4E>(v));
+    if constexpr (L >= 8) LSM_STEP(lsm_dpp<0x141>(v));
+    if constexpr (L >= 16) LSM_STEP(lsm_dpp<0x140>(v));
+    if constexpr (L >= 32) LSM_STEP(lsm_swz16(v));
+    if constexpr (L >= 64) LSM_STEP(__shfl_xor(v, 32, WAVE));
+#undef LSM_STEP
+    return v;
+}
+
+// passes per wave: two for the 8-lane rows (V <= 128: 16 rows = 8 KB per wave at V = 128), one above (V = 256 ... 1024:
+// 299 / 998 us against 306 / 1057 with two, profiles/r04_lsm_rows_ab.txt)
+template <int L> struct RowsShape {
+    static constexpr int UN = L <= 8 ? 2 : 1;
+    static constexpr int RW = WAVE / L;            // rows per pass
+    static constexpr int RPW = RW * UN;            // rows per wave
+};
+
+// loads (all passes first), row maxima and log-sums of the rows at src[p] (one pointer per lane and pass: the lane's
+// first float4 of its row)
+template <typename E, int L, int Q, int MODE>
+__device__ __forceinline__ void lsm_rows_stats(const E* const (&src)[RowsShape<L>::UN], bool last_ok,
+                                               float (&mx)[RowsShape<L>::UN], float (&ls)[RowsShape<L>::UN]) {
+    constexpr int UN = RowsShape<L>::UN, VEC = 4;
+    const float ninf = -__builtin_inff();
+    const unsigned last_off = last_ok ? (Q - 1) * L : 0;   // a last float4 past the row: re-read the first, made -inf
+    float v[UN][Q][VEC];
+#pragma unroll
+    for (int p = 0; p < UN; ++p) {
+#pragma unroll
+        for (int i = 0; i < Q; ++i) {
+            const unsigned off = i < Q - 1 ? i * L : last_off;
+            const float4 t = lsm_ld4<RNNT_LSM_NT_MODE(MODE)>(src[p], off);
+            v[p][i][0] = t.x; v[p][i][1] = t.y; v[p][i][2] = t.z; v[p][i][3] = t.w;
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < UN; ++p)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e)
+            if (!last_ok) v[p][Q - 1][e] = ninf;
+#pragma unroll
+    for (int p = 0; p < UN; ++p) {
+        float m = ninf;
+#pragma unroll
+        for (int i = 0; i < Q; ++i)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) m = fmaxf(m, v[p][i][e]);
+        m = lsm_group_reduce<L, true>(m);
+        const float mb = -m * LOG2E;
+        float s = 0.0f;
+#pragma unroll
+        for (int i = 0; i < Q; ++i)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) s += __builtin_amdgcn_exp2f(__builtin_fmaf(v[p][i][e], LOG2E, mb));
+        s = lsm_group_reduce<L, false>(s);
+        mx[p] = m;
+        ls[p] = __builtin_amdgcn_logf(s) * LN2;
+    }
+}
+
+// lane l < RPW picks up the statistics of row l of the wave: first lane of group l % RW, pass l / RW
+template <int L>
+__device__ __forceinline__ void lsm_rows_stats_of_lane(int lane, const float (&mx)[RowsShape<L>::UN],
+                                                       const float (&ls)[RowsShape<L>::UN], float& m, float& lg) {
+    constexpr int UN = RowsShape<L>::UN, RW = RowsShape<L>::RW;
+    const int srcl = (lane % RW) * L;
+    m = 0.0f;
+    lg = 0.0f;
+#pragma unroll
+    for (int p = 0; p < UN; ++p) {
+        const float mp = __shfl(mx[p], srcl, WAVE), lp = __shfl(ls[p], srcl, WAVE);
+        if (lane / RW == p) { m = mp; lg = lp; }
+    }
+}
+
+// consecutive rows per wave
+template <typename E, int L, int Q>
+__global__ void __launch_bounds__(256)
+k_lsm_rows(const E* x, float* out, const int* __restrict__ labels, int64_t rows, int V, int T, int U, int blank) {
+    DenseMap map{labels, T, U};
+#include "lsm_body_rows.h"
+}
+template <typename E, int L, int Q>
+__global__ void __launch_bounds__(256)
+k_lsm_rows_compact(const E* x, float* out, PackedRows cr, int64_t rows, int V, int blank) {
+    CompactMap<true> map{cr, 0, 0};
+#include "lsm_body_rows.h"
+}
+
+// Along the diagonals (rows that are one or two whole 128-byte lines: V = 32, 64; T >= 16): a wave takes the 16 cells
+// (t' - k mod T, u0 + k), k = 0 ... 15 -- one run of 16 consecutive pairs of the diagonal-major plane, stored as one
+// 128-byte piece -- instead of 16 consecutive rows, whose pairs land 8 bytes each in 16 different lines (counters: 32
+// bytes written per pair; with the pairs stored linearly the kernel is 12-17 us of 145 faster at V = 128, N*T*U = 1.6 M).
+// V = 32 / 64: forward 96.5 / 134 us against 102 / 144; from V = 96 on the scattered rows cost what the stores save (174
+// vs 177, 199 vs 193: consecutive rows kept there).  No index division: grid = (T / 4 rounded up, column blocks of 16, N).
+template <typename E, int Q>
+__global__ void __launch_bounds__(256)
+k_lsm_rows_diag(const E* x, float* out, const int* __restrict__ labels, int V, int T, int U, int blank) {
+    constexpr int L = 8, VEC = 4, MODE = LSM_GATHER;
+    constexpr int UN = RowsShape<L>::UN, RW = RowsShape<L>::RW, RPW = RowsShape<L>::RPW;
+    static_assert(RPW == 16, "one run of 16 pairs per wave");
+    const int lane = threadIdx.x & 63, h = lane % L, rr = lane / L;
+    const int tp = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (tp >= T) return;
+    const int u0 = (int)blockIdx.y * RPW, n = (int)blockIdx.z;
+    const bool last_ok = (h + (Q - 1) * L) * VEC < V;
+    const size_t plane = (size_t)n * T;            // frames in front of this utterance
+    // the pair of cell k = lane (lane < 16), requested first
+    float xb = 0.0f, xl = 0.0f;
+    const bool own = lane < RPW && u0 + lane < U;
+    if (own) {
+        const int u = u0 + lane;
+        int t = tp - lane;
+        t += t < 0 ? T : 0;
+        const int lab = (u < U - 1) ? safe_label(labels[(size_t)n * (U - 1) + u], V, blank) : blank;
+        const E* xr = x + ((plane + t) * U + u) * V;
+        xb = lsm_ld1(xr + blank);
+        xl = lsm_ld1(xr + lab);
+    }
+    const E* src[UN];
+#pragma unroll
+    for (int p = 0; p < UN; ++p) {
+        const int k = p * RW + rr;
+        const int u = min(u0 + k, U - 1);          // (columns past the plane re-read the last one and are dropped)
+        int t = tp - k;
+        t += t < 0 ? T : 0;
+        src[p] = x + ((plane + t) * U + u) * V + h * VEC;
+    }
+    float mx[UN], ls[UN];
+    lsm_rows_stats<E, L, Q, MODE>(src, last_ok, mx, ls);
+    float m, lg;
+    lsm_rows_stats_of_lane<L>(lane, mx, ls, m, lg);
+    int r = tp + u0;
+    r = r >= T ? r % T : r;
+    if (own) reinterpret_cast<float2*>(out)[(plane + r) * U + u0 + lane] = make_float2((xb - m) - lg, (xl - m) - lg);
+}
+
+// rows per group for k_lsm_regs, or 0 when the kernel does not fit V: the largest KR <= 4 with KR*V a multiple of 4 and
+// KR*V/4 <= 32 lanes, if it keeps at least 20 of the 32 lanes of a half busy
+static int lsm_regs_rows_per_group(int V) {
+    if (V < 4) return 0;
+    int best = 0;
+    for (int k = 1; k <= 4; ++k)
+        if ((k * V) % 4 == 0 && (k * V) / 4 <= 32) best = k;
+    return (best && (best * V) / 4 >= 20) ? best : 0;
+}
+
+// One launch of a fused log-softmax kernel family, dense or compact by the map policy.
+template <typename E, int L, int MODE, bool WP, class Map>
+static void launch_lsm_small(unsigned grid, size_t lds, hipStream_t stream, const E* x, LsmOut<MODE, E>* out,
+                             const Map& map, int64_t rows, int V, int R, int q, int blank, LsmBwd bw) {
+    if constexpr (Map::COMPACT)
+        k_lsm_small_compact<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.r, rows, V, R, q, blank, bw);
+    else
+        k_lsm_small<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.labels, rows, V, R, q, map.T, map.U,
+                                                                       blank, bw);
+}
+template <typename E, int MODE, int TH, int NV, class Map>
+static void launch_lsm_large(unsigned grid, hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const Map& map,
+                             int64_t rows, int V, int blank, LsmBwd bw) {
+    if constexpr (Map::COMPACT)
+        k_lsm_large_compact<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
+    else
+        k_lsm_large<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
+}
+template <typename E, int MODE, class Map>
+static void launch_lsm_generic(unsigned grid, hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const Map& map,
+                               int64_t rows, int V, int blank, LsmBwd bw) {
+    if constexpr (Map::COMPACT)
+        k_lsm_generic_compact<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
+    else
+        k_lsm_generic<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
+}
+template <typename E, int L, int Q, class Map>
+static void launch_lsm_rows(unsigned grid, hipStream_t stream, const E* x, float* out, const Map& map, int64_t rows,
+                            int V, int blank) {
+    if constexpr (Map::COMPACT)
+        k_lsm_rows_compact<E, L, Q><<<grid, 256, 0, stream>>>(x, out, map.r, rows, V, blank);
+    else
+        k_lsm_rows<E, L, Q><<<grid, 256, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank);
+}
+
+// E: the storage type of x (and of out in LSM_BWD).  Every byte predicate of the routing is one of whole four-element
+// vectors (16 bytes of fp32, 8 of half), so a V takes the same kernel and the same lanes per row at every E.
+// Map: the row -> cell policy (DenseMap, CompactMap); compact rows never take the diagonal walk of k_lsm_rows_diag.
+template <int MODE, typename E, class Map>
+static hipError_t dispatch_lsm_map(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, Map map, int64_t rows, int V,
+                                   int blank, LsmBwd bw) {
+    constexpr bool GATHER = MODE == LSM_GATHER;
+    if (rows <= 0) return hipSuccess;
+    const bool aligned = (reinterpret_cast<uintptr_t>(x) % (4 * sizeof(E)) == 0) &&
+                         (GATHER || reinterpret_cast<uintptr_t>(out) % (4 * sizeof(*out)) == 0);
+    if constexpr (MODE == LSM_NORM) {
+        // rows in registers where the vocabulary allows it (RNNT_LSM_NO_REGS=1: the LDS-staged kernel, for A/B runs)
+        static const bool no_regs = ab_getenv("RNNT_LSM_NO_REGS") != nullptr;
+        // (below V = 32 -- four rows per group -- the LDS-staged kernel with its straight-line row pass is the faster one
+        //  since round 4: the c4 lattice with V=24 0.584 -> 0.536 ms per step, V=28 0.589-0.605 -> 0.584, c2 0.0343 -> 0.0336;
+        //  from V = 32 on this kernel wins inside the step: V=40 0.71 vs 0.73, V=50 0.870 vs 0.893; tools/step_rate.py)
+        const int kr = (aligned && !no_regs && V >= 32) ? lsm_regs_rows_per_group(V) : 0;
+        if (kr && rows >= kr) {
+            const int64_t ngroups = rows / kr;
+            const int64_t per_wg = 4 * RG_UN * 2;               // 4 waves x RG_UN groups x 2 halves
+            int64_t grid = (ngroups + per_wg - 1) / per_wg;
+            // every XCD streams a contiguous eighth of the tensor (as the row-per-workgroup kernel below; here it costs two
+            // scalar instructions): V=50 1.44 GB equal, 5.76 GB 5.66 -> 5.86 TB/s, V=64 6.25 -> 6.40, 100 5.92 -> 6.19, 128
+            // 6.15 -> 6.44; the c4 step in bench.py 0.8759 / 0.8781 / 0.8779 -> 0.8726 / 0.8702 / 0.8709 ms, three
+            // interleaved pairs (profiles/r04_lsm_xcd_order_ab.txt).  RNNT_LSM_REGS_XCD=0: the plain order (A/B runs)
+            static const int regs_xcd = ab_getenv("RNNT_LSM_REGS_XCD") ? atoi(ab_getenv("RNNT_LSM_REGS_XCD")) : 1;
+            if (regs_xcd) grid = (grid + 7) / 8 * 8;
+            if (grid < ((int64_t)1 << 31)) {
+#define LSM_REGS(KR) \
+    case KR: k_lsm_regs<E, KR, 3><<<(unsigned)grid, 256, 0, stream>>>(x, out, ngroups, V, regs_xcd); break;
+                switch (kr) { LSM_REGS(1) LSM_REGS(2) LSM_REGS(3) LSM_REGS(4) }
+#undef LSM_REGS
+                const hipError_t e = hipGetLastError();
+                const int64_t done = ngroups * kr;              // (a group boundary: vector aligned)
+                if (e != hipSuccess || done == rows) return e;
+                return dispatch_lsm_map<MODE, E>(stream, x + done * V, out + done * V, map, rows - done, V, blank, bw);
+            }
+        }
+    }
+    if constexpr (MODE == LSM_NORM) {
+        // 128 < V <= 1024 whose rows fill a cover of 64 ... 256 threads x one float4 (or an exact 64x2 / 64x3 / 128x2):
+        // the row-in-registers kernel below, one row per small workgroup, instead of the LDS-staged tiles.  Measured
+        // round 3 (tools/lsm_rate.py, 1.44 GB in, TB/s in + out, LDS-staged -> registers; profiles/r03_lsm_midv_probe.txt):
+        // V=256 5.82 -> 6.44, 496 5.33 -> 6.12, 500 5.14 -> 5.90, 512 5.77 -> 6.47, 768 5.58 -> 6.15, 980 5.26 -> 6.00,
+        // 1000 5.14 -> 6.10, 1024 5.76 -> 6.59; with 94 % of the lanes busy still +4 ... +10 % (484, 724, 964), below
+        // that -- and below 98 % for a single wave (V=244: 5.53 -> 5.23) -- the tiles win (V=200, 400, 600: 78 / 59 %).
+        static const bool no_lgr = ab_getenv("RNNT_LSM_NO_LGR") != nullptr;    // A/B runs: the LDS-staged kernel instead
+        if (aligned && !no_lgr && V % 4 == 0 && V > 128 && V <= 1024) {
+            const int nvec = V >> 2, th = (nvec + 63) / 64 * 64;
+            const unsigned grid = (unsigned)(rows < (1 << 22) ? rows : (1 << 22));
+#define LGR(TH, NV) { launch_lsm_large<E, MODE, TH, NV>(grid, stream, x, out, map, rows, V, blank, bw); return hipGetLastError(); }
+            if (nvec == 64) LGR(64, 1)
+            if (nvec == 128) LGR(64, 2)
+            if (nvec == 192) LGR(64, 3)
+            if (nvec == 256) LGR(128, 2)
+            if (th == 64 && nvec >= 63) LGR(64, 1)
+            if (th == 128 && nvec * 100 >= th * 94) LGR(128, 1)
+            if (th == 192 && nvec * 100 >= th * 94) LGR(192, 1)
+            if (th == 256 && nvec * 100 >= th * 94) LGR(256, 1)
+#undef LGR
+        }
+    }
+    if constexpr (MODE == LSM_GATHER) {
+        // V % 4 != 0 (c4's own V = 50: rows that pack into 16-byte groups only in twos) stays on the LDS-staged kernel below.
+        // Round 5 tried the rows-in-registers loads of k_lsm_regs for it once more, with what round 4 had learnt on
+        // k_lsm_rows -- the lane that stores a row's pair asks for its two logits itself, ahead of the group loads, or picks
+        // them out of an LDS copy of the groups: whole fused forward at c4 503-512 us (two and four groups per half-wave:
+        // 558 / 503; LDS copy 512) against 419-433 for the LDS-staged kernel then, and ~400 since its staging loop issues
+        // its loads first (k_lsm_small; the kernel alone 290 -> 225-255 us, 5.6-6.4 TB/s read against 7.0 for a bare
+        // read-only stream, tools/ubench/copy_rate.hip, profiles/r05_loads_first_ab.txt).
+        // Rows in registers, L lanes per row (k_lsm_rows), against the LDS-staged kernel below -- re-measured after that
+        // kernel got its straight-line row pass (forward of the fused entry, N=32, T=500, U=100, us, k_lsm_rows / LDS tiles;
+        // tools/fused_rate.py, profiles/r04_lsm_rows_ab.txt section 9): V=32 97 / 127, 64 140 / 146, 128 187 / 197, 256 320 /
+        // 341, 320 393 / 404; 448 512 / 522, 480 532 / 554, 500 561 / 583, 512 505 / 587, 544 609 / 753, 640 668 / 749, 768
+        // 791 / 812, 896 850 / 930, 1000 986 / 1089, 1024 1016 / 1128; but 96 180 / 163, 160 256 / 237, 192 285 / 262, 224 302 /
+        // 290, 352 426 / 418, 384 456 / 426, 400 510 / 485, and everything whose 8- or 16-lane row instructions straddle
+        // lines (V=100: 236 / 187, 132: 281 / 257) or needs float2 rows (V=50: 169 / 132).  Rule: the powers of two from 32
+        // to 256, and every V % 4 == 0 from 448 on.
+        // (RNNT_LSM_NO_ROWS=1: the LDS-staged kernel, for A/B runs; RNNT_LSM_NO_DIAG=1: consecutive rows per wave for
+        //  every V; RNNT_LSM_ROWS_ANY=1: this kernel for every V % 4 == 0)
+        static const bool no_rows = ab_getenv("RNNT_LSM_NO_ROWS") != nullptr;
+        static const bool no_diag = ab_getenv("RNNT_LSM_NO_DIAG") != nullptr;
+        static const bool rows_any = ab_getenv("RNNT_LSM_ROWS_ANY") != nullptr;
+        const bool rows_rule = V == 32 || V == 64 || V == 128 || V == 256 || V >= 448;
+        if (aligned && !no_rows && V % 4 == 0 && V >= 32 && V <= 1024 && (rows_rule || rows_any)) {
+            int L = 8;
+            while (L < 64 && L * 16 < V) L <<= 1;
+            const int q = (V / 4 + L - 1) / L;         // 1 ... 4
+            if constexpr (!Map::COMPACT) {             // (the diagonal walk needs the dense (T,U) grid)
+                const int* labels = map.labels;
+                const int T = map.T, U = map.U;
+                const int64_t N = rows / ((int64_t)T * U), nub = (U + 15) / 16;
+                if (V <= 64 && V % 32 == 0 && T >= 16 && !no_diag && N <= 65535 && nub <= 65535) {
+                    const dim3 grid((unsigned)((T + 3) / 4), (unsigned)nub, (unsigned)N);
+                    if (q == 1) k_lsm_rows_diag<E, 1><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
+                    else k_lsm_rows_diag<E, 2><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
+                    return hipGetLastError();
+                }
+            }
+            const int64_t rpw = L <= 8 ? 2 * (WAVE / L) : WAVE / L;       // RowsShape<L>::RPW
+            const int64_t grid = stream_grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
+            if ((rows + 4 * rpw - 1) / (4 * rpw) < ((int64_t)1 << 31) - 8) {
+#define LSM_ROWS(LL, QQ) \
+    if (L == LL && q == QQ) launch_lsm_rows<E, LL, QQ>((unsigned)grid, stream, x, out, map, rows, V, blank);
+#define LSM_ROWS_L(LL) LSM_ROWS(LL, 1) LSM_ROWS(LL, 2) LSM_ROWS(LL, 3) LSM_ROWS(LL, 4)
+                LSM_ROWS_L(8) LSM_ROWS_L(16) LSM_ROWS_L(32) LSM_ROWS_L(64)
+#undef LSM_ROWS_L
+#undef LSM_ROWS
+                return hipGetLastError();
+            }
+        }
+    }
+    if (aligned && V <= 1024) {
+        int L = 1;
+        while (L < 64 && L * 16 < V) L <<= 1;          // <= 16 columns per lane
+        const int q = (V + L - 1) / L;
+        const int rpp = SM_THREADS / L;                // rows per pass, a multiple of 4
+        int R = (sm_floats<E, MODE>() / V) / rpp * rpp;   // whole passes
+        if (R < rpp) R = rpp;
+        // wave-private tiles: each wave owns WAVE/L rows (a multiple of 4 for L <= 16), one pass
+        static const bool no_wp = ab_getenv("RNNT_LSM_NO_WP") != nullptr;
+        // Plain log-softmax only: measured 2-3 % faster there (0.506 -> 0.493 ms at c4), slower for the fused
+        // gather (its one-lane-per-row mapping phase wants all rows of the tile in ONE wave: 0.52 -> 0.556 ms)
+        // and for the fused backward (+15 us).
+        static const bool wp_fused = ab_getenv("RNNT_LSM_WP_FUSED") != nullptr;      // (A/B: the wave-private form in the fused modes)
+        const bool wp = (L <= 16) && !no_wp && (MODE == LSM_NORM || wp_fused);
+        if (wp) R = rpp;
+        const size_t lds = (size_t)R * V * sizeof(float) + (GATHER ? (size_t)R * sizeof(float2) : 0);
+        const unsigned grid = stream_grid((unsigned)((rows + R - 1) / R));
+#define LSM_SMALL(LL)                                                                           \
+    case LL:                                                                                    \
+        if (wp && LL <= 16)                                                                     \
+            launch_lsm_small<E, LL, MODE, (LL <= 16)>(grid, lds, stream, x, out, map, rows, V, R, q, blank, bw); \
+        else                                                                                    \
+            launch_lsm_small<E, LL, MODE, false>(grid, lds, stream, x, out, map, rows, V, R, q, blank, bw);     \
+        break;
+        switch (L) {
+            LSM_SMALL(1) LSM_SMALL(2) LSM_SMALL(4) LSM_SMALL(8) LSM_SMALL(16) LSM_SMALL(32)
+            LSM_SMALL(64)
+        }
+#undef LSM_SMALL
+    } else if (aligned && V % 4 == 0 && V <= LG_MAXV) {
+        // Which rows an XCD streams (plain log-softmax only).  Workgroups go to the eight XCDs by blockIdx mod 8, so with
+        // row = work item every XCD reads every eighth row of one moving front; with bw.xcd each streams a contiguous
+        // eighth of the tensor.  Measured (tools/lsm_rate.py, TB/s in + out, every-eighth / contiguous, 1.92 GB in; 8 GB
+        // in brackets; profiles/r04_lsm_xcd_order_ab.txt): V=1500 5.9 / 6.2, 3000 6.0 / 6.2 [5.95 / 6.6], 5000 5.8-5.9 /
+        // 6.0-6.5 [5.7 / 6.1], 7168 6.2 / 6.4, 8192 6.0-6.2 / 6.3-6.4 [5.8 / 6.2], 16384 5.2-5.4 / 6.0 [5.3 / 6.2];
+        // nothing at 2048, 4096, 5120 ... 6144, 12288; WORSE for the three-pass covers of 2048 < V/4 <= 3072 (V=10000:
+        // 6.0 / 5.6 [5.9 / 5.6]), which keep the plain order.  RNNT_LG_XCD=0 / 1 forces one or the other (A/B runs).
+        static const int xcd_force = ab_getenv("RNNT_LG_XCD") ? atoi(ab_getenv("RNNT_LG_XCD")) : -1;
+        // (fused gather / backward modes: no difference at c3 -- fused forward 0.3196 / 0.3184 / 0.3181 vs 0.3186 / 0.3178 /
+        //  0.3190 ms -- so they keep the plain order; RNNT_LG_XCD_FUSED=1 to try)
+        static const int xcd_fused = ab_getenv("RNNT_LG_XCD_FUSED") ? atoi(ab_getenv("RNNT_LG_XCD_FUSED")) : 0;
+        if constexpr (MODE == LSM_NORM) {
+            const int nv4 = V >> 2;
+            bw.xcd = xcd_force >= 0 ? (xcd_force != 0) : !(nv4 > 2048 && nv4 <= 3072);
+        } else {
+            bw.xcd = xcd_fused;
+        }
+        unsigned grid = (unsigned)(rows < (1 << 22) ? rows : (1 << 22));
+        if (bw.xcd) grid = (grid + 7u) & ~7u;
+        if constexpr (MODE == LSM_NORM) {
+            // The read + write stream wants about two float4 per thread and (nearly) every thread busy in every pass;
+            // workgroups of 512 or 1024 threads (which tile a CU's 2048 exactly) beat the sizes in between.  Round 2
+            // (profiles/r02_lsm_large_variants.txt, threads x passes, us for ~1.9 GB in + out): V=3000 256x3 734 /
+            // 384x2 663; V=8192 256x8 687 / 1024x2 666; V=10000 512x5 870 / 1024x3 828-834 / 896x3 811; V=16384 512x8
+            // 707 / 1024x4 723.  Re-swept in round 3 with the non-temporal policies in place
+            // (profiles/r03_xcd_run_order_probe.txt part 3, profiles/r03_lg_cover_ab.txt; TB/s in + out): V=5000 640x2
+            // 5.71 / 512x3 5.79-5.82 (c3 in bench.py: 0.696 -> 0.680 ms); V=5120 640x2 5.90 / 512x3 6.10; V=5600 768x2
+            // 5.96 / 512x3 6.17; V=6144 768x2 6.23 / 512x3 5.99 / 1024x2 6.11; V=7168 896x2 5.90 / 1024x2 6.16.
+            // The thread count is a template parameter on purpose (the same kernel with blockDim.x read at run
+            // time: 780 us at V=5000).
+            const int nvec = V >> 2;
+#define LGN(TH, NV) case TH: launch_lsm_large<E, MODE, TH, NV>(grid, stream, x, out, map, rows, V, blank, bw); break;
+            if (nvec > 3072) {
+                launch_lsm_large<E, MODE, 512, 8>(grid, stream, x, out, map, rows, V, blank, bw);
+            } else if (nvec > 2048) {
+                const int th = (nvec + 383) / 384 * 128;
+                switch (th) { LGN(768, 3) LGN(896, 3) LGN(1024, 3) }
+            } else if (nvec > 1536) {
+                launch_lsm_large<E, MODE, 1024, 2>(grid, stream, x, out, map, rows, V, blank, bw);
+            } else if (nvec > 1408) {
+                launch_lsm_large<E, MODE, 768, 2>(grid, stream, x, out, map, rows, V, blank, bw);
+            } else if (nvec > 1024) {
+                launch_lsm_large<E, MODE, 512, 3>(grid, stream, x, out, map, rows, V, blank, bw);
+            } else {
+                int th = (nvec + 255) / 256 * 128;
+                th = th < 256 ? 256 : th;
+                switch (th) { LGN(256, 2) LGN(384, 2) LGN(512, 2) }
+            }
+#undef LGN
+        } else {
+            // read-mostly modes (fused gather, fused backward): the smallest cover, for the residency
+            if (V <= 4096)
+                launch_lsm_large<E, MODE, 256, 4>(grid, stream, x, out, map, rows, V, blank, bw);
+            else if (V <= 8192)
+                launch_lsm_large<E, MODE, 256, 8>(grid, stream, x, out, map, rows, V, blank, bw);
+            else
+                launch_lsm_large<E, MODE, 512, 8>(grid, stream, x, out, map, rows, V, blank, bw);
+        }
+    } else {
+        launch_lsm_generic<E, MODE>((unsigned)((rows + 3) / 4), stream, x, out, map, rows, V, blank, bw);
+    }
+    return hipGetLastError();
+}
+
+template <int MODE, typename E = float>
+static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const int* labels,
+                               int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
+    return dispatch_lsm_map<MODE, E>(stream, x, out, DenseMap{labels, T, U}, rows, V, blank, bw);
+}
+// compact rows (kernels.h: PackedRows) in the two fused modes
+template <int MODE, typename E>
+static hipError_t dispatch_lsm_compact(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const PackedRows& cr,
+                                       int V, int blank, LsmBwd bw) {
+    static_assert(MODE != LSM_NORM, "the plain log-softmax has no map");
+    return dispatch_lsm_map<MODE, E>(stream, x, out, CompactMap<MODE == LSM_GATHER>{cr, 0, 0}, cr.rows, V, blank, bw);
+}
+
+// The five operations of kernels.h at one storage type: each lsm_<type>.hip instantiates them, and through them the kernels
+// above, for its own E.  (Members defined outside the class: `extern template` does not hold back an inline member.)
+template <typename E> struct LsmOps {
+    static hipError_t log_softmax(hipStream_t stream, const E* x, float* out, int64_t rows, int V);
+    static hipError_t gather(hipStream_t stream, const E* logits, const int* labels, float* ws2, int N, int T, int U, int V,
+                             int blank);
+    static hipError_t backward(hipStream_t stream, const E* logits, const int* labels, const float* g2_diagonal,
+                               const float* scale, E* dlogits, int N, int T, int U, int V, int blank);
+    static hipError_t gather_compact(hipStream_t stream, const E* logits, float* ws2, const PackedRows& cr, int V, int blank);
+    static hipError_t backward_compact(hipStream_t stream, const E* logits, const float* g2_rowmajor, const float* scale,
+                                       E* dlogits, const PackedRows& cr, int V, int blank);
+};
+template <typename E>
+hipError_t LsmOps<E>::log_softmax(hipStream_t stream, const E* x, float* out, int64_t rows, int V) {
+    return dispatch_lsm<LSM_NORM, E>(stream, x, out, nullptr, rows, V, 1, 1, 0, LsmBwd{nullptr, nullptr});
+}
+template <typename E>
+hipError_t LsmOps<E>::gather(hipStream_t stream, const E* logits, const int* labels, float* ws2, int N, int T, int U, int V,
+                             int blank) {
+    return dispatch_lsm<LSM_GATHER, E>(stream, logits, ws2, labels, (int64_t)N * T * U, V, T, U, blank,
+                                       LsmBwd{nullptr, nullptr});
+}
+template <typename E>
+hipError_t LsmOps<E>::backward(hipStream_t stream, const E* logits, const int* labels, const float* g2_diagonal,
+                               const float* scale, E* dlogits, int N, int T, int U, int V, int blank) {
+    return dispatch_lsm<LSM_BWD, E>(stream, logits, dlogits, labels, (int64_t)N * T * U, V, T, U, blank,
+                                    LsmBwd{reinterpret_cast<const float2*>(g2_diagonal), scale});
+}
+template <typename E>
+hipError_t LsmOps<E>::gather_compact(hipStream_t stream, const E* logits, float* ws2, const PackedRows& cr, int V,
+                                     int blank) {
+    return dispatch_lsm_compact<LSM_GATHER, E>(stream, logits, ws2, cr, V, blank, LsmBwd{nullptr, nullptr});
+}
+template <typename E>
+hipError_t LsmOps<E>::backward_compact(hipStream_t stream, const E* logits, const float* g2_rowmajor, const float* scale,
+                                       E* dlogits, const PackedRows& cr, int V, int blank) {
+    return dispatch_lsm_compact<LSM_BWD, E>(stream, logits, dlogits, cr, V, blank,
+                                            LsmBwd{reinterpret_cast<const float2*>(g2_rowmajor), scale});
+}
+extern template struct LsmOps<float>;
+extern template struct LsmOps<__bf16>;
+extern template struct LsmOps<_Float16>;
+
+}  // namespace rnnt

@@ -1,4 +1,4 @@
-// Body of the rows log-softmax kernel family (prologue.hip), included into the dense and the compact
+// Body of the rows log-softmax kernel family (lsm.h), included into the dense and the compact
 // kernel of each instantiation so that the code is the kernel's own: `map` is the row -> cell policy (DenseMap or
 // CompactMap) the including kernel declares.  Not a header of its own.
     constexpr int MODE = LSM_GATHER, VEC = 4;
