@@ -408,6 +408,18 @@ int rnnt_amd_debug_get_lattice_kernel(void);
  * first call (3 was the retired probability-domain kernel). */
 int rnnt_amd_debug_last_lattice_kernel(void);
 
+/* Diagnostics (version 108, additive): which lattice kernel a call with these facts WOULD run -- the library's own planner
+ * (csrc/lattice_plan.h) under the process's knobs, answered on the host: no launch, no device touched.
+ *   loader     0 diagonal-major workspace (every rnnt_amd_* loss entry), 1 row-major pairs, 2 dense + labels
+ *   resources  bit 0: redo flags and work queue present, bit 1: hand-over rings present, bit 2: 32-bit compact offsets
+ *   cus        compute units of the device; 0 = not given, answered as 256
+ *   pin        0 ... 3 as rnnt_amd_debug_set_lattice_kernel, -1 = the process's current pin
+ *   folded     the ring preparation rides in the launch that produces the pair plane (dense and gathered inputs)
+ * Returns  reported | block_diagonals << 8 | rings << 16  -- reported: what rnnt_amd_debug_last_lattice_kernel would say
+ * (1, 2, 4, 5), block_diagonals: 8 or 16 (lattice_wd's block size), rings: 1 when lattice_wd runs with flags and rings (the
+ * redo kernel behind it), 0 otherwise -- or -1 for N <= 0, T < 1, U < 1 or an unknown pin. */
+int rnnt_amd_debug_lattice_plan(int N, int T, int U, int loader, int resources, int cus, int pin, int folded);
+
 /* Library version, for the host-side loader. */
 int rnnt_amd_version(void);
 

@@ -76,7 +76,7 @@ def test_same_bits_as_the_single_workgroup_kernel(N, T, U, ragged):
 
 
 def test_default_route_picks_either_kernel_by_batch_and_the_bits_do_not_change():
-    """csrc/lattice.hip: launch_lattice takes the distributed kernel while 2N*ceil(U/64) <= 2 x the compute units and the
+    """csrc/lattice_plan.h: the plan takes the distributed kernel while 2N*ceil(U/64) <= 2 x the compute units and the
     single-workgroup one beyond.  One utterance, computed in a batch on either side of that line: the same bits."""
     N, T, U = 200, 700, 130                # 2 * 200 * 3 = 1200 column blocks: one workgroup per sweep
     logits, labels, xn, yn = make_case(31, 4, T, U, 5, ragged=True)
@@ -90,6 +90,31 @@ def test_default_route_picks_either_kernel_by_batch_and_the_bits_do_not_change()
     torch.cuda.synchronize()
     assert torch.equal(c_big[:4], c_small) and torch.equal(g_big[:4], g_small)
     assert torch.equal(c_big[-4:], c_small) and torch.equal(g_big[-4:], g_small)
+
+
+def test_the_launch_runs_what_the_plan_says():
+    """csrc/lattice_plan.h decides, launch_lattice launches: on the smallest shapes that reach each kernel -- wd's plain
+    launch, wl, wd with rings, ws and, under the ws pin at U = 700, the single-role kernel -- what ran is what
+    debug.lattice_plan answers for the same facts (the gathered route: flags and rings in the workspace, the ring
+    preparation folded into the re-layout) with the device's own CU count, and the bits are the ws pin's.  (The library reports the kernel only: wd's plain
+    launch against its ring form and the block size are the plan table's, tests/test_host_lattice_plan.py.)"""
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    ran = []
+    for N, T, U in [(2, 40, 33), (2, 40, 130), (2, 130, 400), (2, 100, 400), (2, 60, 700), (100, 40, 200)]:
+        logits, labels, xn, yn = make_case(N + T + U, min(N, 4), T, U, 5, ragged=True)
+        lp2 = torch.tensor(_pairs(logits, labels), device=DEV).repeat(N // min(N, 4), 1, 1, 1).contiguous()
+        txn = torch.tensor(np.tile(xn, N // min(N, 4)), device=DEV)
+        tyn = torch.tensor(np.tile(yn, N // min(N, 4)), device=DEV)
+        c, g = _run(lp2, txn, tyn, "auto")
+        ran.append(debug.last_lattice_kernel())
+        assert ran[-1] == debug.lattice_plan(N, T, U, cus=cus, pin="auto", folded=True).kernel, (N, T, U)
+        c_ws, g_ws = _run(lp2, txn, tyn, "ws")
+        assert debug.last_lattice_kernel() == debug.lattice_plan(N, T, U, cus=cus, pin="ws", folded=True).kernel, (N, T, U)
+        assert torch.equal(c, c_ws) and torch.equal(g, g_ws), (N, T, U)
+        if U == 700:
+            assert debug.last_lattice_kernel() == "lattice (single role)"
+    if cus == 256:      # (MI355X: each of the kernels is reached)
+        assert ran == ["lattice_wd", "lattice_wl", "lattice_wd", "lattice_ws", "lattice_wd", "lattice_ws"], ran
 
 
 def test_wider_than_one_workgroup_can_sweep():
@@ -224,7 +249,7 @@ def test_compact_layout_same_bits(N, T, U, V):
 @pytest.mark.parametrize("from_t", ["1", "1000000"], ids=["sixteen_everywhere", "eight_everywhere"])
 def test_both_block_sizes_same_bits(from_t):
     """csrc/lattice_wd_body.h is compiled twice: blocks of 8 diagonals and blocks of 16, the second the choice from launch
-    bound T >= 1024 on since round 6 (RNNT_WD_K16_FROM_T overrides; csrc/lattice_wd.hip has the history).  Each has to
+    bound T >= 1024 on since round 6 (RNNT_WD_K16_FROM_T overrides; DESIGN.md section 3.2 has the history).  Each has to
     give the bits of the single-workgroup kernel at every length: short and long shapes of SHAPES in a subprocess with
     the knob forcing one size everywhere."""
     code = r'''

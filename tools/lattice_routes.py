@@ -73,7 +73,7 @@ def run(shape, L, dev):
             same.append(f"{k} {'=' if ok else 'DIFFERS FROM'} {base}")
     cells_txt = " ".join(f"{k} {row[k][0]:7.1f} ({row[k][1]:6.1f})" if k in row else f"{k}       -         "
                          for k in ("ws", "wd", "wl", "auto"))
-    print(f"N={N:4d} T={T:5d} U={U:4d}   {cells_txt}   [{', '.join(same)}; auto -> {planes['auto'][3]}]", flush=True)
+    print(f"N={N:4d} T={T:5d} U={U:4d}   {cells_txt}   [{', '.join(same)}; auto -> {planes['auto'][3]}, planned {debug.lattice_plan(N, T, U, folded=False, pin='auto').kernel}]", flush=True)
     debug.set_lattice_kernel("auto")
 
 

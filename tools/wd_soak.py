@@ -19,7 +19,7 @@ Shapes (N, T, U; r = ragged lengths) -- the six-shape set, and a seventh since t
     32,250,100,r    two column blocks, k_lattice_wl, ragged
     32,500,200      four column blocks on a short batch: k_lattice_wl in its large-LDS form
     16,150,40       c2's lattice: one column block, k_lattice_wd as a plain launch
-    12,1300,120,r   two column blocks on a long sweep: k_lattice_wd with rings (from T >= 1200; csrc/lattice.hip), ragged
+    12,1300,120,r   two column blocks on a long sweep: k_lattice_wd with rings (from T >= 1200; csrc/lattice_plan.h), ragged
 WD_SOAK_SHAPES="N,T,U[,r] ..." overrides.
 
     python tools/wd_soak.py --seconds 60 [--procs 6]      (--procs: that many copies at once on the one GPU)

@@ -65,11 +65,12 @@ SYMBOLS = {
     "rnnt_amd_debug_get_lattice_kernel": (_i, []),
     "rnnt_amd_mismatch_flag": (ctypes.POINTER(ctypes.c_uint), [_i]),
     "rnnt_amd_debug_last_lattice_kernel": (_i, []),
+    "rnnt_amd_debug_lattice_plan": (_i, [_i] * 8),
     "rnnt_amd_version": (_i, []),
 }
 
 
-ABI_VERSION = 107   # rnnt_amd_version() of the library these argument lists belong to
+ABI_VERSION = 108   # rnnt_amd_version() of the library these argument lists belong to
 
 
 class RNNTStatusError(RuntimeError):

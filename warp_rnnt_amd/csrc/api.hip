@@ -53,7 +53,7 @@ size_t carve(void* base, size_t cells, int N, int T, int U, size_t pad, Workspac
     int* mismatch = reinterpret_cast<int*>(take((size_t)N * sizeof(int)));
     int* redo = reinterpret_cast<int*>(take(((size_t)N * 2 + 2) * sizeof(int)));   // flags, queue head, launch counter
     // (reserved by SHAPE, never by the current route: the size of a workspace must not depend on a setting)
-    unsigned long long* mail = reinterpret_cast<unsigned long long*>(take(lattice_mail_bytes(N, T, U)));
+    unsigned long long* mail = reinterpret_cast<unsigned long long*>(take(wd_mail_bytes(N, T, U)));
     if (w) *w = Workspace{alphas, betas, ws2, ll, mismatch, redo, mail};
     return off + pad;
 }
@@ -119,13 +119,17 @@ rnntStatus_t grads_in_place_then_split(rnntStream_t stream, float* grads, const 
 
 extern "C" {
 
-int rnnt_amd_version(void) { return 107; }
+int rnnt_amd_version(void) { return 108; }
 
 int rnnt_amd_debug_set_lattice_kernel(int kernel) { return set_lattice_kernel_override(kernel); }
 
 int rnnt_amd_debug_get_lattice_kernel(void) { return lattice_kernel_override(); }
 
 int rnnt_amd_debug_last_lattice_kernel(void) { return last_lattice_kernel(); }
+
+int rnnt_amd_debug_lattice_plan(int N, int T, int U, int loader, int resources, int cus, int pin, int folded) {
+    return debug_lattice_plan(N, T, U, loader, resources, cus, pin, folded);
+}
 
 volatile unsigned* rnnt_amd_mismatch_flag(int device) { return mismatch_words(device, true); }
 
@@ -174,7 +178,7 @@ rnntStatus_t run_warp_rnnt(rnntStream_t stream, unsigned int* counts, float* alp
         size_t off = align_up(cells * 2 * sizeof(float));
         int* redo = nullptr;
         unsigned long long* mail = nullptr;
-        const size_t flag_bytes = align_up(((size_t)N * 2 + 2) * sizeof(int)), ring_bytes = lattice_mail_bytes(N, T, U);
+        const size_t flag_bytes = align_up(((size_t)N * 2 + 2) * sizeof(int)), ring_bytes = wd_mail_bytes(N, T, U);
         if (aligned(base, ALIGN) && off + flag_bytes + align_up(ring_bytes) <= avail) {
             redo = reinterpret_cast<int*>(base + off);
             off += flag_bytes;

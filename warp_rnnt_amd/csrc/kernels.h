@@ -22,12 +22,12 @@ struct LatticeArgs {
     int* queue;           // work-item counter of k_lattice_wd; MUST be redo + 2N (zeroed together);
                           // queue[1] is its launch counter (never zeroed: any start value will do)
     unsigned long long* mail;  // its hand-over rings between column blocks (wd_mail_bytes), needed when U > 64
-    unsigned epoch;       // filled in by launch_lattice_wd
+    unsigned epoch;       // filled in by the ring kernel's launcher
     const unsigned* offs32;  // compact layout with the reference's 32-bit offsets (run_warp_rnnt_compact); used when
                              // offs is null
     int beta_only;        // compact shim, required_grad = false: the alpha sweep is skipped (its buffer aliases betas)
     int prepared;         // the rings and flags of this call have been prepared by the kernel in front (RingPrep below):
-                          // launch_lattice_wd does not launch k_prepare
+                          // the ring kernel's launcher does not launch k_prepare
 };
 
 // What k_prepare does in front of every launch of the ring kernel, as a parcel that the PRODUCER of the call's pair plane
@@ -78,39 +78,20 @@ __device__ inline size_t compact_base(const GradArgs& a, int n) { return a.offs 
 // gradients + costs + guard AND the dense (N,T,U,V) rows in one launch (a.lp = diagonal-major pairs, a.labels, a.V and
 // a.blank of the dense tensor; a.grads unused): for lattices whose planes sit in L2
 hipError_t launch_grads_dense(hipStream_t stream, const GradArgs& a, float* dense, int N);
-hipError_t launch_lattice(hipStream_t stream, const LatticeArgs& a, int N, int loader);
 // ONE arithmetic -- the reference's: one fp32 lse per cell in its operation order -- and several kernels that put the same
-// instructions on the chain and give the same bits (tests/test_gpu_wd.py); launch_lattice picks by shape.
-// lattice_ws.hip: compute + I/O wave pairs, all column blocks of a sweep in one workgroup (diagonal-major loader only);
-// hipErrorNotSupported when U > 512.  With a.redo set only the (utterance, direction) pairs flagged there are swept.
-hipError_t launch_lattice_ws(hipStream_t stream, const LatticeArgs& a, int N);
-// lattice_wd.hip: one three-wave workgroup per 64-column block, boundary columns through L2 rings (diagonal-major loader,
-// padded or 64-bit compact; any U); needs a.redo, a.queue and -- for U > 64 -- a.mail of wd_mail_bytes(N,T,U) bytes;
-// hipErrorNotSupported when they are missing.
-hipError_t launch_lattice_wd(hipStream_t stream, const LatticeArgs& a, int N);
-int device_cus(hipStream_t stream);   // compute units of the stream's device (csrc/lattice.hip)
+// instructions on the chain and give the same bits (tests/test_gpu_wd.py): lattice_plan.h picks one by shape, once per call,
+// and launch_lattice launches it (the per-kernel launchers: lattice_launch.h).
+hipError_t launch_lattice(hipStream_t stream, const LatticeArgs& a, int N, int loader);
+// what a workspace reserves for the hand-over rings of lattice_wd.hip (a function of the shape only)
 size_t wd_mail_bytes(int N, int T, int U);
-// ... and its single-workgroup form (lattice_wd.hip: k_lattice_wl): all column blocks of a sweep as waves of one
-// workgroup, boundary columns through LDS; needs nothing but the planes (no flags, no rings), padded or compact with
-// either offset width, honours a.redo and a.beta_only.  hipErrorNotSupported beyond max_blocks (<= 5) column blocks.
-hipError_t launch_lattice_wl(hipStream_t stream, const LatticeArgs& a, int N, int max_blocks);
-int wl_max_blocks();   // what launch_lattice lets it take by itself (RNNT_WL_MAX_BLOCKS, default 5)
-// what a workspace reserves for the hand-over rings (a function of the shape only)
-inline size_t lattice_mail_bytes(int N, int T, int U) { return wd_mail_bytes(N, T, U); }
-// In front of every launch of the kernel that hands boundary columns over through L2 rings (lattice_wd.hip owns the
-// per-device launch counter): clears n_flags words at `flags` (redo flags + queue head), stores the next value of the
-// launch counter at flags[n_flags] and zeroes ring_bytes (a multiple of 16) at `rings`.
-hipError_t launch_ring_prepare(hipStream_t stream, int* flags, int n_flags, void* rings, size_t ring_bytes);
-// the parcel for a launch of the ring kernel on `a` (flags, queue and rings as launch_lattice_wd would prepare them), or
-// false when there is nothing to prepare / the launch counter's address cannot be had for the stream's device
-bool wd_ring_prep(hipStream_t stream, const LatticeArgs& a, int N, RingPrep* prep);
-unsigned next_launch_epoch();     // host part of the launch epoch: random start, +1 per call
 // DEBUG / A-B ONLY: pin the kernel where several can serve (same bits whichever runs): 0 = by shape, 1 = lattice_ws.hip,
 // 2 = lattice_wd.hip, 3 = k_lattice_wl wherever it fits.  Initial value from the environment variable
 // RNNT_DEBUG_LATTICE_KERNEL=ws|wd|wl.  One process-wide atomic; nothing in the product sets it.
 int last_lattice_kernel();        // what the calling thread's last launch_lattice ran: 1 ws, 2 wd, 4 single-role, 5 wl (0 none yet)
 int lattice_kernel_override();
 int set_lattice_kernel_override(int k);  // returns the previous setting, or -1 for an unknown value (nothing changes)
+// rnnt_amd_debug_lattice_plan (include/warp_rnnt_amd.h): the plan for these facts under the process's knobs, no launch
+int debug_lattice_plan(int N, int T, int U, int loader, int resources, int cus, int pin, int folded);
 hipError_t launch_grads(hipStream_t stream, const GradArgs& a, int N, int loader, int writer);
 
 // streaming kernels in front of and behind the lattice: log-softmax backward (lsm_backward.hip), dense layout turns

@@ -5,6 +5,7 @@
 // :106-126 / :207-227 (the per-cell recurrences), :76-104 / :177-205 (the boundary row and column: plain sums).
 #pragma once
 #include "common.h"
+#include "lattice_plan.h"
 
 namespace rnnt {
 
@@ -12,7 +13,7 @@ namespace ws {
 
 constexpr int K = 8;             // diagonals per block
 constexpr int RING = 4 * K;      // mailbox ring entries per column-block boundary
-constexpr int MAXA = 8;          // compute waves per workgroup (=> 512 columns per pass)
+constexpr int MAXA = WS_MAX_BLOCKS;   // compute waves per workgroup (=> 512 columns per pass); the planner's limit for ws
 constexpr int PSLOTS = 3;        // LDS ring of pair blocks
 constexpr int VSLOTS = 2;        // LDS ring of value blocks
 constexpr int DLOAD = 2;         // I/O wave loads pairs this many blocks before it writes them to LDS

@@ -50,6 +50,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lattice_launch.h"
 #include "lattice_step.h"
 
 namespace rnnt {
@@ -64,27 +65,6 @@ namespace rnnt {
 #include "lattice_wd_body.h"
 #undef RNNT_WD_NS
 #undef RNNT_WD_KK
-
-// Blocks of 16 diagonals from launch bound T >= 1024 on, blocks of 8 below (tools/lattice_routes.py, us per alpha+beta launch,
-// 8 / 16: N=16, T=1500: U=64 68.7 / 64.5, U=300 102.4 / 100.2, U=512 123.8 / 122.6; T=700, U=100 48.2 / 48.8; T=150, U=40
-// 13.2 / 13.7; round 6, whole c4 step in bench.py: 0.8306 / 0.8219 ms).  History: the choice for most of round 5, then
-// switched off at its end -- with several processes sharing the GPU (tools/wd_soak.py) this instantiation was where the
-// storer's dry run, reloads left in flight into registers the compiler reused (lattice_wd_body.h: one_block), showed as
-// lost hand-overs and rare wrong plane values -- and opt-in while the fix was two commits old.  Re-qualified in round 6:
-// the reload check is part of the build, the end-of-block wait holds the refilled registers as operands, and the soak
-// record (profiles/r06_wd_soak.txt: millions of launches under three and six processes, every launch compared with
-// k_lattice_ws's bits) has no mismatch and no lost hand-over on either block size.
-// ONE column block per sweep (U <= 64) hands nothing over, so the longer blocks cost no hand-over distance: 16 from T >= 320
-// while every workgroup has a CU of its own (end of round 6, profiles/r06_k16_threshold.txt, 8 / 16: N=16, U=64: T=350
-// 22.2 / 21.5, T=500 28.5 / 27.5, T=700 36.8 / 34.6, T=1100 53.2 / 49.4; T=150, U=40 12.6 / 12.9 and N=256, T=500 36.4 / 37.3
-// stay with 8); several column blocks: T=640, U=300 63.3 / 64.7, T=900 76.3 / 75.3, T=1024 81.9 / 80.6 -- 1024 stays.
-// RNNT_WD_K16_FROM_T=<T> replaces both thresholds (1: blocks of 16 everywhere; a huge T: blocks of 8 everywhere; same bits).
-static int wd_block_diagonals(hipStream_t stream, int T, int U, int N) {
-    static const int from_t = getenv("RNNT_WD_K16_FROM_T") ? atoi(getenv("RNNT_WD_K16_FROM_T")) : -1;
-    if (from_t >= 0) return T >= from_t ? 16 : 8;
-    if (U <= WAVE && T >= 320 && (long long)2 * N <= (long long)device_cus(stream)) return 16;
-    return T >= 1024 ? 16 : 8;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Ring preparation (until round 5 in lattice_pd.hip, whose probability-domain kernel introduced the protocol).
@@ -108,14 +88,17 @@ __global__ void __launch_bounds__(256) k_prepare(int* p, int n, uint4* mail, siz
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < mail_vec; i += (size_t)gridDim.x * 256) mail[i] = z;
 }
 
-unsigned next_launch_epoch() {
+// host part of the launch epoch: random start, +1 per call
+static unsigned next_launch_epoch() {
     // granules of earlier launches (same buffer) never validate.  Random start so that a recycled allocation of
     // another process does not either; the device-side counter (k_prepare) is added in the kernel.
     static std::atomic<unsigned> epoch{std::random_device{}()};
     return epoch.fetch_add(1, std::memory_order_relaxed) + 1;
 }
 
-hipError_t launch_ring_prepare(hipStream_t stream, int* flags, int n_flags, void* rings, size_t ring_bytes) {
+// clears n_flags words at `flags` (redo flags + queue head), stores the next value of the launch counter at
+// flags[n_flags] and zeroes ring_bytes (a multiple of 16) at `rings`
+static hipError_t launch_ring_prepare(hipStream_t stream, int* flags, int n_flags, void* rings, size_t ring_bytes) {
     // the flags (2N ints) and the queue head are contiguous in the workspace (api.hip: carve).  One tiny kernel:
     // hipMemsetAsync of these few bytes becomes two fill kernels of ~5 us each.
     const size_t mail_vec = ring_bytes / 16;
@@ -142,7 +125,7 @@ static unsigned* launch_counter_address(hipStream_t stream) {
 }
 
 size_t wd_mail_bytes(int N, int T, int U) {
-    const int nA = (U + WAVE - 1) / WAVE;
+    const int nA = column_blocks(U);
     // (by SHAPE only -- the larger of the two block sizes' rings: a workspace's size must not depend on a setting)
     const size_t pitch = std::max(wd8::ring_pitch(T, U), wd16::ring_pitch(T, U));
     size_t bytes = nA < 2 ? 0 : (size_t)2 * N * (nA - 1) * pitch * sizeof(wd8::u64);
@@ -152,55 +135,45 @@ size_t wd_mail_bytes(int N, int T, int U) {
     return bytes;
 }
 
-// bytes of rings a launch on `a` uses (by the block size it will run with)
-static size_t wd_ring_bytes(hipStream_t stream, const LatticeArgs& a, int N) {
-    const int nA = (a.U + WAVE - 1) / WAVE;
-    const size_t pitch = wd_block_diagonals(stream, a.T, a.U, N) == 16 ? wd16::ring_pitch(a.T, a.U) : wd8::ring_pitch(a.T, a.U);
+// bytes of rings a launch on `a` with blocks of block_diagonals uses
+static size_t wd_ring_bytes(const LatticeArgs& a, int N, int block_diagonals) {
+    const int nA = column_blocks(a.U);
+    const size_t pitch = block_diagonals == 16 ? wd16::ring_pitch(a.T, a.U) : wd8::ring_pitch(a.T, a.U);
     return nA < 2 ? 0 : (size_t)2 * N * (nA - 1) * pitch * sizeof(wd8::u64);
 }
 
-bool wd_ring_prep(hipStream_t stream, const LatticeArgs& a, int N, RingPrep* prep) {
+bool wd_ring_prep(hipStream_t stream, const LatticeArgs& a, int N, int block_diagonals, RingPrep* prep) {
     if (N <= 0 || !a.redo || !a.queue || a.queue != a.redo + 2 * N) return false;
-    const int nA = (a.U + WAVE - 1) / WAVE;
-    if (nA > 1 && !a.mail) return false;
+    if (column_blocks(a.U) > 1 && !a.mail) return false;
     unsigned* counter = launch_counter_address(stream);
     if (!counter) return false;
-    const size_t ring_bytes = wd_ring_bytes(stream, a, N);
+    const size_t ring_bytes = wd_ring_bytes(a, N, block_diagonals);
     *prep = RingPrep{a.redo, 2 * N + 1, counter, reinterpret_cast<uint4*>(a.mail), ring_bytes / 16};
     return true;
 }
 
-// Needs a.redo, a.queue = a.redo + 2N with the launch counter's value behind it (and a.mail of wd_mail_bytes when U > 64);
-// zeroes flags, queue head and rings itself unless a.prepared.  With a.redo == nullptr and U <= 64 it is a plain launch.  Sweeps it
-// flags in a.redo (a lost hand-over: never observed outside the short-spin build) are for the caller to redo with the
-// single-workgroup kernel.
-hipError_t launch_lattice_wd(hipStream_t stream, const LatticeArgs& a0, int N) {
+hipError_t launch_lattice_wd(hipStream_t stream, const LatticeArgs& a0, int N, int block_diagonals, bool lone) {
     if (N <= 0) return hipSuccess;
-    const int nA = (a0.U + WAVE - 1) / WAVE;
-    if (a0.offs32 && (nA > 1 || a0.redo)) return hipErrorNotSupported;   // (32-bit offsets: the plain launch only)
+    const int nA = column_blocks(a0.U);
 #ifdef RNNT_WD_STATS
-    if (!a0.mail || !a0.redo || !a0.queue) return hipErrorNotSupported;
-    const bool lone = false;
-#else
-    // one column block per sweep (U <= 64) and no flags asked for: nothing to prepare, nothing to redo behind
-    const bool lone = nA == 1 && !a0.redo;
+    if (lone || !a0.mail) return hipErrorNotSupported;
 #endif
-    if (!lone && (!a0.redo || !a0.queue || (nA > 1 && !a0.mail))) return hipErrorNotSupported;
+    if (lone ? (nA != 1 || a0.redo) : (a0.offs32 || !a0.redo || !a0.queue || (nA > 1 && !a0.mail)))
+        return hipErrorNotSupported;                                     // (32-bit offsets: the plain launch only)
     if ((long long)2 * N * nA >= (1ll << 31)) return hipErrorNotSupported;
-    const bool k16 = wd_block_diagonals(stream, a0.T, a0.U, N) == 16;
     LatticeArgs a = a0;
-    if (lone) {
+    if (lone) {               // nothing to prepare, nothing to redo behind
         a.queue = nullptr;
         a.mail = nullptr;
     } else {
         a.epoch = next_launch_epoch();
         if (!a.prepared) {     // (prepared: the producer of this call's pair plane did it at the tail of its own launch)
-            const hipError_t e = launch_ring_prepare(stream, a.redo, 2 * N + 1, a.mail, wd_ring_bytes(stream, a, N));
+            const hipError_t e = launch_ring_prepare(stream, a.redo, 2 * N + 1, a.mail, wd_ring_bytes(a, N, block_diagonals));
             if (e != hipSuccess) return e;
         }
     }
     const dim3 grid(2 * N * nA), block(3 * WAVE);
-    if (k16) {
+    if (block_diagonals == 16) {
         if (is_compact(a)) wd16::k_lattice_wd<true><<<grid, block, 0, stream>>>(a, nA);
         else wd16::k_lattice_wd<false><<<grid, block, 0, stream>>>(a, nA);
     } else {
@@ -211,45 +184,25 @@ hipError_t launch_lattice_wd(hipStream_t stream, const LatticeArgs& a0, int N) {
 }
 
 // The single-workgroup form: one workgroup of 3 * ceil(U / 64) waves per sweep, nothing but the planes in global memory.
-// Padded or compact (either offset width); honours a.redo (only the flagged sweeps) and a.beta_only.
-// hipErrorNotSupported when the lattice is wider than the workgroup's LDS holds (wl_max_blocks() column blocks).
-int wl_max_blocks() {
-    // 2 column blocks (U <= 128) fit the 64 KiB every kernel gets; 5 (U <= 320) take the large-LDS opt-in, 148 KiB of
-    // the CU's 160 (LDS-DMA lands above 64 KiB as well: M0 carries the full address on gfx950 -- tests/test_gpu_wd.py).
-    // RNNT_WL_MAX_BLOCKS = 0 ... 5 overrides (0: the kernel is never chosen), for A/B runs.
-    static const int v = [] {
-        const char* e = ab_getenv("RNNT_WL_MAX_BLOCKS");
-        const int d = e ? atoi(e) : 5;
-        return d < 0 ? 0 : (d > 5 ? 5 : d);
-    }();
-    return v;
-}
-
+// Two column blocks (U <= 128) fit the 64 KiB every kernel gets; five (U <= 320) take the large-LDS opt-in, 148 KiB of the
+// CU's 160 (LDS-DMA lands above 64 KiB as well: M0 carries the full address on gfx950 -- tests/test_gpu_wd.py).
 hipError_t launch_lattice_wl(hipStream_t stream, const LatticeArgs& a, int N, int max_blocks) {
     if (N <= 0) return hipSuccess;
-    const int nA = (a.U + WAVE - 1) / WAVE;
+    const int nA = column_blocks(a.U);
     const size_t lds = sizeof(wd8::Smem) * nA;
-    if (nA > max_blocks || nA > 5 || lds > 160 * 1024) return hipErrorNotSupported;
+    if (nA > max_blocks || nA > WL_MAX_BLOCKS || lds > 160 * 1024) return hipErrorNotSupported;
     const dim3 grid(2 * N), block((nA == 2 ? 8 : 3 * nA) * WAVE);
     const bool compact = is_compact(a);
     const bool wide = nA > 2;                           // which instantiation (launch bounds: 512 / 960 threads)
-    const void* fn = wide ? (compact ? reinterpret_cast<const void*>(&wd8::k_lattice_wl<true, 5>)
-                                     : reinterpret_cast<const void*>(&wd8::k_lattice_wl<false, 5>))
-                          : (compact ? reinterpret_cast<const void*>(&wd8::k_lattice_wl<true, 2>)
-                                     : reinterpret_cast<const void*>(&wd8::k_lattice_wl<false, 2>));
     if (lds > 64 * 1024) {
-        // > 64 KiB of dynamic LDS: an opt-in per kernel and device (idempotent and thread-safe; remembered per device)
-        static std::atomic<bool> attr_set[4][64];
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-        const int ci = (wide ? 2 : 0) + (compact ? 1 : 0);
-        const bool tracked = dev >= 0 && dev < 64;
-        if (!tracked || !attr_set[ci][dev].load(std::memory_order_acquire)) {
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (int)(sizeof(wd8::Smem) * (wide ? 5 : 2)));
-            if (e != hipSuccess) return e;
-            if (tracked) attr_set[ci][dev].store(true, std::memory_order_release);
-        }
+        static std::atomic<bool> lds_allowed[4][64];
+        const void* fn = wide ? (compact ? reinterpret_cast<const void*>(&wd8::k_lattice_wl<true, 5>)
+                                         : reinterpret_cast<const void*>(&wd8::k_lattice_wl<false, 5>))
+                              : (compact ? reinterpret_cast<const void*>(&wd8::k_lattice_wl<true, 2>)
+                                         : reinterpret_cast<const void*>(&wd8::k_lattice_wl<false, 2>));
+        const hipError_t e = allow_large_lds(fn, sizeof(wd8::Smem) * (wide ? 5 : 2),
+                                             lds_allowed[(wide ? 2 : 0) + (compact ? 1 : 0)]);
+        if (e != hipSuccess) return e;
     }
     if (wide) {
         if (compact) wd8::k_lattice_wl<true, 5><<<grid, block, lds, stream>>>(a);

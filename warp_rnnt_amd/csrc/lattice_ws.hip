@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lattice_launch.h"
 #include "lattice_step.h"
 
 namespace rnnt {
@@ -247,31 +248,21 @@ __global__ void __launch_bounds__(2 * MAXA * WAVE) k_lattice_ws(const LatticeArg
 
 }  // namespace ws
 
-// Returns hipErrorNotSupported when the lattice is too wide for one pass (caller falls back to
-// the single-role kernel of lattice.hip).
+static_assert(ws::MAXA == WS_MAX_BLOCKS, "the planner sends a lattice here while one workgroup sweeps its width");
+
+// Returns hipErrorNotSupported when the lattice is too wide for one pass.
 hipError_t launch_lattice_ws(hipStream_t stream, const LatticeArgs& a, int N) {
     if (N <= 0) return hipSuccess;
-    const int nA = (a.U + WAVE - 1) / WAVE;
+    const int nA = column_blocks(a.U);
     if (nA > ws::MAXA) return hipErrorNotSupported;
     const size_t lds = sizeof(ws::Smem) * nA;
     const dim3 grid(2 * N), block(2 * nA * WAVE);
-    // > 64 KiB of dynamic LDS needs an opt-in per kernel and per device.  hipFuncSetAttribute is idempotent
-    // and thread-safe, so the only state kept is a per-(kernel, device) "already done" bit; devices beyond
-    // the table simply repeat the call every launch.
-    static std::atomic<bool> attr_set[2][64];
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
     const bool compact = is_compact(a);       // 64-bit (native) or 32-bit (core.h shims) offsets: compact_base()
-    const int ci = compact ? 1 : 0;
-    const bool tracked = dev >= 0 && dev < 64;
-    if (!tracked || !attr_set[ci][dev].load(std::memory_order_acquire)) {
-        const void* fn = compact ? reinterpret_cast<const void*>(&ws::k_lattice_ws<true>)
-                                : reinterpret_cast<const void*>(&ws::k_lattice_ws<false>);
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)(sizeof(ws::Smem) * ws::MAXA));
-        if (e != hipSuccess) return e;
-        if (tracked) attr_set[ci][dev].store(true, std::memory_order_release);
-    }
+    static std::atomic<bool> lds_allowed[2][64];
+    const void* fn = compact ? reinterpret_cast<const void*>(&ws::k_lattice_ws<true>)
+                             : reinterpret_cast<const void*>(&ws::k_lattice_ws<false>);
+    const hipError_t e = allow_large_lds(fn, sizeof(ws::Smem) * ws::MAXA, lds_allowed[compact ? 1 : 0]);
+    if (e != hipSuccess) return e;
     if (compact)
         ws::k_lattice_ws<true><<<grid, block, lds, stream>>>(a);
     else

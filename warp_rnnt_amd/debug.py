@@ -4,6 +4,7 @@ One arithmetic serves every call (the reference's fp32 log-sum-exp per cell); se
 instructions on the chain and the same bits, and the library picks one by shape.  `set_lattice_kernel` pins one for tests
 and timing runs (process-wide: `rnnt_amd_debug_set_lattice_kernel`, one atomic int; initial value from the environment
 variable RNNT_DEBUG_LATTICE_KERNEL = ws | wd | wl)."""
+import collections
 import contextlib
 
 from ._lib import load
@@ -38,3 +39,19 @@ def lattice_kernel(kernel):
 def last_lattice_kernel():
     """Name of the lattice kernel this thread's last loss call launched (``rnnt_amd_debug_last_lattice_kernel``)."""
     return LATTICE_KERNELS[load().rnnt_amd_debug_last_lattice_kernel()]
+
+
+LatticePlan = collections.namedtuple("LatticePlan", "kernel block_diagonals rings")
+LOADERS = ("skewed", "rowmajor", "dense")
+
+
+def lattice_plan(N, T, U, loader="skewed", flags=True, rings=True, offs32=False, cus=0, pin=None, folded=True):
+    """What the library's planner (csrc/lattice_plan.h) would run for a call with these facts, under this process's knobs
+    and without a launch (``rnnt_amd_debug_lattice_plan``): ``kernel`` as `last_lattice_kernel` would name it,
+    ``block_diagonals`` of lattice_wd (8 or 16), ``rings``: lattice_wd with flags and rings rather than its plain launch.
+    ``cus=0``: 256; ``pin=None``: the current pin."""
+    r = load().rnnt_amd_debug_lattice_plan(N, T, U, LOADERS.index(loader), int(flags) | int(rings) << 1 | int(offs32) << 2,
+                                           cus, -1 if pin is None else LATTICE_KERNEL_PINS.index(pin), int(folded))
+    if r < 0:
+        raise ValueError(f"no plan for N={N}, T={T}, U={U}, pin={pin!r}")
+    return LatticePlan(LATTICE_KERNELS[r & 255], r >> 8 & 255, bool(r >> 16 & 1))
