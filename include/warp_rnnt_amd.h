@@ -420,6 +420,30 @@ int rnnt_amd_debug_last_lattice_kernel(void);
  * redo kernel behind it), 0 otherwise -- or -1 for N <= 0, T < 1, U < 1 or an unknown pin. */
 int rnnt_amd_debug_lattice_plan(int N, int T, int U, int loader, int resources, int cus, int pin, int folded);
 
+/*
+ * The blank column as a plane of its own (version 108, additive).  A log-softmax that writes, beside its rows, the one
+ * column the loss reads from EVERY row -- col_out[row] = out[row*V + col], the same float, `rows` contiguous floats -- and
+ * a dense loss that takes it: its gather then fetches the label's dword of each row only and reads the blank as a
+ * coalesced stream (rows longer than a 128-byte line: a quarter fewer lines touched at V = 50).  Costs and gradients are
+ * those of the entries without the plane, bit for bit.
+ *   blank_plane   (N,T,U) floats, blank_plane[(n*T + t)*U + u] == log_probs[((n*T + t)*U + u)*V + blank]; the caller
+ *                 vouches for that (it is not checked); a null plane is RNNT_STATUS_INVALID_ARGUMENT.
+ * The log-softmax entries: as their namesakes without the plane (out may alias x for fp32); 0 <= col < V.
+ * The loss entry: the RNNT_IN_LOG_PROBS_DENSE call of the plain loss entry with every grads_kind it takes there.
+ */
+rnntStatus_t rnnt_amd_log_softmax_plane(rnntStream_t stream, const float *x, float *out, float *col_out, int64_t rows,
+                                        int V, int col);
+rnntStatus_t rnnt_amd_log_softmax_plane_typed(rnntStream_t stream, int dtype, const void *x, float *out, float *col_out,
+                                              int64_t rows, int V, int col);
+rnntStatus_t rnnt_amd_loss_blank_plane(rnntStream_t stream, void *workspace, const float *log_probs,
+                                       const float *blank_plane, const int *labels, const int *xn, const int *yn,
+                                       float *costs, float *grads, int grads_kind, int N, int T, int U, int V, int blank,
+                                       float fastemit_lambda);
+/* Diagnostics: the gather-only entry above with the plane, so that the two forms of the gather can be timed alone. */
+rnntStatus_t rnnt_amd_debug_gather_only_blank_plane(rnntStream_t stream, void *workspace, const float *log_probs,
+                                                    const float *blank_plane, const int *labels, int N, int T, int U,
+                                                    int V, int blank);
+
 /* Library version, for the host-side loader. */
 int rnnt_amd_version(void);
 

@@ -68,7 +68,7 @@ def check_inputs(xs, ys, xn, yn, xs_dtypes=None):
             raise RuntimeError(f"{name} must be on the same device as xs")
 
 
-def _native_call(fn, xs, ys, xn, yn, blank, fastemit_lambda):
+def _native_call(fn, xs, ys, xn, yn, blank, fastemit_lambda, *more):
     """One call into the compiled binding.  The forward/backward guard (core_gather.cu:341-354): by default a look at the
     device's sticky diagnostics words before the call (no synchronisation; what earlier kernels reported becomes a
     RuntimeWarning -- warp_rnnt_amd/_mismatch.py); WARP_RNNT_AMD_CHECK_MISMATCH = warn | raise reads this call's own
@@ -77,7 +77,7 @@ def _native_call(fn, xs, ys, xn, yn, blank, fastemit_lambda):
     exact = policy in ("warn", "raise", "1", "on")
     if xs.is_cuda:
         _mismatch.poll(xs.device)
-    costs, grads, mismatch = fn(xs, ys, xn, yn, blank, fastemit_lambda, exact)
+    costs, grads, mismatch = fn(xs, ys, xn, yn, blank, fastemit_lambda, exact, *more)
     if exact:
         bad = mismatch.nonzero().flatten().tolist()          # host synchronisation (opt-in)
         if bad:
@@ -92,6 +92,7 @@ def _native_call(fn, xs, ys, xn, yn, blank, fastemit_lambda):
 def rnnt_loss(xs, ys, xn, yn, blank=0, fastemit_lambda=0.0):
     """(costs (N,), grads like xs).  blank == -1 selects the gathered (N,T,U,2) layout."""
     if _native is not None:
+        _ops._note_loss_plane(False)
         return _native_call(_native.rnnt_loss, xs, ys, xn, yn, blank, fastemit_lambda)
     check_inputs(xs, ys, xn, yn)
     if blank == -1:
@@ -99,14 +100,21 @@ def rnnt_loss(xs, ys, xn, yn, blank=0, fastemit_lambda=0.0):
             raise RuntimeError("xs must have values only for blank and label")
         return _ops.loss(xs, None, xn, yn, _ops.IN_LOG_PROBS_GATHERED, _ops.GRADS_GATHERED,
                          -1, fastemit_lambda)
-    return _ops.loss(xs, ys, xn, yn, _ops.IN_LOG_PROBS_DENSE, _ops.GRADS_DENSE, blank, fastemit_lambda)
+    return _ops.loss(xs, ys, xn, yn, _ops.IN_LOG_PROBS_DENSE, _ops.GRADS_DENSE, blank, fastemit_lambda,
+                     use_blank_plane=False)
 
 
 def rnnt_loss_gather(xs, ys, xn, yn, blank=0, fastemit_lambda=0.0):
     """Native form of the wrapper's ``gather=True`` branch: dense log-probs in, costs and the
-    (opaque, diagonal-major) gathered gradients out; feed those to :func:`rnnt_loss_gather_backward`."""
+    (opaque, diagonal-major) gathered gradients out; feed those to :func:`rnnt_loss_gather_backward`.
+    Log-probs that ``warp_rnnt_amd.ops.log_softmax`` returned with their blank plane, and that are still what they were,
+    are served through it (``ops.blank_plane_of``): the same bits from fewer bytes."""
     if _native is not None:
-        return _native_call(_native.rnnt_loss_gather, xs, ys, xn, yn, blank, fastemit_lambda)
+        plane = _ops.blank_plane_of(xs, blank) if isinstance(xs, torch.Tensor) else None
+        _ops._note_loss_plane(plane is not None)
+        if plane is None:
+            return _native_call(_native.rnnt_loss_gather, xs, ys, xn, yn, blank, fastemit_lambda)
+        return _native_call(_native.rnnt_loss_gather, xs, ys, xn, yn, blank, fastemit_lambda, plane)
     check_inputs(xs, ys, xn, yn)
     return _ops.loss(xs, ys, xn, yn, _ops.IN_LOG_PROBS_DENSE, _ops.GRADS_GATHERED_DIAGONAL,
                      blank, fastemit_lambda)

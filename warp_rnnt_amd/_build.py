@@ -27,7 +27,7 @@ RELOAD_CHECKED = {"lattice_wd.hip": (8, 600)}
 # Sources with inline assembly of any kind: their ISA is walked for the wait-state hazards the compiler's recognizer does
 # not resolve around an `asm` statement (_isa_check: third rule -- DPP behind a VALU write, a transcendental's result in
 # the next slot, a VALU write behind a wide store).  Value: kernels the file is known to hold at least (for the
-# log-softmax units and to_diagonal.hip that is what they hold today).
+# log-softmax units and to_diagonal.hip that is what they held before the blank-plane variants: four and two more now).
 HAZARD_CHECKED = {"lattice_wd.hip": 8, "lattice.hip": 4, "lattice_ws.hip": 2, "lsm_f32.hip": 132, "lsm_bf16.hip": 132,
                   "lsm_f16.hip": 132, "to_diagonal.hip": 8}
 

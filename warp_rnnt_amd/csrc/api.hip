@@ -247,10 +247,12 @@ rnntStatus_t run_warp_rnnt_gather(rnntStream_t stream, unsigned int* counts, flo
     return RNNT_STATUS_SUCCESS;
 }
 
-// rnnt_amd_loss with the element type of the input (RNNT_DTYPE_*: anything but fp32 for RNNT_IN_LOGITS_DENSE only)
+// rnnt_amd_loss with the element type of the input (RNNT_DTYPE_*: anything but fp32 for RNNT_IN_LOGITS_DENSE only);
+// blank_plane (RNNT_IN_LOG_PROBS_DENSE only, or nullptr): the blank column of the log-probs as a plane of its own
 static rnntStatus_t loss_of_type(rnntStream_t stream, void* workspace, int input_kind, int dtype, const void* input_any,
                                  const int* labels, const int* xn, const int* yn, float* costs, float* grads,
-                                 int grads_kind, int N, int T, int U, int V, int blank, float fastemit_lambda) {
+                                 int grads_kind, int N, int T, int U, int V, int blank, float fastemit_lambda,
+                                 const float* blank_plane = nullptr) {
     if (!dtype_ok(dtype) || (dtype != RNNT_DTYPE_F32 && input_kind != RNNT_IN_LOGITS_DENSE))
         return RNNT_STATUS_INVALID_ARGUMENT;
     const float* input = static_cast<const float*>(input_any);      // (fp32 input kinds only)
@@ -275,7 +277,7 @@ static rnntStatus_t loss_of_type(rnntStream_t stream, void* workspace, int input
     switch (input_kind) {
         case RNNT_IN_LOG_PROBS_DENSE:
             la.prepared = lattice_ring_prep(stream, la, N, LOAD_SKEWED, &prep) ? 1 : 0;
-            e = launch_gather(stream, input, labels, w.ws2, N, T, U, V, blank, true, &prep); break;
+            e = launch_gather(stream, input, labels, w.ws2, N, T, U, V, blank, true, &prep, blank_plane); break;
         case RNNT_IN_LOG_PROBS_GATHERED:
             la.prepared = lattice_ring_prep(stream, la, N, LOAD_SKEWED, &prep) ? 1 : 0;
             e = launch_reskew(stream, input, w.ws2, N, T, U, &prep); break;
@@ -325,6 +327,15 @@ rnntStatus_t rnnt_amd_loss(rnntStream_t stream, void* workspace, int input_kind,
                         U, V, blank, fastemit_lambda);
 }
 
+rnntStatus_t rnnt_amd_loss_blank_plane(rnntStream_t stream, void* workspace, const float* log_probs,
+                                       const float* blank_plane, const int* labels, const int* xn, const int* yn,
+                                       float* costs, float* grads, int grads_kind, int N, int T, int U, int V, int blank,
+                                       float fastemit_lambda) {
+    if (!blank_plane) return RNNT_STATUS_INVALID_ARGUMENT;
+    return loss_of_type(stream, workspace, RNNT_IN_LOG_PROBS_DENSE, RNNT_DTYPE_F32, log_probs, labels, xn, yn, costs, grads,
+                        grads_kind, N, T, U, V, blank, fastemit_lambda, blank_plane);
+}
+
 rnntStatus_t rnnt_amd_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits, const int* labels,
                                   const int* xn, const int* yn, float* costs, float* grads, int grads_kind, int N, int T,
                                   int U, int V, int blank, float fastemit_lambda) {
@@ -351,6 +362,19 @@ rnntStatus_t rnnt_amd_debug_gather_only(rnntStream_t stream, void* workspace, co
     Workspace w;
     carve(workspace, N, T, U, &w);
     if (launch_gather(stream, log_probs, labels, w.ws2, N, T, U, V, blank, true) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// ... and the same step with the blank column read from its plane (k_to_diagonal<true, ., true>): the two forms timed alone
+rnntStatus_t rnnt_amd_debug_gather_only_blank_plane(rnntStream_t stream, void* workspace, const float* log_probs,
+                                                    const float* blank_plane, const int* labels, int N, int T, int U,
+                                                    int V, int blank) {
+    if (!dims_ok(N, T, U) || !workspace || !vocab_ok(V, blank) || !blank_plane) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (U > 1 && !labels) return RNNT_STATUS_INVALID_ARGUMENT;
+    Workspace w;
+    carve(workspace, N, T, U, &w);
+    if (launch_gather(stream, log_probs, labels, w.ws2, N, T, U, V, blank, true, nullptr, blank_plane) != hipSuccess)
         return RNNT_STATUS_PROLOGUE_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
@@ -757,6 +781,19 @@ rnntStatus_t rnnt_amd_log_softmax_typed(rnntStream_t stream, int dtype, const vo
 
 rnntStatus_t rnnt_amd_log_softmax(rnntStream_t stream, const float* x, float* out, int64_t rows, int V) {
     return rnnt_amd_log_softmax_typed(stream, RNNT_DTYPE_F32, x, out, rows, V);
+}
+
+rnntStatus_t rnnt_amd_log_softmax_plane_typed(rnntStream_t stream, int dtype, const void* x, float* out, float* col_out,
+                                              int64_t rows, int V, int col) {
+    if (!dtype_ok(dtype) || rows < 0 || V < 1 || col < 0 || col >= V || !col_out) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (launch_log_softmax_plane(stream, dtype, x, out, col_out, rows, V, col) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_log_softmax_plane(rnntStream_t stream, const float* x, float* out, float* col_out, int64_t rows,
+                                        int V, int col) {
+    return rnnt_amd_log_softmax_plane_typed(stream, RNNT_DTYPE_F32, x, out, col_out, rows, V, col);
 }
 
 rnntStatus_t rnnt_amd_log_softmax_backward(rnntStream_t stream, const float* grad_out, const float* out,

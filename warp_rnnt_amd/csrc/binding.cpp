@@ -59,8 +59,19 @@ rnntStream_t current_stream(const at::Tensor& t) {
 std::tuple<at::Tensor, at::Tensor, at::Tensor> loss(const at::Tensor& input, const at::Tensor& labels,
                                                     const at::Tensor& xn, const at::Tensor& yn, int input_kind,
                                                     int grads_kind, int64_t blank, double fastemit_lambda,
-                                                    bool want_mismatch) {
+                                                    bool want_mismatch,
+                                                    const c10::optional<at::Tensor>& blank_plane = c10::nullopt) {
     const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+    // the blank column of dense log-probs as a plane of its own (log_softmax_plane below wrote it; the Python side vouches
+    // that it still belongs to `input`)
+    const bool planed = blank_plane.has_value() && blank_plane->defined();
+    if (planed) {
+        TORCH_CHECK(input_kind == RNNT_IN_LOG_PROBS_DENSE, "blank_plane goes with dense log-probs");
+        TORCH_CHECK(blank_plane->is_contiguous() && blank_plane->scalar_type() == at::ScalarType::Float &&
+                    blank_plane->device() == input.device() &&
+                    blank_plane->numel() == input.size(0) * input.size(1) * input.size(2),
+                    "blank_plane must be a contiguous Float tensor of N*T*U elements on the device of xs");
+    }
     const int64_t N = input.size(0), T = input.size(1), U = input.size(2), V = input.size(3);
     TORCH_CHECK(N < (1ll << 31) && T < (1ll << 31) && U < (1ll << 31) && V < (1ll << 31),
                 "rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes");
@@ -80,11 +91,15 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> loss(const at::Tensor& input, con
     TORCH_CHECK(ws_bytes != 0, "rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): unsupported sizes N=", N, " T=", T,
                 " U=", U);
     at::Tensor ws = at::empty({(int64_t)ws_bytes}, fopt.dtype(at::kByte));
-    const int st = rnnt_amd_loss(current_stream(input), ws.data_ptr(), input_kind, input.data_ptr<float>(),
-                                 labels.defined() && labels.numel() ? labels.data_ptr<int>() : nullptr,
-                                 xn.data_ptr<int>(), yn.data_ptr<int>(), costs.data_ptr<float>(),
-                                 grads.data_ptr<float>(), grads_kind, (int)N, (int)T, (int)U, (int)V, (int)blank,
-                                 (float)fastemit_lambda);
+    const int* labels_ptr = labels.defined() && labels.numel() ? labels.data_ptr<int>() : nullptr;
+    const int st = planed
+        ? rnnt_amd_loss_blank_plane(current_stream(input), ws.data_ptr(), input.data_ptr<float>(),
+                                    blank_plane->data_ptr<float>(), labels_ptr, xn.data_ptr<int>(), yn.data_ptr<int>(),
+                                    costs.data_ptr<float>(), grads.data_ptr<float>(), grads_kind, (int)N, (int)T, (int)U,
+                                    (int)V, (int)blank, (float)fastemit_lambda)
+        : rnnt_amd_loss(current_stream(input), ws.data_ptr(), input_kind, input.data_ptr<float>(), labels_ptr,
+                        xn.data_ptr<int>(), yn.data_ptr<int>(), costs.data_ptr<float>(), grads.data_ptr<float>(),
+                        grads_kind, (int)N, (int)T, (int)U, (int)V, (int)blank, (float)fastemit_lambda);
     check_status(st);
     if (want_mismatch) {
         const int64_t off = (int64_t)rnnt_amd_workspace_mismatch_offset((int)N, (int)T, (int)U);
@@ -111,10 +126,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> rnnt_loss(const at::Tensor& xs, c
 std::tuple<at::Tensor, at::Tensor, at::Tensor> rnnt_loss_gather(const at::Tensor& xs, const at::Tensor& ys,
                                                                 const at::Tensor& xn, const at::Tensor& yn,
                                                                 int64_t blank, double fastemit_lambda,
-                                                                bool want_mismatch) {
+                                                                bool want_mismatch,
+                                                                const c10::optional<at::Tensor>& blank_plane) {
     check_inputs(xs, ys, xn, yn);
     return loss(xs, ys, xn, yn, RNNT_IN_LOG_PROBS_DENSE, RNNT_GRADS_GATHERED_DIAGONAL, blank, fastemit_lambda,
-                want_mismatch);
+                want_mismatch, blank_plane);
 }
 
 // d loss / d log_probs (N,T,U,V) = scatter-add of the gathered grads times grad_costs[n]
@@ -245,6 +261,26 @@ at::Tensor log_softmax(const at::Tensor& x, const c10::optional<at::Tensor>& out
     return out;
 }
 
+// log_softmax and, beside it, column `col` of the result as a contiguous plane of x.numel() / V floats (the blank
+// log-prob of every lattice cell: rnnt_loss_gather takes it back as blank_plane): (out, plane)
+std::tuple<at::Tensor, at::Tensor> log_softmax_plane(const at::Tensor& x, const c10::optional<at::Tensor>& out_opt,
+                                                     int64_t col) {
+    RNNT_CHECK_CONTIGUOUS(x); RNNT_CHECK_FLOAT(x); RNNT_CHECK_CUDA(x);
+    at::Tensor out = out_opt.has_value() ? *out_opt : at::empty_like(x);
+    TORCH_CHECK(out.is_contiguous() && out.scalar_type() == at::ScalarType::Float && out.sizes() == x.sizes() &&
+                out.device() == x.device(), "out must be a contiguous Float tensor like x");
+    TORCH_CHECK(x.dim() >= 1 && x.size(-1) >= 1, "x must have a vocabulary axis");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+    const int64_t V = x.size(-1);
+    const int64_t rows = x.numel() / V;
+    TORCH_CHECK(V < (1ll << 31), "vocabulary too large");
+    TORCH_CHECK(col >= 0 && col < V, "col is not a vocabulary index");
+    at::Tensor plane = at::empty({rows}, x.options());
+    check_status(rnnt_amd_log_softmax_plane(current_stream(x), x.data_ptr<float>(), out.data_ptr<float>(),
+                                            plane.data_ptr<float>(), rows, (int)V, (int)col));
+    return {out, plane};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -252,7 +288,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rnnt_loss", &rnnt_loss, py::arg("xs"), py::arg("ys"), py::arg("xn"), py::arg("yn"), py::arg("blank") = 0,
           py::arg("fastemit_lambda") = 0.0, py::arg("want_mismatch") = false);
     m.def("rnnt_loss_gather", &rnnt_loss_gather, py::arg("xs"), py::arg("ys"), py::arg("xn"), py::arg("yn"),
-          py::arg("blank") = 0, py::arg("fastemit_lambda") = 0.0, py::arg("want_mismatch") = false);
+          py::arg("blank") = 0, py::arg("fastemit_lambda") = 0.0, py::arg("want_mismatch") = false,
+          py::arg("blank_plane") = py::none());
     m.def("rnnt_loss_gather_backward", &rnnt_loss_gather_backward, py::arg("grad_costs"), py::arg("grads_diagonal"),
           py::arg("ys"), py::arg("xn"), py::arg("yn"), py::arg("V"), py::arg("blank") = 0);
     // (names and keywords of the reference's module, binding.cpp:255-268)
@@ -262,5 +299,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rnnt_loss_compact_backward", &rnnt_loss_compact_backward, py::arg("grad_costs"), py::arg("grad_xs"),
           py::arg("cumSum"), py::arg("loc"), py::arg("V"), py::arg("blank") = 0);
     m.def("log_softmax", &log_softmax, py::arg("x"), py::arg("out") = py::none());
+    m.def("log_softmax_plane", &log_softmax_plane, py::arg("x"), py::arg("out") = py::none(), py::arg("col") = 0);
     m.def("library_version", []() { return rnnt_amd_version(); });
 }

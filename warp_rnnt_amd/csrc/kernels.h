@@ -98,8 +98,11 @@ hipError_t launch_grads(hipStream_t stream, const GradArgs& a, int N, int loader
 // (to_diagonal.hip), expand (expand.hip)
 hipError_t launch_log_softmax_backward(hipStream_t stream, const float* dy, const float* y, float* dx,
                                        int64_t rows, int V);
+// blank_plane (skewed only; nullptr: none): (N,T,U) floats, blank_plane[cell] == log_probs[cell*V + blank] -- what
+// launch_log_softmax_plane wrote beside the log-probs; the gather then reads the label's dword of every row only
 hipError_t launch_gather(hipStream_t stream, const float* log_probs, const int* labels, float* out2,
-                         int N, int T, int U, int V, int blank, bool skewed, const RingPrep* prep = nullptr);
+                         int N, int T, int U, int V, int blank, bool skewed, const RingPrep* prep = nullptr,
+                         const float* blank_plane = nullptr);
 hipError_t launch_reskew(hipStream_t stream, const float* lp2_rowmajor, float* ws2, int N, int T, int U,
                          const RingPrep* prep = nullptr);
 // diagonal-major pairs (b == nullptr: float2 plane at a; else two float planes) -> row-major (N,T,U,2)
@@ -154,10 +157,13 @@ hipError_t launch_joint_bwd(hipStream_t stream, int dtype, int act, const void* 
                             const float* grads, const float* grad_costs, void* wt, float* dw_part, float* db_part,
                             int splits, void* df, void* dg, float* dweight, float* dbias, int N, int T, int U, int H,
                             int V, int blank);
-// The forward log-softmax family (lsm.h; lsm_f32.hip holds these five launchers) for logits of any RNNT_DTYPE_*
+// The forward log-softmax family (lsm.h; lsm_f32.hip holds these launchers) for logits of any RNNT_DTYPE_*
 // (hipErrorInvalidValue for another dtype): fp32 arithmetic from the load on, pairs and log-probs in fp32, d/d logits in
 // the logits' type.  Plain log-softmax, fused gather into the diagonal-major pair plane, fused d/d logits:
 hipError_t launch_log_softmax(hipStream_t stream, int dtype, const void* x, float* out, int64_t rows, int V);
+// the same, and col_out[row] = out[row*V + col] (the same float) as a contiguous plane of `rows` floats
+hipError_t launch_log_softmax_plane(hipStream_t stream, int dtype, const void* x, float* out, float* col_out, int64_t rows,
+                                    int V, int col);
 hipError_t launch_log_softmax_gather_skewed(hipStream_t stream, int dtype, const void* logits, const int* labels,
                                             float* ws2, int N, int T, int U, int V, int blank);
 hipError_t launch_logits_backward(hipStream_t stream, int dtype, const void* logits, const int* labels,

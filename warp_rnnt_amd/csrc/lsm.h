@@ -196,6 +196,11 @@ struct LsmBwd {
     const float2* g2;    // diagonal-major gathered gradients (RNNT_GRADS_GATHERED_DIAGONAL)
     const float* scale;  // (N,) upstream gradient per utterance, or nullptr
     int xcd;             // row-per-workgroup kernel: 1 = every XCD streams a contiguous eighth of the rows
+    // LSM_NORM only: the column plane.  col_out[row] receives the float that goes into out[row*V + col] -- the blank
+    // log-prob of every lattice cell, which the dense gather behind this kernel then reads as a coalesced stream instead of
+    // fetching a 128-byte line of the row for it (to_diagonal.hip).  nullptr: no plane.
+    float* col_out;
+    int col;
 };
 
 constexpr int SM_THREADS = 256;
@@ -358,9 +363,14 @@ constexpr int RG_UN = 2;   // groups per half and wave, loads first (1: 500 us, 
 
 // NT: bit 0 = non-temporal loads, bit 1 = non-temporal stores (both: 462 us for the c4 tensor, neither: 484); the launch
 // passes 3, and the stores leave through the strip written through and streaming
-template <typename E, int KR, int NT>
+// PLANE: the column plane (LsmBwd::col_out) on top -- the wave's 4 * KR rows lie in its strip in address order, so lane l
+// picks element `col` of row l out of the strip and the wave's slice of the plane leaves as one store of 4 * KR
+// consecutive floats (a workgroup's four waves: 16 * KR consecutive floats, whole lines from KR = 2 on); plain stores, for L2
+// to put the pieces together.  Three vector instructions, one LDS read and one store per wave on top of ~311.
+template <typename E, int KR, int NT, bool PLANE>
 __global__ void __launch_bounds__(256) k_lsm_regs(const E* __restrict__ x, float* __restrict__ out,
-                                                  const int64_t ngroups, const int V, const int xcd) {
+                                                  const int64_t ngroups, const int V, const int xcd,
+                                                  float* __restrict__ col_out, const int col) {
     const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
     const int g4 = (KR * V) >> 2;                  // float4 per group
     const bool act = j < g4;
@@ -432,6 +442,13 @@ __global__ void __launch_bounds__(256) k_lsm_regs(const E* __restrict__ x, float
     // the wave's 2 * RG_UN groups are 64 * g4 contiguous bytes: out of the strip in address order, one store instruction of
     // 1024 bytes and one of the rest -- every instruction whole 64-byte granules (the strip is the wave's own: no barrier)
     wave_sync_lds();
+    if constexpr (PLANE) {
+        const int64_t wu = (int64_t)wg * 4 + __builtin_amdgcn_readfirstlane(wv);      // w, known to be wave-uniform
+        const int64_t r0w = wu * (2 * RG_UN * KR);                                   // the wave's first row
+        const int nr = (int)min((int64_t)(2 * RG_UN * KR), ngroups * KR - r0w);     // its rows inside the tensor (<= 0: none)
+        const float* srow = reinterpret_cast<const float*>(strip[__builtin_amdgcn_readfirstlane(wv)]);
+        if (lane < nr) col_out[r0w + lane] = srow[__mul24(lane, V) + col];      // (lane < 64, V <= 128)
+    }
     const int64_t f0 = w * (2 * RG_UN) * g4, nf = ngroups * g4;
     const int nw = 2 * RG_UN * g4;                  // float4 of this wave (<= 64 * RG_UN)
 #pragma unroll
@@ -672,12 +689,18 @@ static hipError_t dispatch_lsm_map(hipStream_t stream, const E* x, LsmOut<MODE, 
             if (regs_xcd) grid = (grid + 7) / 8 * 8;
             if (grid < ((int64_t)1 << 31)) {
 #define LSM_REGS(KR) \
-    case KR: k_lsm_regs<E, KR, 3><<<(unsigned)grid, 256, 0, stream>>>(x, out, ngroups, V, regs_xcd); break;
+    case KR:                                                                                                   \
+        if (bw.col_out)                                                                                        \
+            k_lsm_regs<E, KR, 3, true><<<(unsigned)grid, 256, 0, stream>>>(x, out, ngroups, V, regs_xcd, bw.col_out, bw.col); \
+        else                                                                                                   \
+            k_lsm_regs<E, KR, 3, false><<<(unsigned)grid, 256, 0, stream>>>(x, out, ngroups, V, regs_xcd, nullptr, 0); \
+        break;
                 switch (kr) { LSM_REGS(1) LSM_REGS(2) LSM_REGS(3) LSM_REGS(4) }
 #undef LSM_REGS
                 const hipError_t e = hipGetLastError();
                 const int64_t done = ngroups * kr;              // (a group boundary: vector aligned)
                 if (e != hipSuccess || done == rows) return e;
+                if (bw.col_out) bw.col_out += done;             // (the rows left over: the LDS-staged kernel, and its plane)
                 return dispatch_lsm_map<MODE, E>(stream, x + done * V, out + done * V, map, rows - done, V, blank, bw);
             }
         }
@@ -862,10 +885,12 @@ static hipError_t dispatch_lsm_compact(hipStream_t stream, const E* x, LsmOut<MO
     return dispatch_lsm_map<MODE, E>(stream, x, out, CompactMap<MODE == LSM_GATHER>{cr, 0, 0}, cr.rows, V, blank, bw);
 }
 
-// The five operations of kernels.h at one storage type: each lsm_<type>.hip instantiates them, and through them the kernels
+// The operations of kernels.h at one storage type: each lsm_<type>.hip instantiates them, and through them the kernels
 // above, for its own E.  (Members defined outside the class: `extern template` does not hold back an inline member.)
 template <typename E> struct LsmOps {
     static hipError_t log_softmax(hipStream_t stream, const E* x, float* out, int64_t rows, int V);
+    static hipError_t log_softmax_plane(hipStream_t stream, const E* x, float* out, int64_t rows, int V, float* col_out,
+                                        int col);
     static hipError_t gather(hipStream_t stream, const E* logits, const int* labels, float* ws2, int N, int T, int U, int V,
                              int blank);
     static hipError_t backward(hipStream_t stream, const E* logits, const int* labels, const float* g2_diagonal,
@@ -877,6 +902,11 @@ template <typename E> struct LsmOps {
 template <typename E>
 hipError_t LsmOps<E>::log_softmax(hipStream_t stream, const E* x, float* out, int64_t rows, int V) {
     return dispatch_lsm<LSM_NORM, E>(stream, x, out, nullptr, rows, V, 1, 1, 0, LsmBwd{nullptr, nullptr});
+}
+template <typename E>
+hipError_t LsmOps<E>::log_softmax_plane(hipStream_t stream, const E* x, float* out, int64_t rows, int V, float* col_out,
+                                        int col) {
+    return dispatch_lsm<LSM_NORM, E>(stream, x, out, nullptr, rows, V, 1, 1, 0, LsmBwd{nullptr, nullptr, 0, col_out, col});
 }
 template <typename E>
 hipError_t LsmOps<E>::gather(hipStream_t stream, const E* logits, const int* labels, float* ws2, int N, int T, int U, int V,

@@ -33,5 +33,9 @@
         }
     } else {
         float* o = out + row * V;
-        for (int c = lane; c < V; c += WAVE) o[c] = (lsm_ld1(xr + c) - mx) - ls;
+        for (int c = lane; c < V; c += WAVE) {
+            const float r = (lsm_ld1(xr + c) - mx) - ls;
+            o[c] = r;
+            if (bw.col_out && c == bw.col) bw.col_out[row] = r;      // the column plane (LsmBwd::col_out)
+        }
     }

@@ -112,6 +112,12 @@
                 const float4 r = make_float4((v[i].x - mx) - ls, (v[i].y - mx) - ls, (v[i].z - mx) - ls,
                                              (v[i].w - mx) - ls);
                 lsm_st4<true>(dst, j, r);
+                // the column plane (LsmBwd::col_out): the one lane that holds the column stores it (a row per workgroup:
+                // 4 bytes beside 4V)
+                if (bw.col_out && j == (bw.col >> 2)) {
+                    const int c = bw.col & 3;
+                    bw.col_out[row] = c == 0 ? r.x : (c == 1 ? r.y : (c == 2 ? r.z : r.w));
+                }
             }
         }
     }

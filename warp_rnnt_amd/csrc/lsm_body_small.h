@@ -178,6 +178,11 @@
         }
     } else if constexpr (WP) {
         wave_sync_lds();
+        // the column plane (LsmBwd::col_out): the wave's rows are consecutive, so is its slice of the plane
+        if constexpr (MODE == LSM_NORM) {
+            if (bw.col_out)
+                for (int r = lane; r < wn; r += WAVE) bw.col_out[row0 + wr0 + r] = wtile[r * V + bw.col];
+        }
         LsmOut<MODE, E>* wdst = out + (row0 + wr0) * V;
         if constexpr (std::is_same_v<E, float>) {
             for (int i = lane; i < wvec; i += WAVE)
@@ -190,6 +195,10 @@
         }
     } else {
         __syncthreads();
+        if constexpr (MODE == LSM_NORM) {      // the column plane: one contiguous run per workgroup
+            if (bw.col_out)
+                for (int r = tid; r < nrows; r += SM_THREADS) bw.col_out[row0 + r] = tile[r * V + bw.col];
+        }
         LsmOut<MODE, E>* dst = out + row0 * V;
         if constexpr (std::is_same_v<E, float>) {
             for (int i = tid; i < nvec; i += SM_THREADS)

@@ -1,4 +1,4 @@
-// The forward log-softmax kernels of lsm.h for fp32 logits, and the family's five launchers (kernels.h).
+// The forward log-softmax kernels of lsm.h for fp32 logits, and the family's launchers (kernels.h).
 #include "lsm.h"
 #include "../../include/warp_rnnt_amd.h"
 
@@ -19,6 +19,14 @@ hipError_t launch_log_softmax(hipStream_t stream, int dtype, const void* x, floa
     return with_logits_type(dtype, [&](auto* e) {
         using E = std::remove_pointer_t<decltype(e)>;
         return LsmOps<E>::log_softmax(stream, static_cast<const E*>(x), out, rows, V);
+    });
+}
+
+hipError_t launch_log_softmax_plane(hipStream_t stream, int dtype, const void* x, float* out, float* col_out, int64_t rows,
+                                    int V, int col) {
+    return with_logits_type(dtype, [&](auto* e) {
+        using E = std::remove_pointer_t<decltype(e)>;
+        return LsmOps<E>::log_softmax_plane(stream, static_cast<const E*>(x), out, rows, V, col_out, col);
     });
 }
 

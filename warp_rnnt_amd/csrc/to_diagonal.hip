@@ -45,10 +45,17 @@ __device__ __forceinline__ void fold_ring_prepare(const RingPrep& p) {
     }
 }
 
-template <bool DENSE, int TTK>
+// PLANE (dense only): the blank log-prob of every cell comes from a contiguous (N,T,U) plane that the log-softmax in front
+// wrote beside its rows (lsm.h: LsmBwd::col_out) -- a coalesced 4-byte load along u -- and only the label's dword is fetched
+// from the row.  For rows longer than a line the two dwords touch 10.0 M of c4's 11.25 M lines, the label's alone 7.2 M
+// (DESIGN.md 3.5): 0.36 GB of reads less for 28.8 MB more.  Same policy otherwise: non-temporal row loads, tiles from
+// the end, pairs written through.
+template <bool DENSE, int TTK, bool PLANE>
 __global__ void __launch_bounds__(256)
 k_to_diagonal(const float* __restrict__ src, const int* __restrict__ labels, float2* __restrict__ ws2,
-              int T, int U, int V, int blank, int tiles_t, int tiles_u, const RingPrep prep) {
+              int T, int U, int V, int blank, int tiles_t, int tiles_u, const RingPrep prep,
+              const float* __restrict__ blank_plane) {
+    static_assert(DENSE || !PLANE, "the blank plane belongs to the dense gather");
     __shared__ float2 tile[TTK][TD];
     unsigned b = DENSE ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
     const int tu = b % tiles_u; b /= tiles_u;
@@ -71,7 +78,10 @@ k_to_diagonal(const float* __restrict__ src, const int* __restrict__ labels, flo
                 // so this kernel streams ~1.4 lines per cell and none of them is touched again: non-temporal loads
                 // (206 vs 227 us for the probe, 205-229 vs 227-255 us here, box to box).
                 const float* p = src + cell * (size_t)V;
-                tile[tl][ul] = make_float2(__builtin_nontemporal_load(p + blank), __builtin_nontemporal_load(p + lab));
+                if constexpr (PLANE)
+                    tile[tl][ul] = make_float2(blank_plane[cell], __builtin_nontemporal_load(p + lab));
+                else
+                    tile[tl][ul] = make_float2(__builtin_nontemporal_load(p + blank), __builtin_nontemporal_load(p + lab));
             } else {
                 tile[tl][ul] = reinterpret_cast<const float2*>(src)[cell];
             }
@@ -115,21 +125,26 @@ k_gather_rowmajor(const float* __restrict__ lp, const int* __restrict__ labels, 
 
 template <int TTK>
 static hipError_t launch_to_diagonal_tt(hipStream_t stream, const float* src, const int* labels, float* ws2,
-                                        int N, int T, int U, int V, int blank, bool dense, const RingPrep& prep) {
+                                        int N, int T, int U, int V, int blank, bool dense, const RingPrep& prep,
+                                        const float* blank_plane) {
     const int tiles_t = (T + TTK - 1) / TTK, tiles_u = (U + TD - 1) / TD;
     const size_t nblk = (size_t)N * tiles_t * tiles_u;
     if (nblk >= ((size_t)1 << 31)) return hipErrorInvalidValue;
-    if (dense)
-        k_to_diagonal<true, TTK><<<(unsigned)nblk, 256, 0, stream>>>(src, labels, reinterpret_cast<float2*>(ws2), T, U,
-                                                                     V, blank, tiles_t, tiles_u, prep);
+    if (dense && blank_plane)
+        k_to_diagonal<true, TTK, true><<<(unsigned)nblk, 256, 0, stream>>>(src, labels, reinterpret_cast<float2*>(ws2), T,
+                                                                           U, V, blank, tiles_t, tiles_u, prep, blank_plane);
+    else if (dense)
+        k_to_diagonal<true, TTK, false><<<(unsigned)nblk, 256, 0, stream>>>(src, labels, reinterpret_cast<float2*>(ws2), T,
+                                                                            U, V, blank, tiles_t, tiles_u, prep, nullptr);
     else
-        k_to_diagonal<false, TTK><<<(unsigned)nblk, 256, 0, stream>>>(src, labels, reinterpret_cast<float2*>(ws2), T, U,
-                                                                      2, 0, tiles_t, tiles_u, prep);
+        k_to_diagonal<false, TTK, false><<<(unsigned)nblk, 256, 0, stream>>>(src, labels, reinterpret_cast<float2*>(ws2), T,
+                                                                             U, 2, 0, tiles_t, tiles_u, prep, nullptr);
     return hipGetLastError();
 }
 
 static hipError_t launch_to_diagonal(hipStream_t stream, const float* src, const int* labels, float* ws2,
-                                     int N, int T, int U, int V, int blank, bool dense, const RingPrep* prep_in) {
+                                     int N, int T, int U, int V, int blank, bool dense, const RingPrep* prep_in,
+                                     const float* blank_plane = nullptr) {
     const RingPrep prep = prep_in ? *prep_in : RingPrep{nullptr, 0, nullptr, nullptr, 0};
     if ((size_t)N * T * U == 0) return hipSuccess;
     // Small problems: 32-frame tiles do not even give every CU one workgroup (c2: 94 tiles for 256 CUs); 8-frame tiles --
@@ -138,8 +153,8 @@ static hipError_t launch_to_diagonal(hipStream_t stream, const float* src, const
     const size_t tiles32 = (size_t)N * ((T + TT - 1) / TT) * ((U + TD - 1) / TD);
     // (dense entry, us per call, 32- / 8-frame tiles: c2 28.1 / 27.4, N=32 35.1 / 33.2, N=64 46.2 / 45.2, N=128 67.1 / 68.1)
     const bool small_tiles = force >= 0 ? force != 0 : tiles32 < 512;
-    if (small_tiles) return launch_to_diagonal_tt<8>(stream, src, labels, ws2, N, T, U, V, blank, dense, prep);
-    return launch_to_diagonal_tt<TT>(stream, src, labels, ws2, N, T, U, V, blank, dense, prep);
+    if (small_tiles) return launch_to_diagonal_tt<8>(stream, src, labels, ws2, N, T, U, V, blank, dense, prep, blank_plane);
+    return launch_to_diagonal_tt<TT>(stream, src, labels, ws2, N, T, U, V, blank, dense, prep, blank_plane);
 }
 
 // (Round 5 tried the dense gather as a coalesced STREAM for V <= 64, where the two dwords per row touch nearly every
@@ -147,10 +162,11 @@ static hipError_t launch_to_diagonal(hipStream_t stream, const float* src, const
 //  Bit-identical, and slower: c4 274 us against 250 for k_to_diagonal in the same runs, loss path 0.403 vs 0.384 ms
 //  -- a stream pays for all 1.44 GB, the scattered requests for the ~0.9 of the lines they touch.)
 hipError_t launch_gather(hipStream_t stream, const float* log_probs, const int* labels, float* out2,
-                         int N, int T, int U, int V, int blank, bool skewed, const RingPrep* prep) {
+                         int N, int T, int U, int V, int blank, bool skewed, const RingPrep* prep,
+                         const float* blank_plane) {
     const size_t cells = (size_t)N * T * U;
     if (cells == 0) return hipSuccess;
-    if (skewed) return launch_to_diagonal(stream, log_probs, labels, out2, N, T, U, V, blank, true, prep);
+    if (skewed) return launch_to_diagonal(stream, log_probs, labels, out2, N, T, U, V, blank, true, prep, blank_plane);
     k_gather_rowmajor<<<(unsigned)((cells + 255) / 256), 256, 0, stream>>>(
         log_probs, labels, reinterpret_cast<float2*>(out2), cells, T, U, V, blank);
     return hipGetLastError();

@@ -41,6 +41,13 @@ def last_lattice_kernel():
     return LATTICE_KERNELS[load().rnnt_amd_debug_last_lattice_kernel()]
 
 
+def last_loss_used_blank_plane():
+    """Did this process's last loss call on dense log-probs read the blank column from the plane that
+    ``ops.log_softmax`` left beside them (``ops.blank_plane_of``)?  Host-side bookkeeping only: nothing is read back."""
+    from . import ops
+    return ops._LAST_LOSS_PLANE
+
+
 LatticePlan = collections.namedtuple("LatticePlan", "kernel block_diagonals rings")
 LOADERS = ("skewed", "rowmajor", "dense")
 

@@ -42,6 +42,67 @@ def _workspace(dev, size_fn, names, *dims):
     return torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
 
 
+# ---- the blank column as a plane of its own ----
+# log_softmax writes, beside the (N,T,U,V) log-probs, their column 0 -- the blank of every lattice cell -- as a contiguous
+# (N*T*U,) plane and leaves a note on the tensor object it returns; a dense loss call that is handed that very object,
+# unchanged, passes the plane on and its gather fetches one dword per row instead of two.  The note:
+#   (plane, out._version, column, out.data_ptr())
+PLANE_ATTR = "_rnnt_blank_plane"
+PLANE_COLUMN = 0             # the column log_softmax keeps: the default blank
+# Cells from which the plane is produced (DESIGN.md 3.5 has the numbers).  What it costs is fixed -- one more allocation
+# and a second native argument, 3-5 us of host time per step -- and what it saves is one 128-byte line per cell at most,
+# ~25 us per million cells at the gather's rate: from 2^20 cells on the saving is five times the cost.  Below it the step
+# is launch-bound and gains nothing (c3, 96 k cells: within its spread either way).
+PLANE_MIN_CELLS = 1 << 20
+
+
+def wants_blank_plane(cells, V):
+    """The one decision when log_softmax produces the plane -- a pure function of the shape (cells = N*T*U).  Never for
+    rows that fit one 128-byte line (4V <= 128: blank and label share lines, nothing is saved), never below
+    PLANE_MIN_CELLS (the extra store and the host cost would show on launch-bound steps)."""
+    return 4 * V > 128 and cells >= PLANE_MIN_CELLS
+
+
+def plane_note_valid(note, version, data_ptr, shape, dtype, contiguous, blank):
+    """Does ``note`` (the PLANE_ATTR of a tensor) describe the tensor with these facts, for a loss with this blank?
+    Pure: no tensor is touched."""
+    if not (isinstance(note, tuple) and len(note) == 4):
+        return False
+    plane, note_version, column, note_ptr = note
+    if note_version != version or note_ptr != data_ptr or column != blank:
+        return False
+    if len(shape) != 4 or dtype != torch.float32 or not contiguous:
+        return False
+    return plane is not None and plane.numel() == shape[0] * shape[1] * shape[2]
+
+
+def blank_plane_of(log_probs, blank):
+    """The blank plane that belongs to ``log_probs`` as it is now, or None: the note must sit on this very object (a view,
+    a clone, a detach() carry none), and neither the tensor's version counter nor its storage may have moved."""
+    note = getattr(log_probs, PLANE_ATTR, None)
+    if note is None:
+        return None
+    if plane_note_valid(note, log_probs._version, log_probs.data_ptr(), tuple(log_probs.shape), log_probs.dtype,
+                        log_probs.is_contiguous(), blank):
+        return note[0]
+    return None
+
+
+def _drop_plane(t):
+    """Before anything is enqueued that writes into ``t`` through its raw pointer: such a write does not move
+    ``t._version``, so a note left on ``t`` would describe values that are gone."""
+    if t is not None and getattr(t, PLANE_ATTR, None) is not None:
+        delattr(t, PLANE_ATTR)
+
+
+_LAST_LOSS_PLANE = False     # debug.last_loss_used_blank_plane(): did the last dense loss call of this process take a plane?
+
+
+def _note_loss_plane(used):
+    global _LAST_LOSS_PLANE
+    _LAST_LOSS_PLANE = bool(used)
+
+
 def _mismatch_policy():
     """WARP_RNNT_AMD_CHECK_MISMATCH = warn | raise: read the guard flags back after every loss call
     (one host synchronisation: exact and immediate).  Unset (default): no read-back; the counterpart of the
@@ -50,8 +111,12 @@ def _mismatch_policy():
     return os.environ.get("WARP_RNNT_AMD_CHECK_MISMATCH", "").lower()
 
 
-def loss(input, labels, xn, yn, input_kind, grads_kind, blank=0, fastemit_lambda=0.0, return_mismatch=False):
+def loss(input, labels, xn, yn, input_kind, grads_kind, blank=0, fastemit_lambda=0.0, return_mismatch=False,
+         use_blank_plane=True):
     """costs (N,), grads (layout per grads_kind; None for GRADS_NONE) [, mismatch (N,) int32].
+    Dense log-probs that came out of :func:`log_softmax` with their blank plane (and are still what they were:
+    :func:`blank_plane_of`) are served through it -- same bits, one line less read per cell; ``use_blank_plane=False``
+    never looks for one.
     Tensors must be validated by the caller (contiguous, fp32/int32, same GPU; IN_LOGITS_DENSE also takes bf16 / fp16
     logits -- costs and gradient pairs stay fp32).  ``mismatch[n]`` is 1
     where the forward/backward consistency guard zeroed an utterance's gradients (or its lengths were
@@ -79,7 +144,14 @@ def loss(input, labels, xn, yn, input_kind, grads_kind, blank=0, fastemit_lambda
             return costs, grads
         ws = _workspace(dev, L.rnnt_amd_workspace_size, "N T U", N, T, U)
         _mismatch.poll(dev)          # (what an EARLIER call's kernels reported; sets the device's words up at first use)
-        if input_kind == IN_LOGITS_DENSE and _half(input):
+        plane = blank_plane_of(input, blank) if (use_blank_plane and input_kind == IN_LOG_PROBS_DENSE) else None
+        if input_kind == IN_LOG_PROBS_DENSE:
+            _note_loss_plane(plane is not None)
+        if plane is not None:
+            st = L.rnnt_amd_loss_blank_plane(_stream(dev), ws.data_ptr(), input.data_ptr(), plane.data_ptr(),
+                                             _ptr(labels), xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(grads),
+                                             grads_kind, N, T, U, V, blank, float(fastemit_lambda))
+        elif input_kind == IN_LOGITS_DENSE and _half(input):
             st = L.rnnt_amd_loss_logits(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[input.dtype], input.data_ptr(),
                                         _ptr(labels), xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(grads),
                                         grads_kind, N, T, U, V, blank, float(fastemit_lambda))
@@ -138,27 +210,44 @@ def _native_binding():
 _NATIVE = False
 
 
-def log_softmax(x, out=None):
+def log_softmax(x, out=None, blank_plane=None):
     """Row-wise log-softmax over the last axis (contiguous, GPU). ``out`` may be ``x``.  fp32 in, fp32 out; bf16 / fp16
-    in, fp32 out (bit-equal to the fp32 call on ``x.float()``; ``out`` must then be a separate fp32 tensor)."""
+    in, fp32 out (bit-equal to the fp32 call on ``x.float()``; ``out`` must then be a separate fp32 tensor).
+    For fp32 (N,T,U,V) input the kernel can keep column 0 of the result as a plane beside it, for the loss to read
+    (PLANE_ATTR above): ``blank_plane=None`` where :func:`wants_blank_plane` says so, ``True`` / ``False`` always / never
+    (tests, timing runs).  The returned tensor is the same either way."""
+    _drop_plane(out)
     if _half(x):
         return _log_softmax_half(x, out)
+    planed = x.dim() == 4 and x.numel() > 0 and (
+        wants_blank_plane(x.shape[0] * x.shape[1] * x.shape[2], x.shape[3]) if blank_plane is None else bool(blank_plane))
     nb = _native_binding()
     if nb is not None:
-        return nb.log_softmax(x, out)
-    L = _lib.load()
-    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
-    if out is None:
-        out = torch.empty_like(x)
-    V = x.shape[-1]
-    rows = x.numel() // max(V, 1)
-    with torch.cuda.device(x.device):
-        _check(L.rnnt_amd_log_softmax(_stream(x.device), x.data_ptr(), out.data_ptr(), rows, V))
+        if not planed:
+            return nb.log_softmax(x, out)
+        res, plane = nb.log_softmax_plane(x, out, PLANE_COLUMN)
+        out = res if out is None else out
+    else:
+        L = _lib.load()
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        if out is None:
+            out = torch.empty_like(x)
+        V = x.shape[-1]
+        rows = x.numel() // max(V, 1)
+        with torch.cuda.device(x.device):
+            if not planed:
+                _check(L.rnnt_amd_log_softmax(_stream(x.device), x.data_ptr(), out.data_ptr(), rows, V))
+                return out
+            plane = torch.empty((rows,), dtype=torch.float32, device=x.device)
+            _check(L.rnnt_amd_log_softmax_plane(_stream(x.device), x.data_ptr(), out.data_ptr(), plane.data_ptr(), rows,
+                                                V, PLANE_COLUMN))
+    setattr(out, PLANE_ATTR, (plane, out._version, PLANE_COLUMN, out.data_ptr()))
     return out
 
 
 def _log_softmax_half(x, out=None):
     L = _lib.load()
+    _drop_plane(out)
     if not (x.is_cuda and x.is_contiguous()):
         raise RuntimeError("log_softmax: x must be a contiguous tensor on the GPU")
     if out is None:
@@ -304,6 +393,7 @@ def compact_logits_backward(logits, ys, xn, yn, cell_offsets, label_offsets, gra
             out = torch.empty_like(logits)
         if out.dtype != logits.dtype or out.shape != logits.shape or not out.is_contiguous():
             raise RuntimeError("compact_logits_backward: out must be a contiguous tensor like the logits")
+        _drop_plane(out)
         if STU == 0:
             return out
         _check(L.rnnt_amd_compact_logits_backward(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
@@ -338,6 +428,7 @@ def logits_backward(logits, labels, grads_diagonal, grad_costs, blank=0, out=Non
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty_like(logits)
+        _drop_plane(out)
         if N == 0:
             return out
         if _half(logits):
@@ -360,6 +451,7 @@ def log_softmax_backward(grad_out, out, grad_in=None):
     assert out.is_contiguous() and out.shape == grad_out.shape and out.dtype == torch.float32
     if grad_in is None:
         grad_in = torch.empty_like(grad_out)
+    _drop_plane(grad_in)
     V = out.shape[-1]
     rows = out.numel() // max(V, 1)
     with torch.cuda.device(out.device):
