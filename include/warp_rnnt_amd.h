@@ -420,6 +420,28 @@ int rnnt_amd_debug_last_lattice_kernel(void);
  * redo kernel behind it), 0 otherwise -- or -1 for N <= 0, T < 1, U < 1 or an unknown pin. */
 int rnnt_amd_debug_lattice_plan(int N, int T, int U, int loader, int resources, int cus, int pin, int folded);
 
+/* Diagnostics (version 109, additive): which forward log-softmax kernel a call with these facts WOULD run, and in which
+ * shape -- the library's own planner (csrc/lsm_plan.h) under the process's knobs, answered on the host: no launch, no device.
+ *   mode      0 plain log-softmax, 1 fused gather, 2 fused d/d logits, 3 rnnt_amd_log_softmax_backward (fp32; dtype, T, U,
+ *             compact and plane are not looked at)
+ *   dtype     RNNT_DTYPE_* of the logits
+ *   T, U      the dense lattice of modes 1 and 2 (rows = N*T*U); compact != 0: the compact (packed) layout instead
+ *   aligned   the tensors start on a four-element vector (16 bytes of fp32, 8 of half)
+ *   plane     mode 0: the column plane is written too (rnnt_amd_log_softmax_plane)
+ * out[0 ... n_out) receives the first n_out of 16 fields (a family leaves 0 what it does not use):
+ *    0 family   0 rows in registers (k_lsm_regs), 1 a row per small workgroup (k_lsm_large, 128 < V <= 1024), 2 L lanes per
+ *               row (k_lsm_rows), 3 the same along the diagonals (k_lsm_rows_diag), 4 LDS tiles (k_lsm_small), 5 a row per
+ *               workgroup (k_lsm_large), 6 generic
+ *    1 KR       rows per register group          2 L    lanes per row             3 Q    float4 per lane (families 2, 3)
+ *    4 WP       wave-private tiles               5 TH   threads ...               6 NV   ... x float4 per thread (1, 5)
+ *    7, 8, 9    grid x, y, z                    10 lds  dynamic LDS bytes        11 R    rows per tile
+ *   12 q        columns per lane (family 4)     13 xcd  every XCD streams a contiguous eighth
+ *   14 head_rows  family 0: the rows the register kernel takes (at most INT_MAX is reported)
+ *   15 tail     the family that serves the rows left over behind the register kernel, -1: none left
+ * Returns the family, or -1 for an unknown mode or dtype, rows < 0 or V < 1. */
+int rnnt_amd_debug_lsm_plan(int mode, int dtype, int64_t rows, int V, int T, int U, int compact, int aligned, int plane,
+                            int *out, int n_out);
+
 /*
  * The blank column as a plane of its own (version 108, additive).  A log-softmax that writes, beside its rows, the one
  * column the loss reads from EVERY row -- col_out[row] = out[row*V + col], the same float, `rows` contiguous floats -- and

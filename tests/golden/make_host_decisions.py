@@ -49,6 +49,7 @@ BAD_COMPACT_DIMS = [dict(N=-1), dict(N=65536), dict(STU=-1), dict(STU=1 << 32), 
                     dict(N=16, Tmax=1 << 14, Umax=1 << 14)]
 BAD_WORKSPACE = [dict(workspace=0), dict(workspace=P + 8)]
 BAD_DTYPE = [dict(dtype=-1), dict(dtype=3)]
+BAD_PLANE = [dict(rows=-1), dict(V=0), dict(col=-1), dict(col=7), dict(col_out=0)]
 
 
 def bad_vocab(V):
@@ -171,6 +172,20 @@ ENTRIES = {
         "stream workspace log_probs labels N T U V blank",
         dict(stream=0, workspace=P, log_probs=P, labels=P, V=7, blank=0, **DIMS),
         BAD_DIMS + [dict(workspace=0)] + bad_vocab(7) + [dict(labels=0)], []),
+    # the blank column as a plane of its own: what tests/test_host_blank_plane.py asks of these entries, one row each
+    "rnnt_amd_log_softmax_plane": entry("stream x out col_out rows V col",
+                                        dict(stream=0, x=P, out=P, col_out=P, rows=4, V=7, col=0), BAD_PLANE, []),
+    "rnnt_amd_log_softmax_plane_typed": entry(
+        "stream dtype x out col_out rows V col", dict(stream=0, dtype=1, x=P, out=P, col_out=P, rows=4, V=7, col=0),
+        BAD_DTYPE + [dict(bad, dtype=d) for bad in BAD_PLANE for d in DTYPES], []),
+    "rnnt_amd_loss_blank_plane": entry(
+        "stream workspace log_probs blank_plane labels xn yn costs grads grads_kind N T U V blank fastemit_lambda",
+        dict(LOSS, log_probs=P, blank_plane=P),
+        [dict(blank_plane=0)] + BAD_DIMS[:4] + BAD_WORKSPACE + bad_vocab(7) + [dict(labels=0)] + BAD_GRADS[:3], [dict(N=0)]),
+    "rnnt_amd_debug_gather_only_blank_plane": entry(
+        "stream workspace log_probs blank_plane labels N T U V blank",
+        dict(stream=0, workspace=P, log_probs=P, blank_plane=P, labels=P, V=7, blank=0, **DIMS),
+        [dict(blank_plane=0), dict(workspace=0), dict(N=-1), dict(T=0), dict(V=0), dict(blank=7), dict(labels=0)], []),
 }
 
 

@@ -25,7 +25,7 @@ def test_sizes_offsets_and_launch_free_answers_are_the_recorded_ones():
     entries = {fn for fn, (res, _) in _lib.SYMBOLS.items() if res is _lib._i and fn.startswith(("rnnt_amd_", "run_warp"))}
     no_rows = {"rnnt_amd_version", "rnnt_amd_compact_last_status", "rnnt_amd_debug_set_lattice_kernel",
                "rnnt_amd_debug_get_lattice_kernel", "rnnt_amd_debug_last_lattice_kernel",
-               "rnnt_amd_debug_lattice_plan"}     # (no status, or no arguments)
+               "rnnt_amd_debug_lattice_plan", "rnnt_amd_debug_lsm_plan"}     # (no status, or no arguments)
     assert {row[0] for row in table["calls"]} == entries - no_rows
     assert {row[0] for row in table["sizes"]} == {fn for fn, (res, _) in _lib.SYMBOLS.items() if res is _lib._sz}
     wrong = [(fn, args, want, getattr(L, fn)(*args)) for fn, args, want in table["sizes"]

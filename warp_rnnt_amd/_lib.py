@@ -30,12 +30,6 @@ ACT_TANH, ACT_RELU = 0, 1
 _vp, _i, _f, _sz, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
 
 
-class _st(ctypes.c_int):
-    """rnntStatus_t of the entries added to version 108 after tests/golden/host_decisions.json was recorded: that table is
-    the closed set of the `_i` entries; the launch-free answers of these are in tests/test_host_blank_plane.py.  load()
-    turns the returned object into the plain int every other entry returns."""
-
-
 SYMBOLS = {
     "run_warp_rnnt": (_i, [_vp] * 10 + [_i] * 5 + [_f]),
     "run_warp_rnnt_gather": (_i, [_vp] * 9 + [_i] * 3 + [_f]),
@@ -74,16 +68,17 @@ SYMBOLS = {
     "rnnt_amd_mismatch_flag": (ctypes.POINTER(ctypes.c_uint), [_i]),
     "rnnt_amd_debug_last_lattice_kernel": (_i, []),
     "rnnt_amd_debug_lattice_plan": (_i, [_i] * 8),
+    "rnnt_amd_debug_lsm_plan": (_i, [_i, _i, _i64] + [_i] * 6 + [ctypes.POINTER(_i), _i]),
     "rnnt_amd_version": (_i, []),
     # the blank column as a plane of its own (version 108, additive)
-    "rnnt_amd_log_softmax_plane": (_st, [_vp, _vp, _vp, _vp, _i64, _i, _i]),
-    "rnnt_amd_log_softmax_plane_typed": (_st, [_vp, _i, _vp, _vp, _vp, _i64, _i, _i]),
-    "rnnt_amd_loss_blank_plane": (_st, [_vp] * 9 + [_i] * 6 + [_f]),
-    "rnnt_amd_debug_gather_only_blank_plane": (_st, [_vp] * 5 + [_i] * 5),
+    "rnnt_amd_log_softmax_plane": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i]),
+    "rnnt_amd_log_softmax_plane_typed": (_i, [_vp, _i, _vp, _vp, _vp, _i64, _i, _i]),
+    "rnnt_amd_loss_blank_plane": (_i, [_vp] * 9 + [_i] * 6 + [_f]),
+    "rnnt_amd_debug_gather_only_blank_plane": (_i, [_vp] * 5 + [_i] * 5),
 }
 
 
-ABI_VERSION = 108   # rnnt_amd_version() of the library these argument lists belong to
+ABI_VERSION = 109   # rnnt_amd_version() of the library these argument lists belong to
 
 
 class RNNTStatusError(RuntimeError):
@@ -112,8 +107,6 @@ def load():
         fn = getattr(L, name)   # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
-        if res is _st:
-            fn.errcheck = lambda result, func, arguments: result.value
     # the argument lists above are this version's: an older build of the library (a stale prebuilt .so, a
     # WARP_RNNT_AMD_LIB variant built from older sources) would accept the calls and misread them
     if L.rnnt_amd_version() != ABI_VERSION:

@@ -119,7 +119,7 @@ rnntStatus_t grads_in_place_then_split(rnntStream_t stream, float* grads, const 
 
 extern "C" {
 
-int rnnt_amd_version(void) { return 108; }
+int rnnt_amd_version(void) { return 109; }
 
 int rnnt_amd_debug_set_lattice_kernel(int kernel) { return set_lattice_kernel_override(kernel); }
 
@@ -129,6 +129,11 @@ int rnnt_amd_debug_last_lattice_kernel(void) { return last_lattice_kernel(); }
 
 int rnnt_amd_debug_lattice_plan(int N, int T, int U, int loader, int resources, int cus, int pin, int folded) {
     return debug_lattice_plan(N, T, U, loader, resources, cus, pin, folded);
+}
+
+int rnnt_amd_debug_lsm_plan(int mode, int dtype, int64_t rows, int V, int T, int U, int compact, int aligned, int plane,
+                            int* out, int n_out) {
+    return debug_lsm_plan(mode, dtype, rows, V, T, U, compact, aligned, plane, out, n_out);
 }
 
 volatile unsigned* rnnt_amd_mismatch_flag(int device) { return mismatch_words(device, true); }

@@ -159,7 +159,8 @@ hipError_t launch_joint_bwd(hipStream_t stream, int dtype, int act, const void* 
                             int V, int blank);
 // The forward log-softmax family (lsm.h; lsm_f32.hip holds these launchers) for logits of any RNNT_DTYPE_*
 // (hipErrorInvalidValue for another dtype): fp32 arithmetic from the load on, pairs and log-probs in fp32, d/d logits in
-// the logits' type.  Plain log-softmax, fused gather into the diagonal-major pair plane, fused d/d logits:
+// the logits' type.  Which kernel, in which shape: lsm_plan.h decides once per call, the launchers switch on its plan.
+// Plain log-softmax, fused gather into the diagonal-major pair plane, fused d/d logits:
 hipError_t launch_log_softmax(hipStream_t stream, int dtype, const void* x, float* out, int64_t rows, int V);
 // the same, and col_out[row] = out[row*V + col] (the same float) as a contiguous plane of `rows` floats
 hipError_t launch_log_softmax_plane(hipStream_t stream, int dtype, const void* x, float* out, float* col_out, int64_t rows,
@@ -189,6 +190,10 @@ hipError_t launch_lsm_gather_compact(hipStream_t stream, int dtype, const void* 
                                      int V, int blank);
 hipError_t launch_logits_backward_compact(hipStream_t stream, int dtype, const void* logits, const float* g2_rowmajor,
                                           const float* scale, void* dlogits, const PackedRows& cr, int V, int blank);
+// rnnt_amd_debug_lsm_plan (include/warp_rnnt_amd.h): the plan of this family, or of launch_log_softmax_backward, for these
+// facts under the process's knobs, no launch
+__attribute__((visibility("hidden"))) int debug_lsm_plan(int mode, int dtype, int64_t rows, int V, int T, int U, int compact,
+                                                         int aligned, int plane, int* out, int n_out);
 hipError_t launch_expand(hipStream_t stream, const float* g2_skewed, const int* labels,
                          const int* xn, const int* yn, const float* scale, float* dense, int N,
                          int T, int U, int V, int blank, int overwrite_mode);

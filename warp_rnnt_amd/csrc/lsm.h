@@ -12,9 +12,12 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "lsm_plan.h"
 #include "streaming.h"
 
 namespace rnnt {
+
+static_assert(LSM_WAVE == WAVE, "lsm_plan.h plans for this wave");
 
 // The row -> cell map of the fused log-softmax kernels is a policy, passed by value and chosen by a template parameter.
 // chunk(first, last) is called by every wave of a kernel, wave-uniformly, before at() is asked for rows in [first, last];
@@ -152,18 +155,11 @@ struct CompactMap {
 #define RNNT_LSM_LOAD(p) rnnt_load4<RNNT_LSM_NT_MODE(MODE)>(p)
 #define RNNT_LSM_STORE(p, v) rnnt_store4<RNNT_LSM_NT_MODE(MODE)>(p, v)
 
-// What the log-softmax kernels emit.
-enum LsmMode : int {
-    LSM_NORM = 0,    // log-softmax rows
-    LSM_GATHER = 1,  // diagonal-major (blank,label) log-prob pairs; log-probs never materialise
-    LSM_BWD = 2      // d(loss)/d(logits) rows from the gathered gradients:
-                     //   dz[v] = s*( [v==blank]gB + [v==label]gL - softmax(z)[v]*(gB+gL) )
-};
 // Storage type E of the logits: float, or __bf16 / _Float16 (RNNT_DTYPE_BF16 / _F16; one unit each).  Half-precision
 // logits are converted to fp32 as they are loaded -- everything behind the load is the fp32 code -- and d/d logits (LSM_BWD)
 // are converted back ONCE, round to nearest even (the compiler's cast: v_cvt_pk_bf16_f32 / v_cvt_f16_f32), as they are
 // stored.  The kernels move rows in vectors of four elements (16 bytes of fp32, 8 of half) and every alignment predicate of
-// dispatch_lsm is stated in those vectors, so a V reaches the same kernel, the same lanes per row and the same reduction
+// plan_lsm (lsm_plan.h) is stated in those vectors, so a V reaches the same kernel, the same lanes per row and the same reduction
 // tree at every E: the bits of a half-precision row are those of its fp32 upcast.
 template <typename E> struct LsmVec { typedef E type __attribute__((ext_vector_type(4))); };
 template <typename E> using lsm_vec_t = typename LsmVec<E>::type;
@@ -203,14 +199,8 @@ struct LsmBwd {
     int col;
 };
 
-constexpr int SM_THREADS = 256;
-constexpr int SM_FLOATS = 3200;   // LDS tile budget in floats: one pass of the 256 threads over a 12.5 KiB tile.  (512 threads x 25 KiB: 2 % faster in the isolated probe, slower in bench.py and in the fused gather mode; two passes per tile or 50 KiB tiles are clearly worse.)
-// In the fused gather the shared tile of half-precision logits holds twice the rows: 12.8 KB of HBM per tile, as for fp32
-// (c4, bf16: 178 -> 172 us; the fused backward, which also writes the tile back, 287 -> 290 us with it and keeps the
-// fp32 row count).  Rows per tile do not touch the bits: the lanes of a row and its reduction tree stay the same.
-template <typename E, int MODE> constexpr int sm_floats() {
-    return MODE == LSM_GATHER ? SM_FLOATS * (int)(sizeof(float) / sizeof(E)) : SM_FLOATS;
-}
+// (SM_THREADS, SM_FLOATS and the rows per tile of each mode and storage type: lsm_plan.h)
+template <typename E, int MODE> constexpr int sm_floats() { return lsm_tile_floats(MODE, (int)sizeof(E)); }
 
 // WP ("wave private", L <= 16 and one pass per tile): every wave stages, normalises and stores its own
 // WAVE/L consecutive rows (a multiple of 4, so its chunk is 16-byte aligned) and the workgroup never
@@ -245,7 +235,7 @@ k_lsm_small_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t row
 // Shape of the row-per-workgroup kernel: THREADS x NV float4 must cover a row.  The registers that hold
 // the row set the residency (NV=16 x 256 threads: 84 VGPRs, 5 waves/SIMD; NV=8: 8 waves/SIMD).  The launcher
 // picks 1.25-2.5 float4 per thread for the plain log-softmax and the smallest cover for the read-mostly fused modes
-// (dispatch_lsm).
+// (plan_lsm, lsm_plan.h).
 // cache policy of the plain (LSM_NORM) row-per-workgroup stream: non-temporal loads and non-temporal stores.
 // Both (round 3; round 1 had tried them on the LDS-staged small-V kernel only, where they do nothing): c5 (V=10000, in
 // place, 288 GB of traffic) 57.4 -> 51.3 ms per step, c3 (V=5000) 0.708 -> 0.695 ms; loads alone are WORSE (c3 0.733),
@@ -359,7 +349,7 @@ template <int KR> __device__ __forceinline__ void half_max32_rows(float (&M)[KR]
 }
 #undef RNNT_DPPMAX_STEPS
 #undef RNNT_DPPMAX
-constexpr int RG_UN = 2;   // groups per half and wave, loads first (1: 500 us, 2: 462-484, 4: 482-498)
+// (RG_UN = 2 groups per half and wave, loads first: lsm_plan.h)
 
 // NT: bit 0 = non-temporal loads, bit 1 = non-temporal stores (both: 462 us for the c4 tensor, neither: 484); the launch
 // passes 3, and the stores leave through the strip written through and streaming
@@ -615,16 +605,6 @@ k_lsm_rows_diag(const E* x, float* out, const int* __restrict__ labels, int V, i
     if (own) reinterpret_cast<float2*>(out)[(plane + r) * U + u0 + lane] = make_float2((xb - m) - lg, (xl - m) - lg);
 }
 
-// rows per group for k_lsm_regs, or 0 when the kernel does not fit V: the largest KR <= 4 with KR*V a multiple of 4 and
-// KR*V/4 <= 32 lanes, if it keeps at least 20 of the 32 lanes of a half busy
-static int lsm_regs_rows_per_group(int V) {
-    if (V < 4) return 0;
-    int best = 0;
-    for (int k = 1; k <= 4; ++k)
-        if ((k * V) % 4 == 0 && (k * V) / 4 <= 32) best = k;
-    return (best && (best * V) / 4 >= 20) ? best : 0;
-}
-
 // One launch of a fused log-softmax kernel family, dense or compact by the map policy.
 template <typename E, int L, int MODE, bool WP, class Map>
 static void launch_lsm_small(unsigned grid, size_t lds, hipStream_t stream, const E* x, LsmOut<MODE, E>* out,
@@ -660,216 +640,100 @@ static void launch_lsm_rows(unsigned grid, hipStream_t stream, const E* x, float
         k_lsm_rows<E, L, Q><<<grid, 256, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank);
 }
 
-// E: the storage type of x (and of out in LSM_BWD).  Every byte predicate of the routing is one of whole four-element
-// vectors (16 bytes of fp32, 8 of half), so a V takes the same kernel and the same lanes per row at every E.
-// Map: the row -> cell policy (DenseMap, CompactMap); compact rows never take the diagonal walk of k_lsm_rows_diag.
+// What the plan says, launched: a switch on the family and on its template selectors, nothing decided here.
+// E: the storage type of x (and of out in LSM_BWD).  Map: the row -> cell policy (DenseMap, CompactMap).
 template <int MODE, typename E, class Map>
-static hipError_t dispatch_lsm_map(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, Map map, int64_t rows, int V,
-                                   int blank, LsmBwd bw) {
-    constexpr bool GATHER = MODE == LSM_GATHER;
-    if (rows <= 0) return hipSuccess;
-    const bool aligned = (reinterpret_cast<uintptr_t>(x) % (4 * sizeof(E)) == 0) &&
-                         (GATHER || reinterpret_cast<uintptr_t>(out) % (4 * sizeof(*out)) == 0);
-    if constexpr (MODE == LSM_NORM) {
-        // rows in registers where the vocabulary allows it (RNNT_LSM_NO_REGS=1: the LDS-staged kernel, for A/B runs)
-        static const bool no_regs = ab_getenv("RNNT_LSM_NO_REGS") != nullptr;
-        // (below V = 32 -- four rows per group -- the LDS-staged kernel with its straight-line row pass is the faster one
-        //  since round 4: the c4 lattice with V=24 0.584 -> 0.536 ms per step, V=28 0.589-0.605 -> 0.584, c2 0.0343 -> 0.0336;
-        //  from V = 32 on this kernel wins inside the step: V=40 0.71 vs 0.73, V=50 0.870 vs 0.893; tools/step_rate.py)
-        const int kr = (aligned && !no_regs && V >= 32) ? lsm_regs_rows_per_group(V) : 0;
-        if (kr && rows >= kr) {
-            const int64_t ngroups = rows / kr;
-            const int64_t per_wg = 4 * RG_UN * 2;               // 4 waves x RG_UN groups x 2 halves
-            int64_t grid = (ngroups + per_wg - 1) / per_wg;
-            // every XCD streams a contiguous eighth of the tensor (as the row-per-workgroup kernel below; here it costs two
-            // scalar instructions): V=50 1.44 GB equal, 5.76 GB 5.66 -> 5.86 TB/s, V=64 6.25 -> 6.40, 100 5.92 -> 6.19, 128
-            // 6.15 -> 6.44; the c4 step in bench.py 0.8759 / 0.8781 / 0.8779 -> 0.8726 / 0.8702 / 0.8709 ms, three
-            // interleaved pairs (profiles/r04_lsm_xcd_order_ab.txt).  RNNT_LSM_REGS_XCD=0: the plain order (A/B runs)
-            static const int regs_xcd = ab_getenv("RNNT_LSM_REGS_XCD") ? atoi(ab_getenv("RNNT_LSM_REGS_XCD")) : 1;
-            if (regs_xcd) grid = (grid + 7) / 8 * 8;
-            if (grid < ((int64_t)1 << 31)) {
-#define LSM_REGS(KR) \
-    case KR:                                                                                                   \
-        if (bw.col_out)                                                                                        \
-            k_lsm_regs<E, KR, 3, true><<<(unsigned)grid, 256, 0, stream>>>(x, out, ngroups, V, regs_xcd, bw.col_out, bw.col); \
-        else                                                                                                   \
-            k_lsm_regs<E, KR, 3, false><<<(unsigned)grid, 256, 0, stream>>>(x, out, ngroups, V, regs_xcd, nullptr, 0); \
+static hipError_t launch_lsm_plan(hipStream_t stream, const LsmPlan& p, const E* x, LsmOut<MODE, E>* out, const Map& map,
+                                  int64_t rows, int V, int blank, LsmBwd bw) {
+    bw.xcd = p.xcd;
+#define LSM_LARGE(TH_, NV_) \
+    if (p.TH == TH_ && p.NV == NV_) launch_lsm_large<E, MODE, TH_, NV_>(p.grid, stream, x, out, map, rows, V, blank, bw);
+    switch (p.family) {
+        case LsmFamily::REGS:
+            if constexpr (MODE == LSM_NORM) {
+                const int64_t ngroups = p.head_rows / p.KR;
+#define LSM_REGS(KR_) \
+    case KR_:                                                                                                    \
+        if (bw.col_out)                                                                                          \
+            k_lsm_regs<E, KR_, 3, true><<<p.grid, 256, 0, stream>>>(x, out, ngroups, V, p.xcd, bw.col_out, bw.col); \
+        else                                                                                                     \
+            k_lsm_regs<E, KR_, 3, false><<<p.grid, 256, 0, stream>>>(x, out, ngroups, V, p.xcd, nullptr, 0);     \
         break;
-                switch (kr) { LSM_REGS(1) LSM_REGS(2) LSM_REGS(3) LSM_REGS(4) }
+                switch (p.KR) { LSM_REGS(1) LSM_REGS(2) LSM_REGS(3) LSM_REGS(4) }
 #undef LSM_REGS
-                const hipError_t e = hipGetLastError();
-                const int64_t done = ngroups * kr;              // (a group boundary: vector aligned)
-                if (e != hipSuccess || done == rows) return e;
-                if (bw.col_out) bw.col_out += done;             // (the rows left over: the LDS-staged kernel, and its plane)
-                return dispatch_lsm_map<MODE, E>(stream, x + done * V, out + done * V, map, rows - done, V, blank, bw);
             }
-        }
-    }
-    if constexpr (MODE == LSM_NORM) {
-        // 128 < V <= 1024 whose rows fill a cover of 64 ... 256 threads x one float4 (or an exact 64x2 / 64x3 / 128x2):
-        // the row-in-registers kernel below, one row per small workgroup, instead of the LDS-staged tiles.  Measured
-        // round 3 (tools/lsm_rate.py, 1.44 GB in, TB/s in + out, LDS-staged -> registers; profiles/r03_lsm_midv_probe.txt):
-        // V=256 5.82 -> 6.44, 496 5.33 -> 6.12, 500 5.14 -> 5.90, 512 5.77 -> 6.47, 768 5.58 -> 6.15, 980 5.26 -> 6.00,
-        // 1000 5.14 -> 6.10, 1024 5.76 -> 6.59; with 94 % of the lanes busy still +4 ... +10 % (484, 724, 964), below
-        // that -- and below 98 % for a single wave (V=244: 5.53 -> 5.23) -- the tiles win (V=200, 400, 600: 78 / 59 %).
-        static const bool no_lgr = ab_getenv("RNNT_LSM_NO_LGR") != nullptr;    // A/B runs: the LDS-staged kernel instead
-        if (aligned && !no_lgr && V % 4 == 0 && V > 128 && V <= 1024) {
-            const int nvec = V >> 2, th = (nvec + 63) / 64 * 64;
-            const unsigned grid = (unsigned)(rows < (1 << 22) ? rows : (1 << 22));
-#define LGR(TH, NV) { launch_lsm_large<E, MODE, TH, NV>(grid, stream, x, out, map, rows, V, blank, bw); return hipGetLastError(); }
-            if (nvec == 64) LGR(64, 1)
-            if (nvec == 128) LGR(64, 2)
-            if (nvec == 192) LGR(64, 3)
-            if (nvec == 256) LGR(128, 2)
-            if (th == 64 && nvec >= 63) LGR(64, 1)
-            if (th == 128 && nvec * 100 >= th * 94) LGR(128, 1)
-            if (th == 192 && nvec * 100 >= th * 94) LGR(192, 1)
-            if (th == 256 && nvec * 100 >= th * 94) LGR(256, 1)
-#undef LGR
-        }
-    }
-    if constexpr (MODE == LSM_GATHER) {
-        // V % 4 != 0 (c4's own V = 50: rows that pack into 16-byte groups only in twos) stays on the LDS-staged kernel below.
-        // Round 5 tried the rows-in-registers loads of k_lsm_regs for it once more, with what round 4 had learnt on
-        // k_lsm_rows -- the lane that stores a row's pair asks for its two logits itself, ahead of the group loads, or picks
-        // them out of an LDS copy of the groups: whole fused forward at c4 503-512 us (two and four groups per half-wave:
-        // 558 / 503; LDS copy 512) against 419-433 for the LDS-staged kernel then, and ~400 since its staging loop issues
-        // its loads first (k_lsm_small; the kernel alone 290 -> 225-255 us, 5.6-6.4 TB/s read against 7.0 for a bare
-        // read-only stream, tools/ubench/copy_rate.hip, profiles/r05_loads_first_ab.txt).
-        // Rows in registers, L lanes per row (k_lsm_rows), against the LDS-staged kernel below -- re-measured after that
-        // kernel got its straight-line row pass (forward of the fused entry, N=32, T=500, U=100, us, k_lsm_rows / LDS tiles;
-        // tools/fused_rate.py, profiles/r04_lsm_rows_ab.txt section 9): V=32 97 / 127, 64 140 / 146, 128 187 / 197, 256 320 /
-        // 341, 320 393 / 404; 448 512 / 522, 480 532 / 554, 500 561 / 583, 512 505 / 587, 544 609 / 753, 640 668 / 749, 768
-        // 791 / 812, 896 850 / 930, 1000 986 / 1089, 1024 1016 / 1128; but 96 180 / 163, 160 256 / 237, 192 285 / 262, 224 302 /
-        // 290, 352 426 / 418, 384 456 / 426, 400 510 / 485, and everything whose 8- or 16-lane row instructions straddle
-        // lines (V=100: 236 / 187, 132: 281 / 257) or needs float2 rows (V=50: 169 / 132).  Rule: the powers of two from 32
-        // to 256, and every V % 4 == 0 from 448 on.
-        // (RNNT_LSM_NO_ROWS=1: the LDS-staged kernel, for A/B runs; RNNT_LSM_NO_DIAG=1: consecutive rows per wave for
-        //  every V; RNNT_LSM_ROWS_ANY=1: this kernel for every V % 4 == 0)
-        static const bool no_rows = ab_getenv("RNNT_LSM_NO_ROWS") != nullptr;
-        static const bool no_diag = ab_getenv("RNNT_LSM_NO_DIAG") != nullptr;
-        static const bool rows_any = ab_getenv("RNNT_LSM_ROWS_ANY") != nullptr;
-        const bool rows_rule = V == 32 || V == 64 || V == 128 || V == 256 || V >= 448;
-        if (aligned && !no_rows && V % 4 == 0 && V >= 32 && V <= 1024 && (rows_rule || rows_any)) {
-            int L = 8;
-            while (L < 64 && L * 16 < V) L <<= 1;
-            const int q = (V / 4 + L - 1) / L;         // 1 ... 4
-            if constexpr (!Map::COMPACT) {             // (the diagonal walk needs the dense (T,U) grid)
-                const int* labels = map.labels;
-                const int T = map.T, U = map.U;
-                const int64_t N = rows / ((int64_t)T * U), nub = (U + 15) / 16;
-                if (V <= 64 && V % 32 == 0 && T >= 16 && !no_diag && N <= 65535 && nub <= 65535) {
-                    const dim3 grid((unsigned)((T + 3) / 4), (unsigned)nub, (unsigned)N);
-                    if (q == 1) k_lsm_rows_diag<E, 1><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
-                    else k_lsm_rows_diag<E, 2><<<grid, 256, 0, stream>>>(x, out, labels, V, T, U, blank);
-                    return hipGetLastError();
-                }
+            break;
+        case LsmFamily::LGR:
+            if constexpr (MODE == LSM_NORM) {
+                LSM_LARGE(64, 1) LSM_LARGE(64, 2) LSM_LARGE(64, 3) LSM_LARGE(128, 2)
+                LSM_LARGE(128, 1) LSM_LARGE(192, 1) LSM_LARGE(256, 1)
             }
-            const int64_t rpw = L <= 8 ? 2 * (WAVE / L) : WAVE / L;       // RowsShape<L>::RPW
-            const int64_t grid = stream_grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
-            if ((rows + 4 * rpw - 1) / (4 * rpw) < ((int64_t)1 << 31) - 8) {
+            break;
+        case LsmFamily::ROWS:
+            if constexpr (MODE == LSM_GATHER) {
 #define LSM_ROWS(LL, QQ) \
-    if (L == LL && q == QQ) launch_lsm_rows<E, LL, QQ>((unsigned)grid, stream, x, out, map, rows, V, blank);
+    if (p.L == LL && p.Q == QQ) launch_lsm_rows<E, LL, QQ>(p.grid, stream, x, out, map, rows, V, blank);
 #define LSM_ROWS_L(LL) LSM_ROWS(LL, 1) LSM_ROWS(LL, 2) LSM_ROWS(LL, 3) LSM_ROWS(LL, 4)
                 LSM_ROWS_L(8) LSM_ROWS_L(16) LSM_ROWS_L(32) LSM_ROWS_L(64)
 #undef LSM_ROWS_L
 #undef LSM_ROWS
-                return hipGetLastError();
             }
-        }
-    }
-    if (aligned && V <= 1024) {
-        int L = 1;
-        while (L < 64 && L * 16 < V) L <<= 1;          // <= 16 columns per lane
-        const int q = (V + L - 1) / L;
-        const int rpp = SM_THREADS / L;                // rows per pass, a multiple of 4
-        int R = (sm_floats<E, MODE>() / V) / rpp * rpp;   // whole passes
-        if (R < rpp) R = rpp;
-        // wave-private tiles: each wave owns WAVE/L rows (a multiple of 4 for L <= 16), one pass
-        static const bool no_wp = ab_getenv("RNNT_LSM_NO_WP") != nullptr;
-        // Plain log-softmax only: measured 2-3 % faster there (0.506 -> 0.493 ms at c4), slower for the fused
-        // gather (its one-lane-per-row mapping phase wants all rows of the tile in ONE wave: 0.52 -> 0.556 ms)
-        // and for the fused backward (+15 us).
-        static const bool wp_fused = ab_getenv("RNNT_LSM_WP_FUSED") != nullptr;      // (A/B: the wave-private form in the fused modes)
-        const bool wp = (L <= 16) && !no_wp && (MODE == LSM_NORM || wp_fused);
-        if (wp) R = rpp;
-        const size_t lds = (size_t)R * V * sizeof(float) + (GATHER ? (size_t)R * sizeof(float2) : 0);
-        const unsigned grid = stream_grid((unsigned)((rows + R - 1) / R));
-#define LSM_SMALL(LL)                                                                           \
-    case LL:                                                                                    \
-        if (wp && LL <= 16)                                                                     \
-            launch_lsm_small<E, LL, MODE, (LL <= 16)>(grid, lds, stream, x, out, map, rows, V, R, q, blank, bw); \
-        else                                                                                    \
-            launch_lsm_small<E, LL, MODE, false>(grid, lds, stream, x, out, map, rows, V, R, q, blank, bw);     \
+            break;
+        case LsmFamily::ROWS_DIAG:
+            if constexpr (MODE == LSM_GATHER && !Map::COMPACT) {
+                const dim3 grid(p.grid, p.grid_y, p.grid_z);
+                if (p.Q == 1) k_lsm_rows_diag<E, 1><<<grid, 256, 0, stream>>>(x, out, map.labels, V, map.T, map.U, blank);
+                else k_lsm_rows_diag<E, 2><<<grid, 256, 0, stream>>>(x, out, map.labels, V, map.T, map.U, blank);
+            }
+            break;
+        case LsmFamily::SMALL:
+#define LSM_SMALL(LL)                                                                                            \
+    case LL:                                                                                                     \
+        if (p.WP)                                                                                                \
+            launch_lsm_small<E, LL, MODE, (LL <= 16)>(p.grid, p.lds_bytes, stream, x, out, map, rows, V, p.R, p.q, blank, bw); \
+        else                                                                                                     \
+            launch_lsm_small<E, LL, MODE, false>(p.grid, p.lds_bytes, stream, x, out, map, rows, V, p.R, p.q, blank, bw);     \
         break;
-        switch (L) {
-            LSM_SMALL(1) LSM_SMALL(2) LSM_SMALL(4) LSM_SMALL(8) LSM_SMALL(16) LSM_SMALL(32)
-            LSM_SMALL(64)
-        }
-#undef LSM_SMALL
-    } else if (aligned && V % 4 == 0 && V <= LG_MAXV) {
-        // Which rows an XCD streams (plain log-softmax only).  Workgroups go to the eight XCDs by blockIdx mod 8, so with
-        // row = work item every XCD reads every eighth row of one moving front; with bw.xcd each streams a contiguous
-        // eighth of the tensor.  Measured (tools/lsm_rate.py, TB/s in + out, every-eighth / contiguous, 1.92 GB in; 8 GB
-        // in brackets; profiles/r04_lsm_xcd_order_ab.txt): V=1500 5.9 / 6.2, 3000 6.0 / 6.2 [5.95 / 6.6], 5000 5.8-5.9 /
-        // 6.0-6.5 [5.7 / 6.1], 7168 6.2 / 6.4, 8192 6.0-6.2 / 6.3-6.4 [5.8 / 6.2], 16384 5.2-5.4 / 6.0 [5.3 / 6.2];
-        // nothing at 2048, 4096, 5120 ... 6144, 12288; WORSE for the three-pass covers of 2048 < V/4 <= 3072 (V=10000:
-        // 6.0 / 5.6 [5.9 / 5.6]), which keep the plain order.  RNNT_LG_XCD=0 / 1 forces one or the other (A/B runs).
-        static const int xcd_force = ab_getenv("RNNT_LG_XCD") ? atoi(ab_getenv("RNNT_LG_XCD")) : -1;
-        // (fused gather / backward modes: no difference at c3 -- fused forward 0.3196 / 0.3184 / 0.3181 vs 0.3186 / 0.3178 /
-        //  0.3190 ms -- so they keep the plain order; RNNT_LG_XCD_FUSED=1 to try)
-        static const int xcd_fused = ab_getenv("RNNT_LG_XCD_FUSED") ? atoi(ab_getenv("RNNT_LG_XCD_FUSED")) : 0;
-        if constexpr (MODE == LSM_NORM) {
-            const int nv4 = V >> 2;
-            bw.xcd = xcd_force >= 0 ? (xcd_force != 0) : !(nv4 > 2048 && nv4 <= 3072);
-        } else {
-            bw.xcd = xcd_fused;
-        }
-        unsigned grid = (unsigned)(rows < (1 << 22) ? rows : (1 << 22));
-        if (bw.xcd) grid = (grid + 7u) & ~7u;
-        if constexpr (MODE == LSM_NORM) {
-            // The read + write stream wants about two float4 per thread and (nearly) every thread busy in every pass;
-            // workgroups of 512 or 1024 threads (which tile a CU's 2048 exactly) beat the sizes in between.  Round 2
-            // (profiles/r02_lsm_large_variants.txt, threads x passes, us for ~1.9 GB in + out): V=3000 256x3 734 /
-            // 384x2 663; V=8192 256x8 687 / 1024x2 666; V=10000 512x5 870 / 1024x3 828-834 / 896x3 811; V=16384 512x8
-            // 707 / 1024x4 723.  Re-swept in round 3 with the non-temporal policies in place
-            // (profiles/r03_xcd_run_order_probe.txt part 3, profiles/r03_lg_cover_ab.txt; TB/s in + out): V=5000 640x2
-            // 5.71 / 512x3 5.79-5.82 (c3 in bench.py: 0.696 -> 0.680 ms); V=5120 640x2 5.90 / 512x3 6.10; V=5600 768x2
-            // 5.96 / 512x3 6.17; V=6144 768x2 6.23 / 512x3 5.99 / 1024x2 6.11; V=7168 896x2 5.90 / 1024x2 6.16.
-            // The thread count is a template parameter on purpose (the same kernel with blockDim.x read at run
-            // time: 780 us at V=5000).
-            const int nvec = V >> 2;
-#define LGN(TH, NV) case TH: launch_lsm_large<E, MODE, TH, NV>(grid, stream, x, out, map, rows, V, blank, bw); break;
-            if (nvec > 3072) {
-                launch_lsm_large<E, MODE, 512, 8>(grid, stream, x, out, map, rows, V, blank, bw);
-            } else if (nvec > 2048) {
-                const int th = (nvec + 383) / 384 * 128;
-                switch (th) { LGN(768, 3) LGN(896, 3) LGN(1024, 3) }
-            } else if (nvec > 1536) {
-                launch_lsm_large<E, MODE, 1024, 2>(grid, stream, x, out, map, rows, V, blank, bw);
-            } else if (nvec > 1408) {
-                launch_lsm_large<E, MODE, 768, 2>(grid, stream, x, out, map, rows, V, blank, bw);
-            } else if (nvec > 1024) {
-                launch_lsm_large<E, MODE, 512, 3>(grid, stream, x, out, map, rows, V, blank, bw);
-            } else {
-                int th = (nvec + 255) / 256 * 128;
-                th = th < 256 ? 256 : th;
-                switch (th) { LGN(256, 2) LGN(384, 2) LGN(512, 2) }
+            switch (p.L) {
+                LSM_SMALL(1) LSM_SMALL(2) LSM_SMALL(4) LSM_SMALL(8) LSM_SMALL(16) LSM_SMALL(32)
+                LSM_SMALL(64)
             }
-#undef LGN
-        } else {
-            // read-mostly modes (fused gather, fused backward): the smallest cover, for the residency
-            if (V <= 4096)
-                launch_lsm_large<E, MODE, 256, 4>(grid, stream, x, out, map, rows, V, blank, bw);
-            else if (V <= 8192)
-                launch_lsm_large<E, MODE, 256, 8>(grid, stream, x, out, map, rows, V, blank, bw);
-            else
-                launch_lsm_large<E, MODE, 512, 8>(grid, stream, x, out, map, rows, V, blank, bw);
-        }
-    } else {
-        launch_lsm_generic<E, MODE>((unsigned)((rows + 3) / 4), stream, x, out, map, rows, V, blank, bw);
+#undef LSM_SMALL
+            break;
+        case LsmFamily::LARGE:
+            if constexpr (MODE == LSM_NORM) {
+                LSM_LARGE(512, 8) LSM_LARGE(768, 3) LSM_LARGE(896, 3) LSM_LARGE(1024, 3) LSM_LARGE(1024, 2)
+                LSM_LARGE(768, 2) LSM_LARGE(512, 3) LSM_LARGE(256, 2) LSM_LARGE(384, 2) LSM_LARGE(512, 2)
+            } else {
+                LSM_LARGE(256, 4) LSM_LARGE(256, 8) LSM_LARGE(512, 8)
+            }
+            break;
+        case LsmFamily::GENERIC:
+            launch_lsm_generic<E, MODE>(p.grid, stream, x, out, map, rows, V, blank, bw);
+            break;
     }
+#undef LSM_LARGE
     return hipGetLastError();
+}
+
+// Facts, knobs, plan, launch.  The register kernel takes whole groups of rows; what is left over is planned and launched
+// as a call of its own behind it (lsm_plan.h: never the register kernel again), with its slice of the plane.
+template <int MODE, typename E, class Map>
+static hipError_t dispatch_lsm_map(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, Map map, int64_t rows, int V,
+                                   int blank, LsmBwd bw) {
+    if (rows <= 0) return hipSuccess;
+    const bool aligned = (reinterpret_cast<uintptr_t>(x) % (4 * sizeof(E)) == 0) &&
+                         (MODE == LSM_GATHER || reinterpret_cast<uintptr_t>(out) % (4 * sizeof(*out)) == 0);
+    LsmFacts f{MODE, (int)sizeof(E), rows, V, aligned, Map::COMPACT, 1, 1, bw.col_out != nullptr};
+    if constexpr (!Map::COMPACT) { f.T = map.T; f.U = map.U; }
+    const LsmKnobs& knobs = lsm_knobs();
+    const LsmPlan head = plan_lsm(f, knobs);
+    const hipError_t e = launch_lsm_plan<MODE, E>(stream, head, x, out, map, rows, V, blank, bw);
+    if (head.family != LsmFamily::REGS || e != hipSuccess || head.head_rows == rows) return e;
+    const int64_t done = head.head_rows;
+    f.rows = rows - done;
+    if (bw.col_out) bw.col_out += done;
+    return launch_lsm_plan<MODE, E>(stream, plan_lsm(f, knobs), x + done * V, out + done * V, map, f.rows, V, blank, bw);
 }
 
 template <int MODE, typename E = float>

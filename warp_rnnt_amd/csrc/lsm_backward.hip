@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "lsm_plan.h"
 #include "streaming.h"
 
 namespace rnnt {
@@ -16,8 +17,7 @@ namespace rnnt {
 // Same three shapes as the forward kernels (LDS row tiles / one row per workgroup in
 // registers / wave per row); 12V bytes per row element (read dy, read y, write dx).
 // ---------------------------------------------------------------------------
-constexpr int SMB_THREADS = 256;   // backward: two tiles per workgroup, keep the 256-thread shape
-constexpr int SMB_FLOATS = 3200;
+// (SMB_THREADS, SMB_FLOATS: lsm_plan.h)
 template <int L>
 __global__ void __launch_bounds__(SMB_THREADS)
 k_lsmbwd_small(const float* dy, const float* y, float* dx, int64_t rows, int V, int R, int q) {
@@ -135,51 +135,31 @@ k_lsmbwd_generic(const float* dy, const float* y, float* dx, int64_t rows, int V
     for (int c = lane; c < V; c += WAVE) o[c] = g[c] - expf(p[c]) * s;
 }
 
+// plan_lsm_backward (lsm_plan.h) decides; this launches what it says
 hipError_t launch_log_softmax_backward(hipStream_t stream, const float* dy, const float* y, float* dx,
                                        int64_t rows, int V) {
     if (rows <= 0) return hipSuccess;
     const bool aligned = reinterpret_cast<uintptr_t>(dy) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0 &&
                          reinterpret_cast<uintptr_t>(dx) % 16 == 0;
-    if (aligned && V <= 1024) {
-        int L = 1;
-        while (L < 64 && L * 16 < V) L <<= 1;
-        const int q = (V + L - 1) / L;
-        int R = (SMB_FLOATS / V) / 4 * 4;
-        if (R < 4) R = 4;
-        const size_t lds = (size_t)R * V * sizeof(float) * 2;
-        const unsigned grid = stream_grid((unsigned)((rows + R - 1) / R));
-#define LSMB_SMALL(LL) case LL: k_lsmbwd_small<LL><<<grid, SMB_THREADS, lds, stream>>>(dy, y, dx, rows, V, R, q); break;
-        switch (L) { LSMB_SMALL(1) LSMB_SMALL(2) LSMB_SMALL(4) LSMB_SMALL(8) LSMB_SMALL(16) LSMB_SMALL(32) LSMB_SMALL(64) }
+    const LsmPlan p = plan_lsm_backward(rows, V, aligned, lsm_knobs());
+    switch (p.family) {
+        case LsmFamily::SMALL:
+#define LSMB_SMALL(LL) \
+    case LL: k_lsmbwd_small<LL><<<p.grid, SMB_THREADS, p.lds_bytes, stream>>>(dy, y, dx, rows, V, p.R, p.q); break;
+            switch (p.L) { LSMB_SMALL(1) LSMB_SMALL(2) LSMB_SMALL(4) LSMB_SMALL(8) LSMB_SMALL(16) LSMB_SMALL(32) LSMB_SMALL(64) }
 #undef LSMB_SMALL
-    } else if (aligned && V % 4 == 0 && V <= LG_MAXV) {
-        // every XCD streams a contiguous eighth of the rows (as the forward kernel, dispatch_lsm): the reference's call
-        // chain with the native log-softmax function at c3 2.08 / 2.07 / 2.03 -> 2.03 / 2.03 / 1.99 ms per training step;
-        // RNNT_LSMBWD_XCD=0: the plain order (A/B runs)
-        static const int bxcd = ab_getenv("RNNT_LSMBWD_XCD") ? atoi(ab_getenv("RNNT_LSMBWD_XCD")) : 1;
-        unsigned grid = (unsigned)(rows < (1 << 22) ? rows : (1 << 22));
-        if (bxcd) grid = (grid + 7u) & ~7u;
-        static const bool old_rule = ab_getenv("RNNT_LSMBWD_SMALLEST_COVER") != nullptr;    // (A/B knob)
-        if (old_rule) {
-            if (V <= 4096) k_lsmbwd_large<256, 4><<<grid, 256, 0, stream>>>(dy, y, dx, rows, V, bxcd);
-            else if (V <= 8192) k_lsmbwd_large<256, 8><<<grid, 256, 0, stream>>>(dy, y, dx, rows, V, bxcd);
-            else k_lsmbwd_large<512, 8><<<grid, 512, 0, stream>>>(dy, y, dx, rows, V, bxcd);
-        } else {      // as the forward kernel (dispatch_lsm): two or three passes, (nearly) every thread busy
-            const int nvec = V >> 2;
-            const int passes = nvec <= 2048 ? 2 : 3;
-            int th = (nvec + 128 * passes - 1) / (128 * passes) * 128;
-            th = th < 256 ? 256 : th;
-#define LGB(TH, NV) case TH: k_lsmbwd_large<TH, NV><<<grid, TH, 0, stream>>>(dy, y, dx, rows, V, bxcd); break;
-            if (nvec > 3072) {
-                k_lsmbwd_large<512, 8><<<grid, 512, 0, stream>>>(dy, y, dx, rows, V, bxcd);
-            } else if (passes == 2) {
-                switch (th) { LGB(256, 2) LGB(384, 2) LGB(512, 2) LGB(640, 2) LGB(768, 2) LGB(896, 2) LGB(1024, 2) }
-            } else {
-                switch (th) { LGB(768, 3) LGB(896, 3) LGB(1024, 3) }
-            }
+            break;
+        case LsmFamily::LARGE:
+#define LGB(TH_, NV_) \
+    if (p.TH == TH_ && p.NV == NV_) k_lsmbwd_large<TH_, NV_><<<p.grid, TH_, 0, stream>>>(dy, y, dx, rows, V, p.xcd);
+            LGB(256, 4) LGB(256, 8) LGB(512, 8)
+            LGB(256, 2) LGB(384, 2) LGB(512, 2) LGB(640, 2) LGB(768, 2) LGB(896, 2) LGB(1024, 2)
+            LGB(768, 3) LGB(896, 3) LGB(1024, 3)
 #undef LGB
-        }
-    } else {
-        k_lsmbwd_generic<<<(unsigned)((rows + 3) / 4), 256, 0, stream>>>(dy, y, dx, rows, V);
+            break;
+        default:
+            k_lsmbwd_generic<<<p.grid, 256, 0, stream>>>(dy, y, dx, rows, V);
+            break;
     }
     return hipGetLastError();
 }

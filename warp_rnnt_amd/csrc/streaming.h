@@ -81,7 +81,6 @@ template <bool NT> __device__ __forceinline__ void rnnt_store4(float4* p, float4
 
 constexpr float LOG2E = 1.44269504088896340736f;
 constexpr float LN2 = 0.693147180559945309417f;
-constexpr int LG_MAXV = 16384;   // the largest row of the row-per-workgroup kernels (k_lsm_large, k_lsmbwd_large)
 constexpr int TD = 32;   // tile edge of the to-diagonal kernels, dense and compact
 
 }  // namespace rnnt

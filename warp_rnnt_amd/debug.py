@@ -62,3 +62,28 @@ def lattice_plan(N, T, U, loader="skewed", flags=True, rings=True, offs32=False,
     if r < 0:
         raise ValueError(f"no plan for N={N}, T={T}, U={U}, pin={pin!r}")
     return LatticePlan(LATTICE_KERNELS[r & 255], r >> 8 & 255, bool(r >> 16 & 1))
+
+
+LSM_MODES = ("norm", "gather", "bwd", "log_softmax_backward")
+LSM_DTYPES = ("f32", "bf16", "f16")
+LSM_FAMILIES = ("regs", "lgr", "rows", "rows_diag", "small", "large", "generic")
+LSM_PLAN_FIELDS = ("family", "KR", "L", "Q", "WP", "TH", "NV", "grid", "grid_y", "grid_z", "lds", "R", "q", "xcd", "head_rows",
+                   "tail")
+
+
+def lsm_plan(mode, dtype, rows, V, T=1, U=1, compact=False, aligned=True, plane=False):
+    """What the library's planner (csrc/lsm_plan.h) would launch for a forward log-softmax call with these facts -- ``mode``
+    one of `LSM_MODES` (the last: the plan of ``rnnt_amd_log_softmax_backward``), ``dtype`` one of `LSM_DTYPES` -- under this
+    process's knobs and without a launch (``rnnt_amd_debug_lsm_plan``).  A dict of `LSM_PLAN_FIELDS`: ``family`` and ``tail``
+    (the family behind the register kernel's whole groups, None: nothing left over) by their names in `LSM_FAMILIES`."""
+    import ctypes
+    out = (ctypes.c_int * len(LSM_PLAN_FIELDS))()
+    r = load().rnnt_amd_debug_lsm_plan(LSM_MODES.index(mode), LSM_DTYPES.index(dtype), rows, V, T, U, int(compact),
+                                       int(aligned), int(plane), out, len(out))
+    if r < 0:
+        raise ValueError(f"no plan for rows={rows}, V={V}")
+    plan = dict(zip(LSM_PLAN_FIELDS, out))
+    plan["family"] = LSM_FAMILIES[plan["family"]]
+    plan["tail"] = None if plan["tail"] < 0 else LSM_FAMILIES[plan["tail"]]
+    plan["WP"] = bool(plan["WP"])
+    return plan
