@@ -19,6 +19,17 @@ namespace rnnt {
 
 static_assert(LSM_WAVE == WAVE, "lsm_plan.h plans for this wave");
 
+// The exponent of every element is exp2(fma(x, LOG2E, mb)) with mb = -mx * LOG2E ROUNDED to fp32.  That rounding, up to
+// |mx| * 1.44 * 2^-24, is common to the whole row: the sum comes out as s = true sum * 2^-lo, and left in log(s) it moves
+// every log-prob of the row by about |mx| * 6e-8 (2.7e-3 at mx = 60000) -- a log-softmax that is not invariant to a shift
+// of its row.  lo = fma(-mx, LOG2E, -mb) is the residual of the rounded product EXACTLY, so the row's log-sum is
+// log(s) + lo * ln 2: one fma per row, nothing per element.  `log_s` is log(s) however the body forms it.
+// Every (mx, ls) pair a kernel hands on carries this ls.  The fused backward never forms mx + ls (rounded at ulp(mx)): it
+// writes -e_j * (gs / s) with the forward's e_j = exp2(fma(x_j, LOG2E, mb)) -- the residual cancels between e_j and s.
+__device__ __forceinline__ float lsm_log_sum(float log_s, float mx, float mb) {
+    return __builtin_fmaf(__builtin_fmaf(-mx, LOG2E, -mb), LN2, log_s);
+}
+
 // The row -> cell map of the fused log-softmax kernels is a policy, passed by value and chosen by a template parameter.
 // chunk(first, last) is called by every wave of a kernel, wave-uniformly, before at() is asked for rows in [first, last];
 // pair() and scale() read the backward's gradient pair and upstream scale of a mapped row, put() stores the gather's pair.
@@ -404,11 +415,15 @@ __global__ void __launch_bounds__(256) k_lsm_regs(const E* __restrict__ x, float
         for (int r = 1; r < KR; ++r) m_first = r0 == r ? M[r] : m_first;
 #pragma unroll
         for (int r = KR - 2; r >= 0; --r) m_second = r0 + 1 == r ? M[r] : m_second;
-        const float kf = m_first * LOG2E, ks = m_second * LOG2E;
-        const float e0x = __builtin_amdgcn_exp2f(__builtin_fmaf(t.x, LOG2E, -kf));
-        const float e1x = __builtin_amdgcn_exp2f(__builtin_fmaf(t.y, LOG2E, ns > 1 ? -kf : -ks));
-        const float e2x = __builtin_amdgcn_exp2f(__builtin_fmaf(t.z, LOG2E, ns > 2 ? -kf : -ks));
-        const float e3x = __builtin_amdgcn_exp2f(__builtin_fmaf(t.w, LOG2E, ns > 3 ? -kf : -ks));
+        // x - max first, for the exponent AND the result (the association of torch): the exponent exp2((x - max) * LOG2E)
+        // costs what exp2(fma(x, LOG2E, -max * LOG2E)) does, and nothing of the row's maximum is left in the sum -- no
+        // per-row correction (lsm_log_sum), which two rows per lane would pay for per lane here
+        const float d0 = t.x - m_first, d1 = t.y - (ns > 1 ? m_first : m_second);
+        const float d2 = t.z - (ns > 2 ? m_first : m_second), d3 = t.w - (ns > 3 ? m_first : m_second);
+        const float e0x = __builtin_amdgcn_exp2f(d0 * LOG2E);
+        const float e1x = __builtin_amdgcn_exp2f(d1 * LOG2E);
+        const float e2x = __builtin_amdgcn_exp2f(d2 * LOG2E);
+        const float e3x = __builtin_amdgcn_exp2f(d3 * LOG2E);
         const float sf = e0x + (ns > 1 ? e1x : 0.f) + (ns > 2 ? e2x : 0.f) + (ns > 3 ? e3x : 0.f);
         const float ss = (ns > 1 ? 0.f : e1x) + (ns > 2 ? 0.f : e2x) + (ns > 3 ? 0.f : e3x);
         // log-sum of every row; the result is (x - max) - log-sum, the association of the LDS-staged kernel (and of
@@ -423,10 +438,8 @@ __global__ void __launch_bounds__(256) k_lsm_regs(const E* __restrict__ x, float
         for (int r = 1; r < KR; ++r) l_first = r0 == r ? Lg[r] : l_first;
 #pragma unroll
         for (int r = KR - 2; r >= 0; --r) l_second = r0 + 1 == r ? Lg[r] : l_second;
-        const rnnt_f4 res = rnnt_f4{(t.x - m_first) - l_first,
-                                  ns > 1 ? (t.y - m_first) - l_first : (t.y - m_second) - l_second,
-                                  ns > 2 ? (t.z - m_first) - l_first : (t.z - m_second) - l_second,
-                                  ns > 3 ? (t.w - m_first) - l_first : (t.w - m_second) - l_second};
+        const rnnt_f4 res = rnnt_f4{d0 - l_first, d1 - (ns > 1 ? l_first : l_second), d2 - (ns > 2 ? l_first : l_second),
+                                  d3 - (ns > 3 ? l_first : l_second)};
         if (act) strip[wv][(2 * i + half) * g4 + j] = res;
     }
     // the wave's 2 * RG_UN groups are 64 * g4 contiguous bytes: out of the strip in address order, one store instruction of
@@ -524,7 +537,7 @@ __device__ __forceinline__ void lsm_rows_stats(const E* const (&src)[RowsShape<L
             for (int e = 0; e < VEC; ++e) s += __builtin_amdgcn_exp2f(__builtin_fmaf(v[p][i][e], LOG2E, mb));
         s = lsm_group_reduce<L, false>(s);
         mx[p] = m;
-        ls[p] = __builtin_amdgcn_logf(s) * LN2;
+        ls[p] = lsm_log_sum(__builtin_amdgcn_logf(s) * LN2, m, mb);
     }
 }
 

@@ -79,13 +79,13 @@
                  (__builtin_amdgcn_exp2f(__builtin_fmaf(v[i].z, LOG2E, mb)) + __builtin_amdgcn_exp2f(__builtin_fmaf(v[i].w, LOG2E, mb)));
     }
     s = block_reduce<LG_THREADS>(s, false, red);
-    const float ls = logf(s);
+    const float ls = lsm_log_sum(logf(s), mx, mb);
     if constexpr (GATHER) {
         if (threadIdx.x == 0) map.put(out, m, make_float2((side.x - mx) - ls, (side.y - mx) - ls));
     } else if constexpr (MODE == LSM_BWD) {
         const float2 g = side;
         const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
-        const float mb2 = -(mx + ls) * LOG2E;
+        const float gq = gs / s;                                 // p_j = e_j / s (lsm_log_sum)
         LsmOut<MODE, E>* dst = out + row * V;
 #pragma unroll
         for (int i = 0; i < LG_MAXVEC; ++i) {
@@ -95,7 +95,7 @@
 #pragma unroll
                 for (int cc = 0; cc < 4; ++cc) {
                     const int e = 4 * j + cc;
-                    float d = -__builtin_amdgcn_exp2f(__builtin_fmaf(o[cc], LOG2E, mb2)) * gs;
+                    float d = -__builtin_amdgcn_exp2f(__builtin_fmaf(o[cc], LOG2E, mb)) * gq;
                     d += (e == blank) ? gB : 0.0f;
                     d += (e == m.label) ? gL : 0.0f;
                     o[cc] = d;

@@ -93,7 +93,7 @@
 #pragma unroll
         for (int i = 0; i < Q; ++i) s += __builtin_amdgcn_exp2f(__builtin_fmaf(v[i], LOG2E, mb));   // (exp2(-inf) = 0)
         s = group_sum<L>(s);
-        const float ls = __builtin_amdgcn_logf(s) * LN2;
+        const float ls = lsm_log_sum(__builtin_amdgcn_logf(s) * LN2, mx, mb);
         if constexpr (GATHER) {
             if (h == 0) stat[r] = make_float2(mx, ls);
         } else if constexpr (MODE == LSM_BWD) {
@@ -102,11 +102,11 @@
             const float sc = first ? psc : map.scale(bw, m);
             const float2 g = first ? pg : map.pair(bw, m);
             const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
-            const float mb2 = -(mx + ls) * LOG2E;
+            const float gq = gs * __builtin_amdgcn_rcpf(s);      // p_j = e_j / s (lsm_log_sum)
 #pragma unroll
             for (int i = 0; i < Q - 1; ++i)
-                row[h + i * L] = -__builtin_amdgcn_exp2f(__builtin_fmaf(v[i], LOG2E, mb2)) * gs;
-            if (tail_ok) row[ctail] = -__builtin_amdgcn_exp2f(__builtin_fmaf(v[Q - 1], LOG2E, mb2)) * gs;
+                row[h + i * L] = -__builtin_amdgcn_exp2f(__builtin_fmaf(v[i], LOG2E, mb)) * gq;
+            if (tail_ok) row[ctail] = -__builtin_amdgcn_exp2f(__builtin_fmaf(v[Q - 1], LOG2E, mb)) * gq;
             // the L lanes of a row sit in one wave and LDS operations of a wave retire in order
             if (h == 0) { row[blank] += gB; row[m.label] += gL; }
         } else {
@@ -134,7 +134,7 @@
         for (int i = 0, c = h; i < q - 1; ++i, c += L) s += __builtin_amdgcn_exp2f(__builtin_fmaf(row[c], LOG2E, mb));
         if (tail_ok) s += __builtin_amdgcn_exp2f(__builtin_fmaf(row[ctail], LOG2E, mb));
         s = group_sum<L>(s);
-        const float ls = __builtin_amdgcn_logf(s) * LN2;
+        const float ls = lsm_log_sum(__builtin_amdgcn_logf(s) * LN2, mx, mb);
         if constexpr (GATHER) {
             if (h == 0) stat[r] = make_float2(mx, ls);
         } else if constexpr (MODE == LSM_BWD) {
@@ -142,10 +142,10 @@
             const float sc = map.scale(bw, m);
             const float2 g = map.pair(bw, m);
             const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
-            const float mb2 = -(mx + ls) * LOG2E;
+            const float gq = gs * __builtin_amdgcn_rcpf(s);      // p_j = e_j / s (lsm_log_sum)
             for (int i = 0, c = h; i < q - 1; ++i, c += L)
-                row[c] = -__builtin_amdgcn_exp2f(__builtin_fmaf(row[c], LOG2E, mb2)) * gs;
-            if (tail_ok) row[ctail] = -__builtin_amdgcn_exp2f(__builtin_fmaf(row[ctail], LOG2E, mb2)) * gs;
+                row[c] = -__builtin_amdgcn_exp2f(__builtin_fmaf(row[c], LOG2E, mb)) * gq;
+            if (tail_ok) row[ctail] = -__builtin_amdgcn_exp2f(__builtin_fmaf(row[ctail], LOG2E, mb)) * gq;
             // the L lanes of a row sit in one wave and LDS operations of a wave retire in order
             if (h == 0) { row[blank] += gB; row[m.label] += gL; }
         } else {
