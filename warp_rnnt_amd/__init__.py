@@ -5,6 +5,8 @@ Layout
   _build.py        hipcc build of libwarp_rnnt_amd.so (in-tree)
   _lib.py          ctypes loader for the C ABI declared in include/warp_rnnt_amd.h
   ops.py           torch-tensor front ends of the native entry points
+  fused.py         rnnt_loss_from_logits: logits -> loss -> d/d logits, log-probabilities never in HBM
+  compat.py        the same under torchaudio's / warp-transducer's signatures (rnnt_loss, RNNTLoss; gradient clamp)
   functional.py    log_softmax whose result rnnt_loss(..., gather=True) recognises and fuses with (lazy)
   debug.py         kernel pin for A/B runs, last_lattice_kernel()
   distributed.py   batch-sharded loss over RCCL (one rank per GPU)
@@ -15,5 +17,6 @@ There is no CPU fallback anywhere in these packages.
 """
 from ._lib import load, lib_path, RNNTStatusError  # noqa: F401
 from ._mismatch import last_mismatch  # noqa: F401
+from . import compat  # noqa: F401
 
 __version__ = "0.2.0"

@@ -78,6 +78,14 @@ SYMBOLS = {
 }
 
 
+# every symbol include/warp_rnnt_amd_clamp.h declares (the gradient clamp of the fused backward; additive, version 109
+# still): the arguments of the unclamped twin and a float clamp behind them
+CLAMP_SYMBOLS = {
+    "rnnt_amd_logits_backward_clamped": (_i, SYMBOLS["rnnt_amd_logits_backward_typed"][1] + [_f]),
+    "rnnt_amd_compact_logits_backward_clamped": (_i, SYMBOLS["rnnt_amd_compact_logits_backward"][1] + [_f]),
+}
+
+
 ABI_VERSION = 109   # rnnt_amd_version() of the library these argument lists belong to
 
 
@@ -112,5 +120,13 @@ def load():
     if L.rnnt_amd_version() != ABI_VERSION:
         raise RuntimeError(f"{path} reports C-ABI version {L.rnnt_amd_version()}, this package binds version "
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
+    # additive entries do not move the version: a library built before them has to be told apart by its exports
+    for name, (res, args) in CLAMP_SYMBOLS.items():
+        fn = getattr(L, name, None)
+        if fn is None:
+            raise RuntimeError(f"{path} does not export {name} (include/warp_rnnt_amd_clamp.h): it was built from older "
+                               "sources: rebuild it (`python warp_rnnt_amd/_build.py`)")
+        fn.restype = res
+        fn.argtypes = args
     _lib = L
     return L

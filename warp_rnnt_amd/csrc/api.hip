@@ -1,6 +1,7 @@
 // C ABI of libwarp_rnnt_amd.so (declared in include/warp_rnnt_amd.h).
 // Host-side orchestration only: argument checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd.h"
+#include "../../include/warp_rnnt_amd_clamp.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -60,6 +61,8 @@ size_t carve(void* base, size_t cells, int N, int T, int U, size_t pad, Workspac
 size_t carve(void* base, int N, int T, int U, Workspace* w) { return carve(base, (size_t)N * T * U, N, T, U, 0, w); }
 
 inline bool vocab_ok(int V, int blank) { return V >= 1 && blank >= 0 && blank < V; }
+// the gradient clamp of the *_clamped entries: 0 = off, otherwise a finite positive bound
+inline bool clamp_ok(float clamp) { return clamp >= 0.0f && clamp <= 3.402823466e+38f; }     // (false for a NaN)
 inline bool dtype_ok(int dtype) { return dtype == RNNT_DTYPE_F32 || dtype == RNNT_DTYPE_BF16 || dtype == RNNT_DTYPE_F16; }
 inline bool aligned(const void* p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to == 0; }
 inline bool workspace_ok(const void* workspace) { return workspace && aligned(workspace, ALIGN); }
@@ -527,19 +530,42 @@ rnntStatus_t rnnt_amd_loss_compact_logits_bounded(rnntStream_t stream, void* wor
                            grads2, N, STU, Tmax, Umax, V, blank, fastemit_lambda);
 }
 
-rnntStatus_t rnnt_amd_compact_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* ys,
-                                              int64_t n_labels, const int* xn, const int* yn,
-                                              const int64_t* cell_offsets, const int* label_offsets,
-                                              const float* grads2, const float* grad_costs, void* dlogits, int N,
-                                              int64_t STU, int V, int blank) {
+namespace {
+rnntStatus_t compact_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* ys, int64_t n_labels,
+                                     const int* xn, const int* yn, const int64_t* cell_offsets, const int* label_offsets,
+                                     const float* grads2, const float* grad_costs, void* dlogits, int N, int64_t STU,
+                                     int V, int blank, float clamp) {
     if (!dtype_ok(dtype) || !compact_dims_ok(N, STU, 1, 1) || !vocab_ok(V, blank) || n_labels < 0)
         return RNNT_STATUS_INVALID_ARGUMENT;
     if (n_labels > 0 && !ys) return RNNT_STATUS_INVALID_ARGUMENT;
     if (STU == 0) return RNNT_STATUS_SUCCESS;
     const PackedRows cr{cell_offsets, label_offsets, xn, yn, ys, n_labels, STU, N};
-    if (launch_logits_backward_compact(stream, dtype, logits, grads2, grad_costs, dlogits, cr, V, blank) != hipSuccess)
+    if (launch_logits_backward_compact(stream, dtype, logits, grads2, grad_costs, dlogits, cr, V, blank, clamp) !=
+        hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
+}
+}  // namespace
+
+rnntStatus_t rnnt_amd_compact_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* ys,
+                                              int64_t n_labels, const int* xn, const int* yn,
+                                              const int64_t* cell_offsets, const int* label_offsets,
+                                              const float* grads2, const float* grad_costs, void* dlogits, int N,
+                                              int64_t STU, int V, int blank) {
+    return compact_logits_backward(stream, dtype, logits, ys, n_labels, xn, yn, cell_offsets, label_offsets, grads2,
+                                   grad_costs, dlogits, N, STU, V, blank, 0.0f);
+}
+
+// include/warp_rnnt_amd_clamp.h: the same with the gradient clamp of the fused backward -- d/d logits at unit upstream
+// limited to [-clamp, +clamp] elementwise, then scaled by grad_costs.  clamp == 0 IS the entry above.
+rnntStatus_t rnnt_amd_compact_logits_backward_clamped(rnntStream_t stream, int dtype, const void* logits, const int* ys,
+                                                      int64_t n_labels, const int* xn, const int* yn,
+                                                      const int64_t* cell_offsets, const int* label_offsets,
+                                                      const float* grads2, const float* grad_costs, void* dlogits,
+                                                      int N, int64_t STU, int V, int blank, float clamp) {
+    if (!clamp_ok(clamp)) return RNNT_STATUS_INVALID_ARGUMENT;
+    return compact_logits_backward(stream, dtype, logits, ys, n_labels, xn, yn, cell_offsets, label_offsets, grads2,
+                                   grad_costs, dlogits, N, STU, V, blank, clamp);
 }
 
 // Replaces run_scatter_grad_for_compact (core.h:56-60, core_compact.cu:456-500): dense (STU,V)
@@ -685,15 +711,31 @@ rnntStatus_t rnnt_amd_expand_grads(rnntStream_t stream, const float* grads_diago
 }
 
 // Backward of the fused RNNT_IN_LOGITS_DENSE path: d(sum_n grad_costs[n]*cost[n]) / d(logits).
+namespace {
+rnntStatus_t logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* labels,
+                             const float* grads_diagonal, const float* grad_costs, void* dlogits, int N, int T, int U,
+                             int V, int blank, float clamp) {
+    if (!dtype_ok(dtype) || !dims_ok(N, T, U) || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (U > 1 && !labels) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (launch_logits_backward(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank,
+                               clamp) != hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+}  // namespace
+
 rnntStatus_t rnnt_amd_logits_backward_typed(rnntStream_t stream, int dtype, const void* logits, const int* labels,
                                             const float* grads_diagonal, const float* grad_costs, void* dlogits,
                                             int N, int T, int U, int V, int blank) {
-    if (!dtype_ok(dtype) || !dims_ok(N, T, U) || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (U > 1 && !labels) return RNNT_STATUS_INVALID_ARGUMENT;
-    if (launch_logits_backward(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
-        hipSuccess)
-        return RNNT_STATUS_EXPAND_FAILED;
-    return RNNT_STATUS_SUCCESS;
+    return logits_backward(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank, 0.0f);
+}
+
+// include/warp_rnnt_amd_clamp.h: the same with the gradient clamp.  clamp == 0 IS rnnt_amd_logits_backward_typed.
+rnntStatus_t rnnt_amd_logits_backward_clamped(rnntStream_t stream, int dtype, const void* logits, const int* labels,
+                                              const float* grads_diagonal, const float* grad_costs, void* dlogits,
+                                              int N, int T, int U, int V, int blank, float clamp) {
+    if (!clamp_ok(clamp)) return RNNT_STATUS_INVALID_ARGUMENT;
+    return logits_backward(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank, clamp);
 }
 
 rnntStatus_t rnnt_amd_logits_backward(rnntStream_t stream, const float* logits, const int* labels,

@@ -167,9 +167,11 @@ hipError_t launch_log_softmax_plane(hipStream_t stream, int dtype, const void* x
                                     int V, int col);
 hipError_t launch_log_softmax_gather_skewed(hipStream_t stream, int dtype, const void* logits, const int* labels,
                                             float* ws2, int N, int T, int U, int V, int blank);
+// clamp > 0: d/d logits at unit upstream limited to [-clamp, +clamp] elementwise, in front of the scale (lsm.h: the clamped
+// twins of the plan's kernel); 0: the unclamped kernels
 hipError_t launch_logits_backward(hipStream_t stream, int dtype, const void* logits, const int* labels,
                                   const float* g2_diagonal, const float* scale, void* dlogits, int N, int T, int U, int V,
-                                  int blank);
+                                  int blank, float clamp = 0.0f);
 // The fused modes over compact (ragged packed) logits (STU,V): row c belongs to utterance n = the first n with
 // offs[n+1] > c, as the (t,u) cell of its row-major (T_n, U_n = yn[n]+1) block.  A row that belongs to nobody -- outside
 // its owner's range, an owner whose range is not T_n*U_n rows or ends past STU, T_n < 1, a label index at or past nlab --
@@ -189,7 +191,8 @@ struct PackedRows {
 hipError_t launch_lsm_gather_compact(hipStream_t stream, int dtype, const void* logits, float* ws2, const PackedRows& cr,
                                      int V, int blank);
 hipError_t launch_logits_backward_compact(hipStream_t stream, int dtype, const void* logits, const float* g2_rowmajor,
-                                          const float* scale, void* dlogits, const PackedRows& cr, int V, int blank);
+                                          const float* scale, void* dlogits, const PackedRows& cr, int V, int blank,
+                                          float clamp = 0.0f);
 // rnnt_amd_debug_lsm_plan (include/warp_rnnt_amd.h): the plan of this family, or of launch_log_softmax_backward, for these
 // facts under the process's knobs, no launch
 __attribute__((visibility("hidden"))) int debug_lsm_plan(int mode, int dtype, int64_t rows, int V, int T, int U, int compact,

@@ -203,12 +203,51 @@ struct LsmBwd {
     const float2* g2;    // diagonal-major gathered gradients (RNNT_GRADS_GATHERED_DIAGONAL)
     const float* scale;  // (N,) upstream gradient per utterance, or nullptr
     int xcd;             // row-per-workgroup kernel: 1 = every XCD streams a contiguous eighth of the rows
+    // The clamped backward kernels only (CLAMP below; > 0 there): d/d logits at unit upstream are limited to [-clamp, +clamp]
+    // elementwise, behind the two one-hot additions and IN FRONT of the upstream scale.  It belongs with `scale`; it sits
+    // here, in what was padding, so that no other member moves and the unclamped kernels read their arguments where they did.
+    float clamp;
     // LSM_NORM only: the column plane.  col_out[row] receives the float that goes into out[row*V + col] -- the blank
     // log-prob of every lattice cell, which the dense gather behind this kernel then reads as a coalesced stream instead of
     // fetching a 128-byte line of the row for it (to_diagonal.hip).  nullptr: no plane.
     float* col_out;
     int col;
 };
+
+// The gradient clamp of the fused backward (torchaudio's and warp-transducer's `clamp`):
+//     u[v]  = [v==blank] gB + [v==label] gL - softmax(z)[v] (gB+gL)        (unit upstream)
+//     dz[v] = s_n * min(max(u[v], -c), +c)
+// CLAMP is a compile-time constant of every kernel that includes a body: false in the kernels that have always been here
+// (their code is what it was), true in the k_*_clamped twins, which exist for LSM_BWD only and which a call with c > 0
+// launches under the SAME plan.  The clamped bodies keep the unclamped operation order -- e_j * (gs / s), the two
+// additions, then the clamp, then * s_n -- with the pair left unscaled, so at s_n = 1 and a clamp nothing reaches they give
+// the unclamped bits.
+__device__ __forceinline__ float lsm_clamp(float u, float c) { return __builtin_amdgcn_fmed3f(u, -c, c); }
+// clamp, then scale, for a result that is stored straight from the register (LARGE, GENERIC).  The product is pinned as an
+// fp32 value: with fp16 logits the store's conversion otherwise takes the multiply with it (v_fma_mixlo_f16, which measured
+// as ONE rounding of the exact product to fp16 -- results off the fp32 kernel's by an fp16 ulp at ties), and a half result
+// is the fp32 result rounded once.  (An empty statement: no instruction.)
+__device__ __forceinline__ float lsm_clamp_scale(float u, float c, float sc) {
+    float d = lsm_clamp(u, c) * sc;
+    asm("" : "+v"(d));
+    return d;
+}
+// SMALL: the one-hot additions of the unclamped kernel are LDS fix-ups by lane 0 of the row, made behind the row pass --
+// behind which a clamped row is already clamped and scaled.  The clamped kernel has lane 0 form the two entries whole
+// instead: it reads the blank's and the label's LOGIT out of the tile in front of the row pass, repeats the owning lane's
+// exp2 and product (the same instructions on the same operands: the same bits), adds gB and gL in the order of the fix-ups
+// (a label that is the blank -- the last column of a lattice -- takes both), clamps, scales, and stores the two floats over
+// the row's behind the row pass.  The product is rounded on its own, as the LDS round trip of the unclamped kernel rounds it.
+__device__ __forceinline__ void lsm_hot_clamped(float xb, float xl, bool same, float mb, float gq, float gB, float gL,
+                                                float c, float sc, float& hb, float& hl) {
+#pragma clang fp contract(off)
+    const float pb = -__builtin_amdgcn_exp2f(__builtin_fmaf(xb, LOG2E, mb)) * gq;
+    const float pl = -__builtin_amdgcn_exp2f(__builtin_fmaf(xl, LOG2E, mb)) * gq;
+    const float ub = pb + gB;
+    const float ul = (same ? ub : pl) + gL;
+    hb = lsm_clamp(ub, c) * sc;
+    hl = lsm_clamp(ul, c) * sc;
+}
 
 // (SM_THREADS, SM_FLOATS and the rows per tile of each mode and storage type: lsm_plan.h)
 template <typename E, int MODE> constexpr int sm_floats() { return lsm_tile_floats(MODE, (int)sizeof(E)); }
@@ -227,6 +266,7 @@ template <typename E, int L, int MODE, bool WP>
 __global__ void __launch_bounds__(SM_THREADS)
 k_lsm_small(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
             int64_t rows, int V, int R, int q, int T, int U, int blank, LsmBwd bw) {
+    constexpr bool CLAMP = false;
     DenseMap map{labels, T, U};
 #include "lsm_body_small.h"
 }
@@ -234,7 +274,27 @@ template <typename E, int L, int MODE, bool WP>
 __global__ void __launch_bounds__(SM_THREADS)
 k_lsm_small_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int R, int q, int blank,
                     LsmBwd bw) {
+    constexpr bool CLAMP = false;
     CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
+#include "lsm_body_small.h"
+}
+// (the clamped twins: LSM_BWD only)
+template <typename E, int L, int MODE, bool WP>
+__global__ void __launch_bounds__(SM_THREADS)
+k_lsm_small_clamped(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
+                    int64_t rows, int V, int R, int q, int T, int U, int blank, LsmBwd bw) {
+    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
+    constexpr bool CLAMP = true;
+    DenseMap map{labels, T, U};
+#include "lsm_body_small.h"
+}
+template <typename E, int L, int MODE, bool WP>
+__global__ void __launch_bounds__(SM_THREADS)
+k_lsm_small_compact_clamped(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int R, int q, int blank,
+                            LsmBwd bw) {
+    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
+    constexpr bool CLAMP = true;
+    CompactMap<false> map{cr, 0, 0};
 #include "lsm_body_small.h"
 }
 
@@ -256,13 +316,32 @@ template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
 __global__ void __launch_bounds__(LG_THREADS)
 k_lsm_large(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
             int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
+    constexpr bool CLAMP = false;
     DenseMap map{labels, T, U};
 #include "lsm_body_large.h"
 }
 template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
 __global__ void __launch_bounds__(LG_THREADS)
 k_lsm_large_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
+    constexpr bool CLAMP = false;
     CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
+#include "lsm_body_large.h"
+}
+template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
+__global__ void __launch_bounds__(LG_THREADS)
+k_lsm_large_clamped(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
+                    int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
+    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
+    constexpr bool CLAMP = true;
+    DenseMap map{labels, T, U};
+#include "lsm_body_large.h"
+}
+template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
+__global__ void __launch_bounds__(LG_THREADS)
+k_lsm_large_compact_clamped(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
+    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
+    constexpr bool CLAMP = true;
+    CompactMap<false> map{cr, 0, 0};
 #include "lsm_body_large.h"
 }
 
@@ -273,13 +352,32 @@ template <typename E, int MODE>
 __global__ void __launch_bounds__(256)
 k_lsm_generic(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
               int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
+    constexpr bool CLAMP = false;
     DenseMap map{labels, T, U};
 #include "lsm_body_generic.h"
 }
 template <typename E, int MODE>
 __global__ void __launch_bounds__(256)
 k_lsm_generic_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
+    constexpr bool CLAMP = false;
     CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
+#include "lsm_body_generic.h"
+}
+template <typename E, int MODE>
+__global__ void __launch_bounds__(256)
+k_lsm_generic_clamped(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
+                      int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
+    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
+    constexpr bool CLAMP = true;
+    DenseMap map{labels, T, U};
+#include "lsm_body_generic.h"
+}
+template <typename E, int MODE>
+__global__ void __launch_bounds__(256)
+k_lsm_generic_compact_clamped(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
+    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
+    constexpr bool CLAMP = true;
+    CompactMap<false> map{cr, 0, 0};
 #include "lsm_body_generic.h"
 }
 
@@ -618,28 +716,43 @@ k_lsm_rows_diag(const E* x, float* out, const int* __restrict__ labels, int V, i
     if (own) reinterpret_cast<float2*>(out)[(plane + r) * U + u0 + lane] = make_float2((xb - m) - lg, (xl - m) - lg);
 }
 
-// One launch of a fused log-softmax kernel family, dense or compact by the map policy.
-template <typename E, int L, int MODE, bool WP, class Map>
+// One launch of a fused log-softmax kernel family, dense or compact by the map policy; CLAMP (LSM_BWD only): the clamped
+// twin of the same kernel, in the same launch shape.
+template <typename E, int L, int MODE, bool WP, bool CLAMP, class Map>
 static void launch_lsm_small(unsigned grid, size_t lds, hipStream_t stream, const E* x, LsmOut<MODE, E>* out,
                              const Map& map, int64_t rows, int V, int R, int q, int blank, LsmBwd bw) {
-    if constexpr (Map::COMPACT)
+    if constexpr (CLAMP && Map::COMPACT)
+        k_lsm_small_compact_clamped<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.r, rows, V, R, q, blank,
+                                                                                       bw);
+    else if constexpr (CLAMP)
+        k_lsm_small_clamped<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.labels, rows, V, R, q, map.T,
+                                                                               map.U, blank, bw);
+    else if constexpr (Map::COMPACT)
         k_lsm_small_compact<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.r, rows, V, R, q, blank, bw);
     else
         k_lsm_small<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.labels, rows, V, R, q, map.T, map.U,
                                                                        blank, bw);
 }
-template <typename E, int MODE, int TH, int NV, class Map>
+template <typename E, int MODE, int TH, int NV, bool CLAMP, class Map>
 static void launch_lsm_large(unsigned grid, hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const Map& map,
                              int64_t rows, int V, int blank, LsmBwd bw) {
-    if constexpr (Map::COMPACT)
+    if constexpr (CLAMP && Map::COMPACT)
+        k_lsm_large_compact_clamped<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
+    else if constexpr (CLAMP)
+        k_lsm_large_clamped<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
+    else if constexpr (Map::COMPACT)
         k_lsm_large_compact<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
     else
         k_lsm_large<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
 }
-template <typename E, int MODE, class Map>
+template <typename E, int MODE, bool CLAMP, class Map>
 static void launch_lsm_generic(unsigned grid, hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const Map& map,
                                int64_t rows, int V, int blank, LsmBwd bw) {
-    if constexpr (Map::COMPACT)
+    if constexpr (CLAMP && Map::COMPACT)
+        k_lsm_generic_compact_clamped<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
+    else if constexpr (CLAMP)
+        k_lsm_generic_clamped<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
+    else if constexpr (Map::COMPACT)
         k_lsm_generic_compact<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
     else
         k_lsm_generic<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
@@ -654,13 +767,14 @@ static void launch_lsm_rows(unsigned grid, hipStream_t stream, const E* x, float
 }
 
 // What the plan says, launched: a switch on the family and on its template selectors, nothing decided here.
-// E: the storage type of x (and of out in LSM_BWD).  Map: the row -> cell policy (DenseMap, CompactMap).
-template <int MODE, typename E, class Map>
+// E: the storage type of x (and of out in LSM_BWD).  Map: the row -> cell policy (DenseMap, CompactMap).  CLAMP: the clamped
+// twins of the plan's kernel (LSM_BWD, whose plans name SMALL, LARGE or GENERIC).
+template <int MODE, typename E, bool CLAMP, class Map>
 static hipError_t launch_lsm_plan(hipStream_t stream, const LsmPlan& p, const E* x, LsmOut<MODE, E>* out, const Map& map,
                                   int64_t rows, int V, int blank, LsmBwd bw) {
     bw.xcd = p.xcd;
 #define LSM_LARGE(TH_, NV_) \
-    if (p.TH == TH_ && p.NV == NV_) launch_lsm_large<E, MODE, TH_, NV_>(p.grid, stream, x, out, map, rows, V, blank, bw);
+    if (p.TH == TH_ && p.NV == NV_) launch_lsm_large<E, MODE, TH_, NV_, CLAMP>(p.grid, stream, x, out, map, rows, V, blank, bw);
     switch (p.family) {
         case LsmFamily::REGS:
             if constexpr (MODE == LSM_NORM) {
@@ -703,9 +817,9 @@ static hipError_t launch_lsm_plan(hipStream_t stream, const LsmPlan& p, const E*
 #define LSM_SMALL(LL)                                                                                            \
     case LL:                                                                                                     \
         if (p.WP)                                                                                                \
-            launch_lsm_small<E, LL, MODE, (LL <= 16)>(p.grid, p.lds_bytes, stream, x, out, map, rows, V, p.R, p.q, blank, bw); \
+            launch_lsm_small<E, LL, MODE, (LL <= 16), CLAMP>(p.grid, p.lds_bytes, stream, x, out, map, rows, V, p.R, p.q, blank, bw); \
         else                                                                                                     \
-            launch_lsm_small<E, LL, MODE, false>(p.grid, p.lds_bytes, stream, x, out, map, rows, V, p.R, p.q, blank, bw);     \
+            launch_lsm_small<E, LL, MODE, false, CLAMP>(p.grid, p.lds_bytes, stream, x, out, map, rows, V, p.R, p.q, blank, bw);     \
         break;
             switch (p.L) {
                 LSM_SMALL(1) LSM_SMALL(2) LSM_SMALL(4) LSM_SMALL(8) LSM_SMALL(16) LSM_SMALL(32)
@@ -722,7 +836,7 @@ static hipError_t launch_lsm_plan(hipStream_t stream, const LsmPlan& p, const E*
             }
             break;
         case LsmFamily::GENERIC:
-            launch_lsm_generic<E, MODE>(p.grid, stream, x, out, map, rows, V, blank, bw);
+            launch_lsm_generic<E, MODE, CLAMP>(p.grid, stream, x, out, map, rows, V, blank, bw);
             break;
     }
 #undef LSM_LARGE
@@ -731,7 +845,7 @@ static hipError_t launch_lsm_plan(hipStream_t stream, const LsmPlan& p, const E*
 
 // Facts, knobs, plan, launch.  The register kernel takes whole groups of rows; what is left over is planned and launched
 // as a call of its own behind it (lsm_plan.h: never the register kernel again), with its slice of the plane.
-template <int MODE, typename E, class Map>
+template <int MODE, typename E, bool CLAMP = false, class Map>
 static hipError_t dispatch_lsm_map(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, Map map, int64_t rows, int V,
                                    int blank, LsmBwd bw) {
     if (rows <= 0) return hipSuccess;
@@ -741,25 +855,26 @@ static hipError_t dispatch_lsm_map(hipStream_t stream, const E* x, LsmOut<MODE, 
     if constexpr (!Map::COMPACT) { f.T = map.T; f.U = map.U; }
     const LsmKnobs& knobs = lsm_knobs();
     const LsmPlan head = plan_lsm(f, knobs);
-    const hipError_t e = launch_lsm_plan<MODE, E>(stream, head, x, out, map, rows, V, blank, bw);
+    static_assert(!CLAMP || MODE == LSM_BWD, "the clamp is the backward's");
+    const hipError_t e = launch_lsm_plan<MODE, E, CLAMP>(stream, head, x, out, map, rows, V, blank, bw);
     if (head.family != LsmFamily::REGS || e != hipSuccess || head.head_rows == rows) return e;
     const int64_t done = head.head_rows;
     f.rows = rows - done;
     if (bw.col_out) bw.col_out += done;
-    return launch_lsm_plan<MODE, E>(stream, plan_lsm(f, knobs), x + done * V, out + done * V, map, f.rows, V, blank, bw);
+    return launch_lsm_plan<MODE, E, CLAMP>(stream, plan_lsm(f, knobs), x + done * V, out + done * V, map, f.rows, V, blank, bw);
 }
 
-template <int MODE, typename E = float>
+template <int MODE, typename E = float, bool CLAMP = false>
 static hipError_t dispatch_lsm(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const int* labels,
                                int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
-    return dispatch_lsm_map<MODE, E>(stream, x, out, DenseMap{labels, T, U}, rows, V, blank, bw);
+    return dispatch_lsm_map<MODE, E, CLAMP>(stream, x, out, DenseMap{labels, T, U}, rows, V, blank, bw);
 }
 // compact rows (kernels.h: PackedRows) in the two fused modes
-template <int MODE, typename E>
+template <int MODE, typename E, bool CLAMP = false>
 static hipError_t dispatch_lsm_compact(hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const PackedRows& cr,
                                        int V, int blank, LsmBwd bw) {
     static_assert(MODE != LSM_NORM, "the plain log-softmax has no map");
-    return dispatch_lsm_map<MODE, E>(stream, x, out, CompactMap<MODE == LSM_GATHER>{cr, 0, 0}, cr.rows, V, blank, bw);
+    return dispatch_lsm_map<MODE, E, CLAMP>(stream, x, out, CompactMap<MODE == LSM_GATHER>{cr, 0, 0}, cr.rows, V, blank, bw);
 }
 
 // The operations of kernels.h at one storage type: each lsm_<type>.hip instantiates them, and through them the kernels
@@ -770,11 +885,12 @@ template <typename E> struct LsmOps {
                                         int col);
     static hipError_t gather(hipStream_t stream, const E* logits, const int* labels, float* ws2, int N, int T, int U, int V,
                              int blank);
+    // clamp > 0: the clamped twins (LsmBwd::clamp); 0: the kernels that have always been here
     static hipError_t backward(hipStream_t stream, const E* logits, const int* labels, const float* g2_diagonal,
-                               const float* scale, E* dlogits, int N, int T, int U, int V, int blank);
+                               const float* scale, E* dlogits, int N, int T, int U, int V, int blank, float clamp);
     static hipError_t gather_compact(hipStream_t stream, const E* logits, float* ws2, const PackedRows& cr, int V, int blank);
     static hipError_t backward_compact(hipStream_t stream, const E* logits, const float* g2_rowmajor, const float* scale,
-                                       E* dlogits, const PackedRows& cr, int V, int blank);
+                                       E* dlogits, const PackedRows& cr, int V, int blank, float clamp);
 };
 template <typename E>
 hipError_t LsmOps<E>::log_softmax(hipStream_t stream, const E* x, float* out, int64_t rows, int V) {
@@ -783,7 +899,7 @@ hipError_t LsmOps<E>::log_softmax(hipStream_t stream, const E* x, float* out, in
 template <typename E>
 hipError_t LsmOps<E>::log_softmax_plane(hipStream_t stream, const E* x, float* out, int64_t rows, int V, float* col_out,
                                         int col) {
-    return dispatch_lsm<LSM_NORM, E>(stream, x, out, nullptr, rows, V, 1, 1, 0, LsmBwd{nullptr, nullptr, 0, col_out, col});
+    return dispatch_lsm<LSM_NORM, E>(stream, x, out, nullptr, rows, V, 1, 1, 0, LsmBwd{nullptr, nullptr, 0, 0.0f, col_out, col});
 }
 template <typename E>
 hipError_t LsmOps<E>::gather(hipStream_t stream, const E* logits, const int* labels, float* ws2, int N, int T, int U, int V,
@@ -793,9 +909,11 @@ hipError_t LsmOps<E>::gather(hipStream_t stream, const E* logits, const int* lab
 }
 template <typename E>
 hipError_t LsmOps<E>::backward(hipStream_t stream, const E* logits, const int* labels, const float* g2_diagonal,
-                               const float* scale, E* dlogits, int N, int T, int U, int V, int blank) {
-    return dispatch_lsm<LSM_BWD, E>(stream, logits, dlogits, labels, (int64_t)N * T * U, V, T, U, blank,
-                                    LsmBwd{reinterpret_cast<const float2*>(g2_diagonal), scale});
+                               const float* scale, E* dlogits, int N, int T, int U, int V, int blank, float clamp) {
+    const LsmBwd bw{reinterpret_cast<const float2*>(g2_diagonal), scale, 0, clamp};
+    if (clamp > 0.0f)
+        return dispatch_lsm<LSM_BWD, E, true>(stream, logits, dlogits, labels, (int64_t)N * T * U, V, T, U, blank, bw);
+    return dispatch_lsm<LSM_BWD, E>(stream, logits, dlogits, labels, (int64_t)N * T * U, V, T, U, blank, bw);
 }
 template <typename E>
 hipError_t LsmOps<E>::gather_compact(hipStream_t stream, const E* logits, float* ws2, const PackedRows& cr, int V,
@@ -804,9 +922,10 @@ hipError_t LsmOps<E>::gather_compact(hipStream_t stream, const E* logits, float*
 }
 template <typename E>
 hipError_t LsmOps<E>::backward_compact(hipStream_t stream, const E* logits, const float* g2_rowmajor, const float* scale,
-                                       E* dlogits, const PackedRows& cr, int V, int blank) {
-    return dispatch_lsm_compact<LSM_BWD, E>(stream, logits, dlogits, cr, V, blank,
-                                            LsmBwd{reinterpret_cast<const float2*>(g2_rowmajor), scale});
+                                       E* dlogits, const PackedRows& cr, int V, int blank, float clamp) {
+    const LsmBwd bw{reinterpret_cast<const float2*>(g2_rowmajor), scale, 0, clamp};
+    if (clamp > 0.0f) return dispatch_lsm_compact<LSM_BWD, E, true>(stream, logits, dlogits, cr, V, blank, bw);
+    return dispatch_lsm_compact<LSM_BWD, E>(stream, logits, dlogits, cr, V, blank, bw);
 }
 extern template struct LsmOps<float>;
 extern template struct LsmOps<__bf16>;

@@ -23,12 +23,14 @@
         const CellMap m = map.at((size_t)row, V, blank);
         const float sc = map.scale(bw, m);
         const float2 g = map.pair(bw, m);
-        const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
+        // CLAMP: the pair stays unscaled -- the row is clamped behind the two additions and scaled behind the clamp
+        const float gB = CLAMP ? g.x : g.x * sc, gL = CLAMP ? g.y : g.y * sc, gs = gB + gL;
         LsmOut<MODE, E>* o = out + row * V;
         for (int c = lane; c < V; c += WAVE) {
             float d = -expf((lsm_ld1(xr + c) - mx) - ls) * gs;
             d += (c == blank) ? gB : 0.0f;
             d += (c == m.label) ? gL : 0.0f;
+            if constexpr (CLAMP) d = lsm_clamp_scale(d, bw.clamp, sc);
             lsm_st1(o + c, d);
         }
     } else {

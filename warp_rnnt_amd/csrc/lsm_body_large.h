@@ -84,7 +84,8 @@
         if (threadIdx.x == 0) map.put(out, m, make_float2((side.x - mx) - ls, (side.y - mx) - ls));
     } else if constexpr (MODE == LSM_BWD) {
         const float2 g = side;
-        const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
+        // CLAMP: the pair stays unscaled -- the row is clamped behind the two additions and scaled behind the clamp
+        const float gB = CLAMP ? g.x : g.x * sc, gL = CLAMP ? g.y : g.y * sc, gs = gB + gL;
         const float gq = gs / s;                                 // p_j = e_j / s (lsm_log_sum)
         LsmOut<MODE, E>* dst = out + row * V;
 #pragma unroll
@@ -98,6 +99,7 @@
                     float d = -__builtin_amdgcn_exp2f(__builtin_fmaf(o[cc], LOG2E, mb)) * gq;
                     d += (e == blank) ? gB : 0.0f;
                     d += (e == m.label) ? gL : 0.0f;
+                    if constexpr (CLAMP) d = lsm_clamp_scale(d, bw.clamp, sc);
                     o[cc] = d;
                 }
                 lsm_st4<true>(dst, j, make_float4(o[0], o[1], o[2], o[3]));

@@ -101,6 +101,21 @@
             const CellMap m = first ? pm : map.at((size_t)(row0 + r), V, blank);
             const float sc = first ? psc : map.scale(bw, m);
             const float2 g = first ? pg : map.pair(bw, m);
+            if constexpr (CLAMP) {
+                // the clamp behind the sum and in front of the scale: the pair stays unscaled, every lane clamps and scales
+                // what it writes, and lane 0 forms the two one-hot entries whole -- from the logits still in the tile --
+                // and puts them over the row's behind the row pass (lsm_hot_clamped)
+                const float gB = g.x, gL = g.y, gs = gB + gL;
+                const float gq = gs * __builtin_amdgcn_rcpf(s);
+                float hb = 0.0f, hl = 0.0f;
+                if (h == 0) lsm_hot_clamped(row[blank], row[m.label], m.label == blank, mb, gq, gB, gL, bw.clamp, sc, hb, hl);
+#pragma unroll
+                for (int i = 0; i < Q - 1; ++i)
+                    row[h + i * L] = lsm_clamp(-__builtin_amdgcn_exp2f(__builtin_fmaf(v[i], LOG2E, mb)) * gq, bw.clamp) * sc;
+                if (tail_ok)
+                    row[ctail] = lsm_clamp(-__builtin_amdgcn_exp2f(__builtin_fmaf(v[Q - 1], LOG2E, mb)) * gq, bw.clamp) * sc;
+                if (h == 0) { row[blank] = hb; row[m.label] = hl; }
+            } else {
             const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
             const float gq = gs * __builtin_amdgcn_rcpf(s);      // p_j = e_j / s (lsm_log_sum)
 #pragma unroll
@@ -109,6 +124,7 @@
             if (tail_ok) row[ctail] = -__builtin_amdgcn_exp2f(__builtin_fmaf(v[Q - 1], LOG2E, mb)) * gq;
             // the L lanes of a row sit in one wave and LDS operations of a wave retire in order
             if (h == 0) { row[blank] += gB; row[m.label] += gL; }
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < Q - 1; ++i) row[h + i * L] = (v[i] - mx) - ls;
@@ -141,6 +157,17 @@
             const CellMap m = map.at((size_t)(row0 + r), V, blank);
             const float sc = map.scale(bw, m);
             const float2 g = map.pair(bw, m);
+            if constexpr (CLAMP) {       // (as in the straight-line form above)
+                const float gB = g.x, gL = g.y, gs = gB + gL;
+                const float gq = gs * __builtin_amdgcn_rcpf(s);
+                float hb = 0.0f, hl = 0.0f;
+                if (h == 0) lsm_hot_clamped(row[blank], row[m.label], m.label == blank, mb, gq, gB, gL, bw.clamp, sc, hb, hl);
+                for (int i = 0, c = h; i < q - 1; ++i, c += L)
+                    row[c] = lsm_clamp(-__builtin_amdgcn_exp2f(__builtin_fmaf(row[c], LOG2E, mb)) * gq, bw.clamp) * sc;
+                if (tail_ok)
+                    row[ctail] = lsm_clamp(-__builtin_amdgcn_exp2f(__builtin_fmaf(row[ctail], LOG2E, mb)) * gq, bw.clamp) * sc;
+                if (h == 0) { row[blank] = hb; row[m.label] = hl; }
+            } else {
             const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
             const float gq = gs * __builtin_amdgcn_rcpf(s);      // p_j = e_j / s (lsm_log_sum)
             for (int i = 0, c = h; i < q - 1; ++i, c += L)
@@ -148,6 +175,7 @@
             if (tail_ok) row[ctail] = -__builtin_amdgcn_exp2f(__builtin_fmaf(row[ctail], LOG2E, mb)) * gq;
             // the L lanes of a row sit in one wave and LDS operations of a wave retire in order
             if (h == 0) { row[blank] += gB; row[m.label] += gL; }
+            }
         } else {
             for (int i = 0, c = h; i < q - 1; ++i, c += L) row[c] = (row[c] - mx) - ls;
             if (tail_ok) row[ctail] = (row[ctail] - mx) - ls;

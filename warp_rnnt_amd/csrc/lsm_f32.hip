@@ -84,11 +84,11 @@ hipError_t launch_log_softmax_gather_skewed(hipStream_t stream, int dtype, const
 
 hipError_t launch_logits_backward(hipStream_t stream, int dtype, const void* logits, const int* labels,
                                   const float* g2_diagonal, const float* scale, void* dlogits, int N, int T, int U, int V,
-                                  int blank) {
+                                  int blank, float clamp) {
     return with_logits_type(dtype, [&](auto* e) {
         using E = std::remove_pointer_t<decltype(e)>;
         return LsmOps<E>::backward(stream, static_cast<const E*>(logits), labels, g2_diagonal, scale,
-                                   static_cast<E*>(dlogits), N, T, U, V, blank);
+                                   static_cast<E*>(dlogits), N, T, U, V, blank, clamp);
     });
 }
 
@@ -101,11 +101,12 @@ hipError_t launch_lsm_gather_compact(hipStream_t stream, int dtype, const void* 
 }
 
 hipError_t launch_logits_backward_compact(hipStream_t stream, int dtype, const void* logits, const float* g2_rowmajor,
-                                          const float* scale, void* dlogits, const PackedRows& cr, int V, int blank) {
+                                          const float* scale, void* dlogits, const PackedRows& cr, int V, int blank,
+                                          float clamp) {
     return with_logits_type(dtype, [&](auto* e) {
         using E = std::remove_pointer_t<decltype(e)>;
         return LsmOps<E>::backward_compact(stream, static_cast<const E*>(logits), g2_rowmajor, scale,
-                                           static_cast<E*>(dlogits), cr, V, blank);
+                                           static_cast<E*>(dlogits), cr, V, blank, clamp);
     });
 }
 

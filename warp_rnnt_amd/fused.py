@@ -29,19 +29,20 @@ def check_logits_inputs(xs, ys, xn, yn):
 class RNNTLossFromLogits(torch.autograd.Function):
 
     @staticmethod
-    def forward(ctx, logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
+    def forward(ctx, logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0, clamp=0.0):
         check_logits_inputs(logits, labels, frames_lengths, labels_lengths)
         costs, grads = ops.loss(logits, labels, frames_lengths, labels_lengths, ops.IN_LOGITS_DENSE,
                                 ops.GRADS_GATHERED_DIAGONAL, blank, fastemit_lambda)
         ctx.save_for_backward(logits, labels, grads)
         ctx.blank = blank
+        ctx.clamp = clamp
         return costs
 
     @staticmethod
     def backward(ctx, grads_output):
         logits, labels, grads = ctx.saved_tensors
         go = grads_output.reshape(-1).to(torch.float32).contiguous()
-        return ops.logits_backward(logits, labels, grads, go, ctx.blank), None, None, None, None, None
+        return (ops.logits_backward(logits, labels, grads, go, ctx.blank, clamp=ctx.clamp),) + (None,) * 6
 
 
 def check_compact_logits_inputs(xs, ys, xn, yn):
@@ -66,12 +67,13 @@ class RNNTLossCompactFromLogits(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0,
-                enable_grad: bool = True, max_frames=None, max_labels=None):
+                enable_grad: bool = True, max_frames=None, max_labels=None, clamp=0.0):
         costs, grads, offs, loffs = ops.loss_compact_logits(logits, labels, frames_lengths, labels_lengths, blank,
                                                             fastemit_lambda, enable_grad, max_frames, max_labels)
         if enable_grad:
             ctx.save_for_backward(logits, labels, frames_lengths, labels_lengths, offs, loffs, grads)
         ctx.blank = blank
+        ctx.clamp = clamp
         return costs
 
     @staticmethod
@@ -79,33 +81,42 @@ class RNNTLossCompactFromLogits(torch.autograd.Function):
         logits, labels, xn, yn, offs, loffs, grads = ctx.saved_tensors
         _mismatch.poll(grads.device)
         go = grads_output.reshape(-1).to(torch.float32).contiguous()
-        dlogits = ops.compact_logits_backward(logits, labels, xn, yn, offs, loffs, grads, go, ctx.blank)
-        return (dlogits,) + (None,) * 8
+        dlogits = ops.compact_logits_backward(logits, labels, xn, yn, offs, loffs, grads, go, ctx.blank, clamp=ctx.clamp)
+        return (dlogits,) + (None,) * 9
 
 
 def rnnt_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, frames_lengths: torch.Tensor,
                           labels_lengths: torch.Tensor, average_frames: bool = False,
                           reduction: Optional[str] = "none", blank: int = 0,
                           fastemit_lambda: float = 0.0, compact: bool = False,
-                          max_frames: Optional[int] = None, max_labels: Optional[int] = None) -> torch.Tensor:
+                          max_frames: Optional[int] = None, max_labels: Optional[int] = None,
+                          clamp: float = 0.0) -> torch.Tensor:
     """Same value and gradients as ``warp_rnnt.rnnt_loss(F.log_softmax(logits, -1), ..., gather=True)``
     (arguments as there), without materialising the log-probabilities.
 
     ``compact=True``: the ragged packed layout of ``rnnt_loss(compact=True)`` -- logits ``(sum_n T_n*(U_n+1), V)``,
     labels ``(sum_n U_n,)`` -- with that call's checks and ``max_frames`` / ``max_labels`` (launch bounds: no host
     synchronisation, capturable; a batch that does not fit comes back with NaN costs and zero gradients).  Without them
-    one host synchronisation.  The log-probabilities and their (STU,V) gradient never exist."""
+    one host synchronisation.  The log-probabilities and their (STU,V) gradient never exist.
+
+    ``clamp`` > 0: the gradient clamp of torchaudio's and warp-transducer's rnnt_loss -- d/d logits of every utterance's
+    cost are limited to [-clamp, +clamp] elementwise and only then multiplied by the upstream gradient (which carries the
+    ``reduction`` and ``average_frames``).  It sits inside the backward kernel (the unscaled gradient never exists in
+    memory); the costs do not depend on it.  0.0: no clamp, the kernels and bits there have always been."""
     assert reduction is None or reduction in ("none", "mean", "sum")
     assert isinstance(blank, int)
+    clamp = float(clamp)
+    if not 0.0 <= clamp < float("inf"):
+        raise ValueError(f"clamp must be a finite number >= 0 (0 = off), not {clamp}")
     if not compact and (max_frames is not None or max_labels is not None):
         raise ValueError("max_frames / max_labels are launch bounds of the compact layout: pass compact=True with them")
     if compact:
         check_compact_logits_inputs(logits, labels, frames_lengths, labels_lengths)
         wants_grad = logits.requires_grad and torch.is_grad_enabled()
         costs = RNNTLossCompactFromLogits.apply(logits, labels, frames_lengths, labels_lengths, blank, fastemit_lambda,
-                                                wants_grad, max_frames, max_labels)
+                                                wants_grad, max_frames, max_labels, clamp)
     else:
-        costs = RNNTLossFromLogits.apply(logits, labels, frames_lengths, labels_lengths, blank, fastemit_lambda)
+        costs = RNNTLossFromLogits.apply(logits, labels, frames_lengths, labels_lengths, blank, fastemit_lambda, clamp)
     if average_frames:
         costs = costs / frames_lengths.to(costs)      # (fp32 costs: T_n rounded to bf16 would be 1499 -> 1496)
     if reduction == "none" or reduction is None:

@@ -381,9 +381,11 @@ def loss_compact_logits(logits, ys, xn, yn, blank=0, fastemit_lambda=0.0, requir
     return costs, grads, offs[:N + 1], loffs
 
 
-def compact_logits_backward(logits, ys, xn, yn, cell_offsets, label_offsets, grads, grad_costs, blank=0, out=None):
+def compact_logits_backward(logits, ys, xn, yn, cell_offsets, label_offsets, grads, grad_costs, blank=0, out=None,
+                            clamp=0.0):
     """d(sum_n grad_costs[n]*cost[n]) / d(logits) (STU,V) for the compact fused path, in the logits' dtype; grads and the
-    offsets are those :func:`loss_compact_logits` returned.  Rows that belong to no utterance come back zero."""
+    offsets are those :func:`loss_compact_logits` returned.  Rows that belong to no utterance come back zero.
+    ``clamp`` > 0: as in :func:`logits_backward`."""
     L = _lib.load()
     STU, V = logits.shape
     N = xn.shape[0]
@@ -396,10 +398,13 @@ def compact_logits_backward(logits, ys, xn, yn, cell_offsets, label_offsets, gra
         _drop_plane(out)
         if STU == 0:
             return out
-        _check(L.rnnt_amd_compact_logits_backward(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
-                                                  _ptr(ys), ys.numel(), xn.data_ptr(), yn.data_ptr(),
-                                                  cell_offsets.data_ptr(), label_offsets.data_ptr(), grads.data_ptr(),
-                                                  _ptr(grad_costs), out.data_ptr(), N, STU, V, blank))
+        args = (_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(), _ptr(ys), ys.numel(), xn.data_ptr(),
+                yn.data_ptr(), cell_offsets.data_ptr(), label_offsets.data_ptr(), grads.data_ptr(), _ptr(grad_costs),
+                out.data_ptr(), N, STU, V, blank)
+        if clamp == 0.0:
+            _check(L.rnnt_amd_compact_logits_backward(*args))
+        else:
+            _check(L.rnnt_amd_compact_logits_backward_clamped(*args, float(clamp)))
     return out
 
 
@@ -419,9 +424,11 @@ def compact_scatter_grads(grad_cost, grad_xs, cum_lens, loc, V, blank):
     return out
 
 
-def logits_backward(logits, labels, grads_diagonal, grad_costs, blank=0, out=None):
+def logits_backward(logits, labels, grads_diagonal, grad_costs, blank=0, out=None, clamp=0.0):
     """d(sum_n grad_costs[n]*cost[n]) / d(logits) for the fused RNNT_IN_LOGITS_DENSE path, in the logits' dtype (fp32,
-    bf16 or fp16: the fp32 result rounded once)."""
+    bf16 or fp16: the fp32 result rounded once).  ``clamp`` > 0: the gradient of every cost is limited to
+    [-clamp, +clamp] elementwise BEFORE it is multiplied by grad_costs (the clamp of torchaudio and warp-transducer;
+    include/warp_rnnt_amd_clamp.h); 0.0 calls the unclamped entries."""
     L = _lib.load()
     N, T, U, V = logits.shape
     dev = logits.device
@@ -431,7 +438,13 @@ def logits_backward(logits, labels, grads_diagonal, grad_costs, blank=0, out=Non
         _drop_plane(out)
         if N == 0:
             return out
-        if _half(logits):
+        if clamp != 0.0:
+            if out.dtype != logits.dtype:
+                raise RuntimeError("logits_backward: out must have the logits' dtype")
+            _check(L.rnnt_amd_logits_backward_clamped(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
+                                                      _ptr(labels), grads_diagonal.data_ptr(), _ptr(grad_costs),
+                                                      out.data_ptr(), N, T, U, V, blank, float(clamp)))
+        elif _half(logits):
             if out.dtype != logits.dtype:
                 raise RuntimeError("logits_backward: out must have the logits' dtype")
             _check(L.rnnt_amd_logits_backward_typed(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
