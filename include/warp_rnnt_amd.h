@@ -334,11 +334,15 @@ rnntStatus_t rnnt_amd_compact_logits_backward(rnntStream_t stream, int dtype, co
  * are NULL f / g / weight / xn / yn / costs / workspace, NULL labels while U > 1, a misaligned pointer, an unknown
  * dtype or activation.
  * rnnt_amd_joint_workspace_size: bytes of the workspace (256-byte aligned) either call needs; 0 for a refused size.
- * rnnt_amd_joint_loss: costs (N,) always; with grads != NULL also lse (N,T,U) fp32, the log-normaliser of every cell, and
- * grads (N,T,U,2) in the RNNT_GRADS_GATHERED_DIAGONAL layout (lse must then be non-NULL).
+ * rnnt_amd_joint_loss: costs (N,) always; with grads != NULL also lse (N,T,U,2) fp32, 8-byte aligned -- the log-normaliser
+ * of every cell in two parts, (max_v z, log sum_v exp(z - max)), since version 110 (107-109: one float per cell, (N,T,U);
+ * their sum rounds at ulp(max), which a log-softmax under a large common offset of its logits does not survive) -- and
+ * grads (N,T,U,2) in the RNNT_GRADS_GATHERED_DIAGONAL layout (lse must then be non-NULL).  The buffer is opaque: hand it
+ * to rnnt_amd_joint_backward as it is.  Logits of -inf (bias[v] = -inf masks entry v) get probability and gradient
+ * exactly 0; a cell needs one finite logit, and +inf, NaN, -inf on the blank or on a label in use are not supported.
  * rnnt_amd_joint_backward: d(sum_n grad_costs[n]*cost[n]) (grad_costs NULL = 1) with respect to f -> df (N,T,H), g ->
  * dg (N,U,H) (both of type `dtype`, rounded once from fp32; rows t >= xn[n] / u > yn[n] are zero), weight -> dweight
- * (V,H) fp32 and bias -> dbias (V,) fp32, from the lse and grads of the forward; any output may be NULL (not computed).
+ * (V,H) fp32 and bias -> dbias (V,) fp32, from the lse (N,T,U,2) and grads of the forward; any output may be NULL (not computed).
  * Both calls only enqueue work: nothing is read back, both can be captured into a HIP graph.  Each bit of the results
  * is a function of the inputs and the shape: df / dg rows and costs of an utterance do not depend on the batch around it.
  */

@@ -1,5 +1,5 @@
-/* Gradient clamp on the fused logits path: additive entries of libwarp_rnnt_amd.so (C-ABI version 109, unchanged --
- * nothing that was there moves).
+/* Gradient clamp on the fused logits path: additive entries of libwarp_rnnt_amd.so (they did not move the C-ABI
+ * version -- nothing that was there moves).
  *
  * torchaudio.functional.rnnt_loss and warp-transducer's RNNTLoss take logits and a `clamp`: the d/d logits of every
  * utterance are limited to [-clamp, +clamp] elementwise and only THEN multiplied by the upstream gradient.  On the fused

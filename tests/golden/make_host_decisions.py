@@ -159,12 +159,13 @@ ENTRIES = {
     "rnnt_amd_joint_loss": entry(
         "stream workspace dtype activation f g weight bias labels xn yn costs lse grads N T U H V blank fastemit_lambda",
         dict(JOINT_IN, costs=P, lse=P, grads=P, fastemit_lambda=0.0),
-        BAD_JOINT + [dict(costs=0), dict(lse=0), dict(N=0, workspace=0)],
+        BAD_JOINT + [dict(costs=0), dict(lse=0), dict(N=0, workspace=0), dict(lse=P + 4)],
         [dict(N=0), dict(N=0, dtype=2, activation=1, bias=0, lse=0, grads=0)]),
     "rnnt_amd_joint_backward": entry(
         "stream workspace dtype activation f g weight bias labels xn yn lse grads grad_costs df dg dweight dbias N T U H V blank",
         dict(JOINT_IN, lse=P, grads=P, grad_costs=P, df=P, dg=P, dweight=P, dbias=P),
-        BAD_JOINT + [dict(lse=0), dict(grads=0), dict(grads=P + 4), dict(df=0, dg=0, dweight=0, dbias=0, workspace=P + 8)],
+        BAD_JOINT + [dict(lse=0), dict(grads=0), dict(grads=P + 4), dict(df=0, dg=0, dweight=0, dbias=0, workspace=P + 8),
+                     dict(lse=P + 4)],
         [dict(N=0), dict(df=0, dg=0, dweight=0, dbias=0), dict(df=0, dg=0, dweight=0, dbias=0, bias=0, grad_costs=0, dtype=1)]),
     "rnnt_amd_debug_lattice_only": entry("stream workspace xn yn N T U", dict(stream=0, workspace=P, xn=P, yn=P, **DIMS),
                                          BAD_DIMS + [dict(workspace=0)], []),

@@ -58,7 +58,7 @@ def test_clamp_header_declares_what_the_table_binds_and_the_library_exports():
 
 def test_clamp_entries_do_not_move_the_abi_version():
     from warp_rnnt_amd import _lib as lib
-    assert _lib().rnnt_amd_version() == lib.ABI_VERSION == 109
+    assert _lib().rnnt_amd_version() == lib.ABI_VERSION == 110
 
 
 def test_library_without_the_clamp_entries_is_refused_with_the_rebuild_message(monkeypatch):

@@ -21,7 +21,7 @@ def _lib():
 def test_compact_logits_entries_exported_and_declared():
     from warp_rnnt_amd import _lib as lib
     L = _lib()
-    assert L.rnnt_amd_version() == 109
+    assert L.rnnt_amd_version() == 110
     hdr = open(os.path.join(ROOT, "include", "warp_rnnt_amd.h")).read().replace(" (", "(")
     syms = subprocess.check_output(["nm", "-D", "--defined-only", lib.lib_path()]).decode()
     for name in NEW:

@@ -21,7 +21,7 @@ def test_typed_entries_exported_and_version():
     import subprocess
     from warp_rnnt_amd import _lib as lib
     L = _lib()
-    assert L.rnnt_amd_version() == 109 == lib.ABI_VERSION
+    assert L.rnnt_amd_version() == 110 == lib.ABI_VERSION
     hdr = open(os.path.join(ROOT, "include", "warp_rnnt_amd.h")).read()
     syms = subprocess.check_output(["nm", "-D", "--defined-only", lib.lib_path()]).decode()
     for name in NEW:

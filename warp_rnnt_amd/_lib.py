@@ -78,15 +78,15 @@ SYMBOLS = {
 }
 
 
-# every symbol include/warp_rnnt_amd_clamp.h declares (the gradient clamp of the fused backward; additive, version 109
-# still): the arguments of the unclamped twin and a float clamp behind them
+# every symbol include/warp_rnnt_amd_clamp.h declares (the gradient clamp of the fused backward; additive: it did not
+# move the version): the arguments of the unclamped twin and a float clamp behind them
 CLAMP_SYMBOLS = {
     "rnnt_amd_logits_backward_clamped": (_i, SYMBOLS["rnnt_amd_logits_backward_typed"][1] + [_f]),
     "rnnt_amd_compact_logits_backward_clamped": (_i, SYMBOLS["rnnt_amd_compact_logits_backward"][1] + [_f]),
 }
 
 
-ABI_VERSION = 109   # rnnt_amd_version() of the library these argument lists belong to
+ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
 
 
 class RNNTStatusError(RuntimeError):

@@ -122,7 +122,7 @@ rnntStatus_t grads_in_place_then_split(rnntStream_t stream, float* grads, const 
 
 extern "C" {
 
-int rnnt_amd_version(void) { return 109; }
+int rnnt_amd_version(void) { return 110; }
 
 int rnnt_amd_debug_set_lattice_kernel(int kernel) { return set_lattice_kernel_override(kernel); }
 
@@ -787,12 +787,12 @@ rnntStatus_t rnnt_amd_joint_loss(rnntStream_t stream, void* workspace, int dtype
     if (!joint_args_ok(dtype, activation, N, T, U, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (!workspace_ok(workspace) || !f || !g || !weight || !xn || !yn || !costs || (U > 1 && !labels) || (grads && !lse))
         return RNNT_STATUS_INVALID_ARGUMENT;
-    if (!joint_inputs_aligned(f, g, weight, bias)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!joint_inputs_aligned(f, g, weight, bias) || !aligned(lse, 8)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (N == 0) return RNNT_STATUS_SUCCESS;
     Workspace w;
     carve(workspace, N, T, U, &w);
     // 1. z tile by tile: the (blank,label) log-prob pairs into the pair plane (launch_log_softmax_gather_skewed's
-    //    layout), lse per cell
+    //    layout), (max, log sum) per cell
     if (launch_joint_fwd(stream, dtype, activation, f, g, weight, bias, labels, xn, yn, w.ws2, grads ? lse : nullptr, N,
                          T, U, H, V, blank) != hipSuccess)
         return RNNT_STATUS_PROLOGUE_FAILED;
@@ -809,7 +809,8 @@ rnntStatus_t rnnt_amd_joint_backward(rnntStream_t stream, void* workspace, int d
     if (!joint_args_ok(dtype, activation, N, T, U, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (!workspace_ok(workspace) || !f || !g || !weight || !xn || !yn || !lse || !grads || (U > 1 && !labels))
         return RNNT_STATUS_INVALID_ARGUMENT;
-    if (!joint_inputs_aligned(f, g, weight, bias) || !aligned(grads, 8)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!joint_inputs_aligned(f, g, weight, bias) || !aligned(grads, 8) || !aligned(lse, 8))
+        return RNNT_STATUS_INVALID_ARGUMENT;
     if (N == 0 || (!df && !dg && !dweight && !dbias)) return RNNT_STATUS_SUCCESS;
     JointWorkspace jw;
     carve_joint(workspace, N, T, U, H, V, &jw);

@@ -79,7 +79,7 @@ struct JointArgs {
     const float2* g2;     // diagonal-major gradient pairs (backward)
     const float* scale;   // (N,) upstream gradient or nullptr (backward)
     float2* pairs;        // diagonal-major log-prob pairs (forward)
-    float* lse;           // (N,T,U) log-normaliser per cell
+    float2* lse;          // (N,T,U) per cell: (max of the logits, log of the sum of exp(z - max)) -- see k_joint_fwd
     int N, T, U, H, V, Vp, blank, wpg;
 };
 
@@ -138,7 +138,11 @@ __device__ __forceinline__ int label_of(const JointArgs& a, int n, int u) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Forward: 4 frames x 4 labels per wave; online max / sum of exponentials per cell, (blank, label) log-probs into the
-// diagonal-major pair plane at launch_log_softmax_gather_skewed's addresses, lse per cell.
+// diagonal-major pair plane at launch_log_softmax_gather_skewed's addresses, (mall, log sc) per cell.
+// The log-normaliser is never formed as ONE float: mall + log sc rounds at ulp(mall) (4e-3 at a bias of 60000), and a
+// log-softmax must not change under a shift of its row.  Log-probs are (z - mall) - log sc, the backward's exponent the
+// same.  A logit of -inf (a masked vocabulary entry) contributes nothing to max or sum, also
+// when it comes before the first finite one; a row needs one finite logit.
 // ---------------------------------------------------------------------------------------------------------------------
 template <typename E, int ACT>
 __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_fwd(JointArgs a) {
@@ -155,7 +159,7 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_fwd(JointArgs a) {
     const int t = t0 + (c >> 2), u = u0 + (c & 3);
     const bool in_grid = t < a.T && u < a.U, live = t < len.Tn && u < len.Un;
     float2 pair = make_float2(0.0f, 0.0f);
-    float lse = 0.0f;
+    float2 lse = make_float2(0.0f, 0.0f);
     if (t0 < len.Tn && u0 < len.Un) {
         E* hs = reinterpret_cast<E*>(j_lds) + (size_t)wave * 16 * hs_pitch<E>(a.H);
         stage_h<E, ACT>(a, n, hs, [&](int cc, int& ct, int& cu) { ct = t0 + (cc >> 2); cu = u0 + (cc & 3); }, len.Tn,
@@ -169,7 +173,7 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_fwd(JointArgs a) {
                 const int v = v0 + 4 * q + i;
                 if (v < a.V) {
                     const float z = acc[i] + (a.bias ? a.bias[v] : 0.0f);
-                    if (z > m) { s = s * expf(m - z) + 1.0f; m = z; } else { s += expf(z - m); }
+                    if (z > m) { s = s * expf(m - z) + 1.0f; m = z; } else if (z > -INFINITY) { s += expf(z - m); }
                     if (v == a.blank) zb = z;
                     if (v == lab) zl = z;
                 }
@@ -188,9 +192,11 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_fwd(JointArgs a) {
         xb += __shfl_xor(xb, 32, WAVE);
         xl += __shfl_xor(xl, 16, WAVE);
         xl += __shfl_xor(xl, 32, WAVE);
-        lse = mall + logf(sc);
-        if (live) pair = make_float2(xb - lse, xl - lse);
-        else lse = 0.0f;
+        const float logsc = logf(sc);
+        if (live) {
+            pair = make_float2((xb - mall) - logsc, (xl - mall) - logsc);
+            lse = make_float2(mall, logsc);
+        }
     }
     if (q == 0 && in_grid) {
         int d = t + u;
@@ -200,16 +206,20 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_fwd(JointArgs a) {
     }
 }
 
+// The softmax probability of a logit z of a cell whose forward stored (mall, log sc): exp((z - mall) - log sc).  z - mall is
+// formed first and alone: mall + log sc in one float would round at ulp(mall).  z = -inf gives exactly 0.
+__device__ __forceinline__ float cell_prob(float z, float mall, float logsc) { return expf((z - mall) - logsc); }
+
 // dz of the 16x16 block `z` (rows v0 + 4q + i, column = this lane's cell): the LSM_BWD formula of lsm.h.
-__device__ __forceinline__ jf4 dz_block(const JointArgs& a, jf4 z, int v0, int q, bool live, float lse, float gB,
-                                        float gL, int lab) {
+__device__ __forceinline__ jf4 dz_block(const JointArgs& a, jf4 z, int v0, int q, bool live, float mall, float logsc,
+                                        float gB, float gL, int lab) {
     jf4 d;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int v = v0 + 4 * q + i;
         float x = 0.0f;
         if (live && v < a.V) {
-            const float p = expf(z[i] + (a.bias ? a.bias[v] : 0.0f) - lse);
+            const float p = cell_prob(z[i] + (a.bias ? a.bias[v] : 0.0f), mall, logsc);
             x = (v == a.blank ? gB : 0.0f) + (v == lab ? gL : 0.0f) - p * (gB + gL);
         }
         d[i] = x;
@@ -219,11 +229,11 @@ __device__ __forceinline__ jf4 dz_block(const JointArgs& a, jf4 z, int v0, int q
 
 struct CellGrad {
     bool live;
-    float lse, gB, gL;
+    float mall, logsc, gB, gL;   // (the forward's pair: cell_prob)
     int lab;
 };
 __device__ __forceinline__ CellGrad cell_grad(const JointArgs& a, int n, int t, int u, const UttLens& len) {
-    CellGrad cg{t < len.Tn && u < len.Un, 0.0f, 0.0f, 0.0f, a.blank};
+    CellGrad cg{t < len.Tn && u < len.Un, 0.0f, 0.0f, 0.0f, 0.0f, a.blank};
     if (cg.live) {
         const float s = a.scale ? a.scale[n] : 1.0f;
         int d = t + u;
@@ -231,7 +241,9 @@ __device__ __forceinline__ CellGrad cell_grad(const JointArgs& a, int n, int t, 
         const float2 p = a.g2[((size_t)n * a.T + d) * a.U + u];
         cg.gB = p.x * s;
         cg.gL = p.y * s;
-        cg.lse = a.lse[((size_t)n * a.T + t) * a.U + u];
+        const float2 ml = a.lse[((size_t)n * a.T + t) * a.U + u];
+        cg.mall = ml.x;
+        cg.logsc = ml.y;
         cg.lab = label_of(a, n, u);
     }
     return cg;
@@ -279,7 +291,7 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_fg(JointArgs a, E* 
 #pragma unroll
                 for (int zb = 0; zb < ZB<E>; ++zb) {
                     const jf4 z = z_block<E, false>(a, hs, 0, v0 + 16 * zb, lane);
-                    dz[zb] = dz_block(a, z, v0 + 16 * zb, q, cg.live, cg.lse, cg.gB, cg.gL, cg.lab);
+                    dz[zb] = dz_block(a, z, v0 + 16 * zb, q, cg.live, cg.mall, cg.logsc, cg.gB, cg.gL, cg.lab);
                 }
                 const jfrag_t<E> adz = pack_acc<E>(dz);
 #pragma unroll
@@ -357,7 +369,7 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_w(JointArgs a, int 
                 n = (int)(fr / a.T);
                 len = utt_lens<false>(a.xn, a.yn, n, a.T, a.U);
             }
-            cgs[zb] = cell < cells ? cell_grad(a, n, t, u, len) : CellGrad{false, 0.0f, 0.0f, 0.0f, a.blank};
+            cgs[zb] = cell < cells ? cell_grad(a, n, t, u, len) : CellGrad{false, 0.0f, 0.0f, 0.0f, 0.0f, a.blank};
             frow[zb] = (size_t)n * a.T + t;
             grow[zb] = (size_t)n * a.U + u;
             any |= cgs[zb].live;
@@ -400,13 +412,13 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_w(JointArgs a, int 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int src = 4 * q + r;
-                const float lse = __shfl(cgs[zb].lse, src, WAVE), gB = __shfl(cgs[zb].gB, src, WAVE);
-                const float gL = __shfl(cgs[zb].gL, src, WAVE);
+                const float mall = __shfl(cgs[zb].mall, src, WAVE), logsc = __shfl(cgs[zb].logsc, src, WAVE);
+                const float gB = __shfl(cgs[zb].gB, src, WAVE), gL = __shfl(cgs[zb].gL, src, WAVE);
                 const int lab = __shfl(cgs[zb].lab, src, WAVE);
                 const bool live = __shfl((int)cgs[zb].live, src, WAVE) != 0;
                 float x = 0.0f;
                 if (live && v < a.V) {
-                    const float p = expf(z[r] + (a.bias ? a.bias[v] : 0.0f) - lse);
+                    const float p = cell_prob(z[r] + (a.bias ? a.bias[v] : 0.0f), mall, logsc);
                     x = (v == a.blank ? gB : 0.0f) + (v == lab ? gL : 0.0f) - p * (gB + gL);
                 }
                 dz[zb][r] = x;
@@ -534,8 +546,8 @@ int joint_w_splits(int N, int T, int U, int H, int V, int dtype) {
 hipError_t launch_joint_fwd(hipStream_t stream, int dtype, int act, const void* f, const void* g, const void* w,
                             const float* bias, const int* labels, const int* xn, const int* yn, float* pairs,
                             float* lse, int N, int T, int U, int H, int V, int blank) {
-    JointArgs a{f, g, w, nullptr, bias, labels, xn, yn, nullptr, nullptr, reinterpret_cast<float2*>(pairs), lse,
-                N, T, U, H, V, joint_vpad(V), blank, 1};
+    JointArgs a{f, g, w, nullptr, bias, labels, xn, yn, nullptr, nullptr, reinterpret_cast<float2*>(pairs),
+                reinterpret_cast<float2*>(lse), N, T, U, H, V, joint_vpad(V), blank, 1};
     const bool tanh_ = act == RNNT_ACT_TANH;
     switch (dtype) {
         case RNNT_DTYPE_F32: return tanh_ ? fwd_typed<float, RNNT_ACT_TANH>(stream, a) : fwd_typed<float, RNNT_ACT_RELU>(stream, a);
@@ -550,7 +562,7 @@ hipError_t launch_joint_bwd(hipStream_t stream, int dtype, int act, const void* 
                             int splits, void* df, void* dg, float* dweight, float* dbias, int N, int T, int U, int H,
                             int V, int blank) {
     JointArgs a{f, g, w, nullptr, bias, labels, xn, yn, reinterpret_cast<const float2*>(grads), grad_costs, nullptr,
-                const_cast<float*>(lse), N, T, U, H, V, joint_vpad(V), blank, 1};
+                reinterpret_cast<float2*>(const_cast<float*>(lse)), N, T, U, H, V, joint_vpad(V), blank, 1};
     const bool tanh_ = act == RNNT_ACT_TANH;
 #define RNNT_JOINT_BWD(E, A) bwd_typed<E, A>(stream, a, wt, dw_part, db_part, splits, df, dg, dweight, dbias)
     switch (dtype) {

@@ -145,7 +145,7 @@ hipError_t launch_scatter_compact(hipStream_t stream, const float* grad_cost, co
                                   const int64_t* loc, const int* cum_lens, float* out, int64_t STU, int N,
                                   int V, int blank);
 // the joint network fused into the loss (joint.hip): dtype RNNT_DTYPE_*, act RNNT_ACT_*; `pairs` = the workspace's
-// diagonal-major pair plane, lse (N,T,U) or nullptr
+// diagonal-major pair plane, lse (N,T,U,2) = (max, log sum of exp(z - max)) per cell or nullptr
 int joint_vpad(int V);
 int joint_w_splits(int N, int T, int U, int H, int V, int dtype);
 hipError_t launch_joint_fwd(hipStream_t stream, int dtype, int act, const void* f, const void* g, const void* w,

@@ -3,8 +3,9 @@
 A training step of a transducer puts a joint network in front of the loss, ``z = Linear(H, V)(act(f_t + g_u))``.  Run
 as written it materialises two (N,T,U,H) tensors -- ``f + g`` and its activation -- plus the (N,T,U,V) logits, and their
 gradients.  :func:`rnnt_loss_from_joint` takes the joint's inputs instead and forms z tile by tile in HIP kernels
-(MFMA), so none of those tensors ever exists: forward keeps one fp32 log-normaliser and one gradient pair per lattice
-cell, backward recomputes z.
+(MFMA), so none of those tensors ever exists: forward keeps the log-normaliser (two fp32: the row's maximum and the log of
+the sum) and one gradient pair per lattice cell, 16 B in all, backward recomputes z (DESIGN.md
+section 3.9).
 """
 from typing import Optional
 

@@ -478,7 +478,8 @@ ACTIVATIONS = {"tanh": _lib.ACT_TANH, "relu": _lib.ACT_RELU}
 
 def joint_loss(f, g, weight, bias, labels, xn, yn, activation="tanh", blank=0, fastemit_lambda=0.0, with_grads=True):
     """The joint network fused into the loss: f (N,T,H), g (N,U,H), weight (V,H) of one dtype (fp32 / bf16 / fp16),
-    bias (V,) fp32 or None; validated by the caller.  Returns costs (N,) fp32 and, with_grads, lse (N,T,U) fp32 and the
+    bias (V,) fp32 or None; validated by the caller.  Returns costs (N,) fp32 and, with_grads, lse (N,T,U,2) fp32 -- the
+    log-normaliser of every cell as (max, log sum of exp(z - max)), never added up in fp32 -- and the
     gradient pairs (N,T,U,2) in the diagonal-major layout -- what :func:`joint_backward` reads (else None, None)."""
     L = _lib.load()
     N, T, H = f.shape
@@ -488,7 +489,7 @@ def joint_loss(f, g, weight, bias, labels, xn, yn, activation="tanh", blank=0, f
     _mismatch.poll(dev)
     with torch.cuda.device(dev):
         costs = torch.empty((N,), dtype=torch.float32, device=dev)
-        lse = torch.empty((N, T, U), dtype=torch.float32, device=dev) if with_grads else None
+        lse = torch.empty((N, T, U, 2), dtype=torch.float32, device=dev) if with_grads else None
         grads = torch.empty((N, T, U, 2), dtype=torch.float32, device=dev) if with_grads else None
         if N == 0:
             return costs, lse, grads
