@@ -5,7 +5,11 @@
   logits : JointNetwork (logits)      -> rnnt_loss_from_logits
   joint  : rnnt_loss_from_joint(f, g, weight, bias, ...)
 
-python tools/joint_fused_rate.py [--steps 10] [--warmup 3] [--shapes T,U,V ...]"""
+--dropout P puts Dropout(P) between the activation and the projection of the `joint` way (inside its kernels, the seed
+tensor refreshed in place every step as a training loop would); the other two ways have no such
+stage and are not run then.
+
+python tools/joint_fused_rate.py [--steps 10] [--warmup 3] [--shapes T,U,V ...] [--dropout P]"""
 import argparse
 import json
 import os
@@ -20,12 +24,16 @@ sys.path.insert(0, os.path.join(ROOT, "examples"))
 from joint_benchmark import GRID, JointNetwork, make_batch  # noqa: E402
 
 
-def step_fn(way, joint, f, g, ys, xn, yn, dtype):
+def step_fn(way, joint, f, g, ys, xn, yn, dtype, dropout=0.0):
     from warp_rnnt import rnnt_loss
     from warp_rnnt_amd.fused import rnnt_loss_from_logits
     from warp_rnnt_amd.joint import rnnt_loss_from_joint
 
+    seed = torch.zeros(1, dtype=torch.int64, device=f.device)
+
     def step():
+        if dropout > 0:
+            seed.add_(1)
         joint.zero_grad(set_to_none=True)
         f.grad = g.grad = None
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=dtype == "bf16"):
@@ -36,7 +44,8 @@ def step_fn(way, joint, f, g, ys, xn, yn, dtype):
                 joint.normalise = False
                 loss = rnnt_loss_from_logits(joint(f, g), ys, xn, yn)
             else:
-                loss = rnnt_loss_from_joint(f, g, joint.proj.weight, joint.proj.bias, ys, xn, yn)
+                loss = rnnt_loss_from_joint(f, g, joint.proj.weight, joint.proj.bias, ys, xn, yn, dropout=dropout,
+                                            dropout_seed=seed if dropout > 0 else None)
         loss.sum().backward()
     return step
 
@@ -64,7 +73,10 @@ def main():
     p.add_argument("--H", type=int, default=512)
     p.add_argument("--shapes", nargs="*")
     p.add_argument("--ways", default="gather,logits,joint")
+    p.add_argument("--dropout", type=float, default=0.0)
     args = p.parse_args()
+    if args.dropout > 0:
+        args.ways = "joint"
     grid = GRID if not args.shapes else [tuple(int(v) for v in s.split(",")) for s in args.shapes]
     dev = torch.device("cuda:0")
     for (T, U, V) in grid:
@@ -79,9 +91,10 @@ def main():
                     g = g.detach().to(torch.bfloat16).requires_grad_(True)
                 joint = JointNetwork(args.H, V).to(dev)
                 try:
-                    ms, gb = measure(step_fn(way, joint, f, g, ys, xn, yn, dtype), args.steps, args.warmup)
+                    ms, gb = measure(step_fn(way, joint, f, g, ys, xn, yn, dtype, args.dropout), args.steps,
+                                     args.warmup)
                     rec = {"T": T, "U": U, "V": V, "N": args.N, "H": args.H, "dtype": dtype, "way": way,
-                           "ms_per_step": round(ms, 3), "peak_extra_GB": round(gb, 3)}
+                           "dropout": args.dropout, "ms_per_step": round(ms, 3), "peak_extra_GB": round(gb, 3)}
                 except torch.cuda.OutOfMemoryError:
                     rec = {"T": T, "U": U, "V": V, "N": args.N, "H": args.H, "dtype": dtype, "way": way, "oom": True}
                 print(json.dumps(rec), flush=True)

@@ -86,6 +86,19 @@ CLAMP_SYMBOLS = {
 }
 
 
+# every symbol include/warp_rnnt_amd_joint_dropout.h declares (dropout inside the fused joint; additive: it did not move
+# the version): the arguments of the twin with `float p, const uint64_t *seed` (a device pointer) behind them, and the
+# mask's definition on the host
+_u64 = ctypes.c_uint64
+DROPOUT_SYMBOLS = {
+    "rnnt_amd_joint_loss_dropout": (_i, SYMBOLS["rnnt_amd_joint_loss"][1] + [_f, _vp]),
+    "rnnt_amd_joint_backward_dropout": (_i, SYMBOLS["rnnt_amd_joint_backward"][1] + [_f, _vp]),
+    "rnnt_amd_joint_dropout_mask_host": (_i, [_u64, _f, _i, _i, _i, _i, _vp]),
+}
+# additive tables: (symbols, the header that declares them)
+ADDITIVE = ((CLAMP_SYMBOLS, "warp_rnnt_amd_clamp.h"), (DROPOUT_SYMBOLS, "warp_rnnt_amd_joint_dropout.h"))
+
+
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
 
 
@@ -121,12 +134,13 @@ def load():
         raise RuntimeError(f"{path} reports C-ABI version {L.rnnt_amd_version()}, this package binds version "
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
-    for name, (res, args) in CLAMP_SYMBOLS.items():
-        fn = getattr(L, name, None)
-        if fn is None:
-            raise RuntimeError(f"{path} does not export {name} (include/warp_rnnt_amd_clamp.h): it was built from older "
-                               "sources: rebuild it (`python warp_rnnt_amd/_build.py`)")
-        fn.restype = res
-        fn.argtypes = args
+    for table, header in ADDITIVE:
+        for name, (res, args) in table.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise RuntimeError(f"{path} does not export {name} (include/{header}): it was built from older "
+                                   "sources: rebuild it (`python warp_rnnt_amd/_build.py`)")
+            fn.restype = res
+            fn.argtypes = args
     _lib = L
     return L

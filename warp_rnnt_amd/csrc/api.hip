@@ -2,12 +2,14 @@
 // Host-side orchestration only: argument checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd.h"
 #include "../../include/warp_rnnt_amd_clamp.h"
+#include "../../include/warp_rnnt_amd_joint_dropout.h"
 
 #include <cstdio>
 #include <cstdlib>
 
 #include "common.h"
 #include "kernels.h"
+#include "philox.h"
 
 using namespace rnnt;
 
@@ -780,10 +782,12 @@ size_t rnnt_amd_joint_workspace_size(int N, int T, int U, int H, int V) {
     return carve_joint(nullptr, N, T, U, H, V, nullptr);
 }
 
-rnntStatus_t rnnt_amd_joint_loss(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
-                                 const void* g, const void* weight, const float* bias, const int* labels, const int* xn,
-                                 const int* yn, float* costs, float* lse, float* grads, int N, int T, int U, int H, int V,
-                                 int blank, float fastemit_lambda) {
+// p, seed: the dropout of include/warp_rnnt_amd_joint_dropout.h (p == 0: none, seed unread)
+namespace {
+rnntStatus_t joint_loss(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f, const void* g,
+                        const void* weight, const float* bias, const int* labels, const int* xn, const int* yn,
+                        float* costs, float* lse, float* grads, int N, int T, int U, int H, int V, int blank,
+                        float fastemit_lambda, float p, const uint64_t* seed) {
     if (!joint_args_ok(dtype, activation, N, T, U, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (!workspace_ok(workspace) || !f || !g || !weight || !xn || !yn || !costs || (U > 1 && !labels) || (grads && !lse))
         return RNNT_STATUS_INVALID_ARGUMENT;
@@ -794,18 +798,18 @@ rnntStatus_t rnnt_amd_joint_loss(rnntStream_t stream, void* workspace, int dtype
     // 1. z tile by tile: the (blank,label) log-prob pairs into the pair plane (launch_log_softmax_gather_skewed's
     //    layout), (max, log sum) per cell
     if (launch_joint_fwd(stream, dtype, activation, f, g, weight, bias, labels, xn, yn, w.ws2, grads ? lse : nullptr, N,
-                         T, U, H, V, blank) != hipSuccess)
+                         T, U, H, V, blank, p, seed) != hipSuccess)
         return RNNT_STATUS_PROLOGUE_FAILED;
     // 2. + 3. as rnnt_amd_loss_logits(RNNT_GRADS_GATHERED_DIAGONAL or RNNT_GRADS_NONE)
     return sweeps_and_pair_grads(stream, w, xn, yn, costs, grads ? grads : w.ws2, WRITE_SKEWED2, N, T, U, nullptr,
                                  fastemit_lambda);
 }
 
-rnntStatus_t rnnt_amd_joint_backward(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
-                                     const void* g, const void* weight, const float* bias, const int* labels,
-                                     const int* xn, const int* yn, const float* lse, const float* grads,
-                                     const float* grad_costs, void* df, void* dg, float* dweight, float* dbias, int N,
-                                     int T, int U, int H, int V, int blank) {
+rnntStatus_t joint_backward(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                            const void* g, const void* weight, const float* bias, const int* labels, const int* xn,
+                            const int* yn, const float* lse, const float* grads, const float* grad_costs, void* df,
+                            void* dg, float* dweight, float* dbias, int N, int T, int U, int H, int V, int blank, float p,
+                            const uint64_t* seed) {
     if (!joint_args_ok(dtype, activation, N, T, U, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
     if (!workspace_ok(workspace) || !f || !g || !weight || !xn || !yn || !lse || !grads || (U > 1 && !labels))
         return RNNT_STATUS_INVALID_ARGUMENT;
@@ -816,8 +820,70 @@ rnntStatus_t rnnt_amd_joint_backward(rnntStream_t stream, void* workspace, int d
     carve_joint(workspace, N, T, U, H, V, &jw);
     if (launch_joint_bwd(stream, dtype, activation, f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs, jw.wt,
                          jw.dw_part, jw.db_part, joint_w_splits(N, T, U, H, V, dtype), df, dg, dweight, dbias, N, T, U,
-                         H, V, blank) != hipSuccess)
+                         H, V, blank, p, seed) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// the dropout of the *_dropout entries: p in [0,1) (false for a NaN); p > 0 needs the device word
+inline bool dropout_ok(float p, const uint64_t* seed) {
+    return p >= 0.0f && p < 1.0f && (p == 0.0f || (seed && aligned(seed, 8)));
+}
+}  // namespace
+
+rnntStatus_t rnnt_amd_joint_loss(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                 const void* g, const void* weight, const float* bias, const int* labels, const int* xn,
+                                 const int* yn, float* costs, float* lse, float* grads, int N, int T, int U, int H, int V,
+                                 int blank, float fastemit_lambda) {
+    return joint_loss(stream, workspace, dtype, activation, f, g, weight, bias, labels, xn, yn, costs, lse, grads, N, T, U,
+                      H, V, blank, fastemit_lambda, 0.0f, nullptr);
+}
+
+rnntStatus_t rnnt_amd_joint_backward(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                     const void* g, const void* weight, const float* bias, const int* labels,
+                                     const int* xn, const int* yn, const float* lse, const float* grads,
+                                     const float* grad_costs, void* df, void* dg, float* dweight, float* dbias, int N,
+                                     int T, int U, int H, int V, int blank) {
+    return joint_backward(stream, workspace, dtype, activation, f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs,
+                          df, dg, dweight, dbias, N, T, U, H, V, blank, 0.0f, nullptr);
+}
+
+// include/warp_rnnt_amd_joint_dropout.h: the same with dropout between the activation and the projection.  p == 0 IS the
+// entry above (seed unread).
+rnntStatus_t rnnt_amd_joint_loss_dropout(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                         const void* g, const void* weight, const float* bias, const int* labels,
+                                         const int* xn, const int* yn, float* costs, float* lse, float* grads, int N,
+                                         int T, int U, int H, int V, int blank, float fastemit_lambda, float p,
+                                         const uint64_t* seed) {
+    if (!dropout_ok(p, seed)) return RNNT_STATUS_INVALID_ARGUMENT;
+    return joint_loss(stream, workspace, dtype, activation, f, g, weight, bias, labels, xn, yn, costs, lse, grads, N, T, U,
+                      H, V, blank, fastemit_lambda, p, p > 0.0f ? seed : nullptr);
+}
+
+rnntStatus_t rnnt_amd_joint_backward_dropout(rnntStream_t stream, void* workspace, int dtype, int activation,
+                                             const void* f, const void* g, const void* weight, const float* bias,
+                                             const int* labels, const int* xn, const int* yn, const float* lse,
+                                             const float* grads, const float* grad_costs, void* df, void* dg,
+                                             float* dweight, float* dbias, int N, int T, int U, int H, int V, int blank,
+                                             float p, const uint64_t* seed) {
+    if (!dropout_ok(p, seed)) return RNNT_STATUS_INVALID_ARGUMENT;
+    return joint_backward(stream, workspace, dtype, activation, f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs,
+                          df, dg, dweight, dbias, N, T, U, H, V, blank, p, p > 0.0f ? seed : nullptr);
+}
+
+// The keep mask of those entries on the host (philox.h is one definition for both sides): no HIP call.
+rnntStatus_t rnnt_amd_joint_dropout_mask_host(uint64_t seed, float p, int N, int T, int U, int H, unsigned char* keep) {
+    if (!(p >= 0.0f && p < 1.0f) || N < 0 || T < 0 || U < 0 || H < 0 || !keep) return RNNT_STATUS_INVALID_ARGUMENT;
+    const uint32_t thr = dropout_threshold(p);
+    for (int n = 0; n < N; ++n)
+        for (int t = 0; t < T; ++t)
+            for (int u = 0; u < U; ++u) {
+                unsigned char* row = keep + (((size_t)n * T + t) * U + u) * H;
+                for (int k = 0; k < H; k += 4) {
+                    const Philox4 r = dropout_words(seed, n, t, u, k >> 2);
+                    for (int j = 0; j < 4 && k + j < H; ++j) row[k + j] = r.w[j] < thr;
+                }
+            }
     return RNNT_STATUS_SUCCESS;
 }
 

@@ -15,6 +15,7 @@
 #include "../../include/warp_rnnt_amd.h"
 #include "common.h"
 #include "kernels.h"
+#include "philox.h"
 
 namespace rnnt {
 
@@ -83,13 +84,52 @@ struct JointArgs {
     int N, T, U, H, V, Vp, blank, wpg;
 };
 
+// Dropout between the activation and the projection (include/warp_rnnt_amd_joint_dropout.h): the
+// staged operand becomes m * scale * act(f+g), m from philox.h.  DROP is a template parameter of the three kernels; the
+// DROP = false instantiations take JointArgs and are the code without dropout.
+struct JointDropArgs : JointArgs {
+    const unsigned long long* seed;   // one device word, read when the kernel runs (a graph replays with its contents then)
+    uint32_t thr;                     // keep iff word < thr
+    float scale, keep;                // 1 / (1 - p) and 1 - p
+};
+template <bool DROP> using jargs_t = std::conditional_t<DROP, JointDropArgs, JointArgs>;
+
+// o[0..3] *= scale for elements 4 k4 ... 4 k4 + 3 of cell (n,t,u); returns the four keep bits (bit j: element j)
+__device__ __forceinline__ unsigned drop4(const JointDropArgs& a, unsigned long long seed, int n, int t, int u, int k4,
+                                          float* o) {
+    const Philox4 r = dropout_words(seed, n, t, u, k4);
+    unsigned m = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        o[j] *= a.scale;
+        m |= (unsigned)(r.w[j] < a.thr) << j;
+    }
+    return m;
+}
+
+// How k_joint_bwd_fg's act' step gets its mask.  It cannot be read off h~ == 0: a kept element may hold an exact zero
+// (tanh at f + g = 0) and has derivative scale there.  The staged value carries it in the sign of zero instead: a DROPPED
+// element is staged as -0.0, a kept one never is (a kept value that rounds to a zero of either sign is staged as +0.0).
+// To the matrix products -0.0 is a zero like the other -- accumulators start at +0.0, and +0.0 + -0.0 = +0.0 -- so z
+// and dW are what a plane of +0.0 gives, bit for bit; the act' step tests the one bit pattern.  Against a bit plane in
+// LDS beside hs (16 H / 8 bytes per wave: DESIGN.md section 3.11 has the comparison, built and measured) this costs no
+// LDS, no further LDS reads in the innermost loop, and four registers in a kernel that holds 256 without dropout (the
+// plane's reads took it to 512 and 1 KB of scratch per lane).
+template <typename E> __device__ __forceinline__ E drop_stage(float v, bool keep) {
+    const E e = (E)v;
+    return keep ? (e == (E)0.0f ? (E)0.0f : e) : (E)(-0.0f);
+}
+template <typename E> __device__ __forceinline__ bool dropped(E h) { return __float_as_uint((float)h) == 0x80000000u; }
+
 // LDS row pitch of the staged activations: H elements + 16 bytes (the 16 rows of a fragment read then start on
 // different banks)
 template <typename E> __device__ __forceinline__ int hs_pitch(int H) { return H + EPF<E>; }
 
 // Stage h = act(f[n,t(c)] + g[n,u(c)]) of the wave's 16 cells (fp32 arithmetic, rounded once to E); dead cells get zeros.
-template <typename E, int ACT, typename CellOf>
-__device__ __forceinline__ void stage_h(const JointArgs& a, int n, E* hs, CellOf cell_of, int Tn, int Un, int lane) {
+// DROP: m * scale * act(...), the product in fp32, rounded once; dropped elements as -0.0 (drop_stage).
+template <typename E, int ACT, bool DROP, typename CellOf>
+__device__ __forceinline__ void stage_h(const jargs_t<DROP>& a, int n, E* hs, CellOf cell_of, int Tn, int Un, int lane,
+                                        unsigned long long seed = 0) {
     const E* f = static_cast<const E*>(a.f);
     const E* g = static_cast<const E*>(a.g);
     const int H = a.H, P = hs_pitch<E>(H), H4 = H >> 2;
@@ -98,14 +138,21 @@ __device__ __forceinline__ void stage_h(const JointArgs& a, int n, E* hs, CellOf
         int t, u;
         cell_of(c, t, u);
         float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        [[maybe_unused]] unsigned m = 15u;   // (dead cells: plain zeros)
         if (t < Tn && u < Un) {
             const E* fp = f + ((size_t)n * a.T + t) * H + k;
             const E* gp = g + ((size_t)n * a.U + u) * H + k;
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = act_fwd<ACT>((float)fp[j] + (float)gp[j]);
+            if constexpr (DROP) m = drop4(a, seed, n, t, u, k >> 2, o);
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) hs[c * P + k + j] = (E)o[j];
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (DROP)
+                hs[c * P + k + j] = drop_stage<E>(o[j], (m >> j) & 1u);
+            else
+                hs[c * P + k + j] = (E)o[j];
+        }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -144,8 +191,8 @@ __device__ __forceinline__ int label_of(const JointArgs& a, int n, int u) {
 // same.  A logit of -inf (a masked vocabulary entry) contributes nothing to max or sum, also
 // when it comes before the first finite one; a row needs one finite logit.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename E, int ACT>
-__global__ void __launch_bounds__(WAVE * JWAVES) k_joint_fwd(JointArgs a) {
+template <typename E, int ACT, bool DROP>
+__global__ void __launch_bounds__(WAVE * JWAVES) k_joint_fwd(jargs_t<DROP> a) {
     extern __shared__ __align__(16) unsigned char j_lds[];
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
     const int tt = (a.T + 3) >> 2, tu = (a.U + 3) >> 2;
@@ -162,8 +209,10 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_fwd(JointArgs a) {
     float2 lse = make_float2(0.0f, 0.0f);
     if (t0 < len.Tn && u0 < len.Un) {
         E* hs = reinterpret_cast<E*>(j_lds) + (size_t)wave * 16 * hs_pitch<E>(a.H);
-        stage_h<E, ACT>(a, n, hs, [&](int cc, int& ct, int& cu) { ct = t0 + (cc >> 2); cu = u0 + (cc & 3); }, len.Tn,
-                        len.Un, lane);
+        unsigned long long seed = 0;
+        if constexpr (DROP) seed = *a.seed;
+        stage_h<E, ACT, DROP>(a, n, hs, [&](int cc, int& ct, int& cu) { ct = t0 + (cc >> 2); cu = u0 + (cc & 3); },
+                              len.Tn, len.Un, lane, seed);
         const int lab = label_of(a, n, u < a.U ? u : a.U - 1);
         float m = -INFINITY, s = 0.0f, zb = 0.0f, zl = 0.0f;
         for (int v0 = 0; v0 < a.V; v0 += 16) {
@@ -257,8 +306,10 @@ __device__ __forceinline__ CellGrad cell_grad(const JointArgs& a, int n, int t, 
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int FG_MAXB = 64;   // H / 16 at H = 1024
 
-template <typename E, int ACT, bool SIDE_G>
-__global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_fg(JointArgs a, E* out) {
+// DROP: d/d(f+g) = dh m scale act'(y), y = h~ / scale recovered from the staged value as h~ (1 - p); m from the sign of a
+// staged zero (dropped; never from h~ == 0: a kept tanh(0) has derivative scale).
+template <typename E, int ACT, bool SIDE_G, bool DROP>
+__global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_fg(jargs_t<DROP> a, E* out) {
     extern __shared__ __align__(16) unsigned char j_lds[];
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
     const int own_tiles = SIDE_G ? (a.U + 3) >> 2 : (a.T + 3) >> 2;
@@ -271,6 +322,8 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_fg(JointArgs a, E* 
     const int H = a.H, P = hs_pitch<E>(H), q = lane >> 4, c = lane & 15, nb = H >> 4;
     const E* WT = static_cast<const E*>(a.wt);
     E* hs = reinterpret_cast<E*>(j_lds) + (size_t)wave * 16 * P;
+    unsigned long long seed = 0;
+    if constexpr (DROP) seed = *a.seed;
     float acc[FG_MAXB];
 #pragma unroll
     for (int b = 0; b < FG_MAXB; ++b) acc[b] = 0.0f;
@@ -282,7 +335,8 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_fg(JointArgs a, E* 
     };
     if (o0 < own_n) {
         for (int w0 = 0; w0 < walk_n; w0 += 4) {
-            stage_h<E, ACT>(a, n, hs, [&](int cc, int& ct, int& cu) { tu_of(cc, w0, ct, cu); }, len.Tn, len.Un, lane);
+            stage_h<E, ACT, DROP>(a, n, hs, [&](int cc, int& ct, int& cu) { tu_of(cc, w0, ct, cu); }, len.Tn, len.Un,
+                                  lane, seed);
             int t, u;
             tu_of(c, w0, t, u);
             const CellGrad cg = cell_grad(a, n, t, u, len);
@@ -306,7 +360,14 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_fg(JointArgs a, E* 
                         // dh[r]: cell 4q + r, column k
                         float x = acc[b];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) x += dh[r] * act_bwd<ACT>((float)hs[(4 * q + r) * P + k]);
+                        for (int r = 0; r < 4; ++r) {
+                            if constexpr (DROP) {
+                                const E hv = hs[(4 * q + r) * P + k];
+                                x += dh[r] * (dropped(hv) ? 0.0f : a.scale * act_bwd<ACT>((float)hv * a.keep));
+                            } else {
+                                x += dh[r] * act_bwd<ACT>((float)hs[(4 * q + r) * P + k]);
+                            }
+                        }
                         acc[b] = x;
                     }
                 }
@@ -331,8 +392,8 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_fg(JointArgs a, E* 
 // ---------------------------------------------------------------------------------------------------------------------
 template <typename E> constexpr int CG = 16 * ZB<E>;   // cells per group: 16 (f32), 32 (half)
 
-template <typename E, int ACT>
-__global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_w(JointArgs a, int splits, long groups_per_split,
+template <typename E, int ACT, bool DROP>
+__global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_w(jargs_t<DROP> a, int splits, long groups_per_split,
                                                               float* dw_part, float* db_part) {
     extern __shared__ __align__(16) unsigned char j_lds[];
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
@@ -350,6 +411,8 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_w(JointArgs a, int 
 #pragma unroll
     for (int b = 0; b < HC_W / 16; ++b) acc[b] = jf4{0.0f, 0.0f, 0.0f, 0.0f};
     float db = 0.0f;
+    unsigned long long seed = 0;
+    if constexpr (DROP) seed = *a.seed;
     const long g_end = min(groups, (long)(s + 1) * groups_per_split);
     for (long gi = (long)s * groups_per_split; gi < g_end; ++gi) {
         const long cell0 = gi * CG<E>;
@@ -357,6 +420,7 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_w(JointArgs a, int 
         bool any = false;
         CellGrad cgs[ZB<E>];
         size_t frow[ZB<E>], grow[ZB<E>];   // rows of f and g of cell 16 zb + c (the staging below fetches them by shuffle)
+        [[maybe_unused]] int cn[ZB<E>], ct[ZB<E>], cu[ZB<E>];   // DROP: the cell itself, the mask's counter
 #pragma unroll
         for (int zb = 0; zb < ZB<E>; ++zb) {
             const long cell = cell0 + 16 * zb + c;
@@ -372,6 +436,7 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_w(JointArgs a, int 
             cgs[zb] = cell < cells ? cell_grad(a, n, t, u, len) : CellGrad{false, 0.0f, 0.0f, 0.0f, 0.0f, a.blank};
             frow[zb] = (size_t)n * a.T + t;
             grow[zb] = (size_t)n * a.U + u;
+            if constexpr (DROP) { cn[zb] = n; ct[zb] = t; cu[zb] = u; }
             any |= cgs[zb].live;
         }
         if (__ballot(any) == 0) continue;
@@ -388,15 +453,28 @@ __global__ void __launch_bounds__(WAVE * JWAVES) k_joint_bwd_w(JointArgs a, int 
                 const bool live = __shfl((int)cgs[zb].live, cc, WAVE) != 0;
                 const size_t fr = __shfl((unsigned long long)frow[zb], cc, WAVE);
                 const size_t gr = __shfl((unsigned long long)grow[zb], cc, WAVE);
+                [[maybe_unused]] int dn = 0, dt = 0, du = 0;
+                if constexpr (DROP) {
+                    dn = __shfl(cn[zb], cc, WAVE);
+                    dt = __shfl(ct[zb], cc, WAVE);
+                    du = __shfl(cu[zb], cc, WAVE);
+                }
                 float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                [[maybe_unused]] unsigned m = 15u;
                 if (live) {
                     const E* fp = f + fr * H + k;
                     const E* gp = g + gr * H + k;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) o[j] = act_fwd<ACT>((float)fp[j] + (float)gp[j]);
+                    if constexpr (DROP) m = drop4(a, seed, dn, dt, du, k >> 2, o);
                 }
 #pragma unroll
-                for (int j = 0; j < 4; ++j) hz[cc * P + k + j] = (E)o[j];
+                for (int j = 0; j < 4; ++j) {
+                    if constexpr (DROP)
+                        hz[cc * P + k + j] = drop_stage<E>(o[j], (m >> j) & 1u);
+                    else
+                        hz[cc * P + k + j] = (E)o[j];
+                }
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -488,16 +566,16 @@ template <typename E> int waves_per_group(int rows, int H) {
 
 inline unsigned blocks_for(long items, int wpg) { return (unsigned)((items + wpg - 1) / wpg); }
 
-template <typename E, int ACT> hipError_t fwd_typed(hipStream_t stream, JointArgs a) {
+template <typename E, int ACT, bool DROP> hipError_t fwd_typed(hipStream_t stream, jargs_t<DROP> a) {
     a.wpg = waves_per_group<E>(16, a.H);
     const long items = (long)a.N * ((a.T + 3) / 4) * ((a.U + 3) / 4);
     const size_t lds = (size_t)a.wpg * 16 * (a.H + EPF<E>) * sizeof(E);
-    k_joint_fwd<E, ACT><<<blocks_for(items, a.wpg), WAVE * a.wpg, lds, stream>>>(a);
+    k_joint_fwd<E, ACT, DROP><<<blocks_for(items, a.wpg), WAVE * a.wpg, lds, stream>>>(a);
     return hipGetLastError();
 }
 
-template <typename E, int ACT>
-hipError_t bwd_typed(hipStream_t stream, JointArgs a, void* wt, float* dw_part, float* db_part, int splits, void* df,
+template <typename E, int ACT, bool DROP>
+hipError_t bwd_typed(hipStream_t stream, jargs_t<DROP> a, void* wt, float* dw_part, float* db_part, int splits, void* df,
                      void* dg, float* dweight, float* dbias) {
     const long tw = (long)a.H * a.Vp;
     k_joint_transpose_w<E><<<(unsigned)((tw + 255) / 256), 256, 0, stream>>>(static_cast<const E*>(a.w),
@@ -507,25 +585,60 @@ hipError_t bwd_typed(hipStream_t stream, JointArgs a, void* wt, float* dw_part, 
     const size_t lds = (size_t)a.wpg * 16 * (a.H + EPF<E>) * sizeof(E);
     if (df) {
         const long items = (long)a.N * ((a.T + 3) / 4);
-        k_joint_bwd_fg<E, ACT, false><<<blocks_for(items, a.wpg), WAVE * a.wpg, lds, stream>>>(a, static_cast<E*>(df));
+        k_joint_bwd_fg<E, ACT, false, DROP><<<blocks_for(items, a.wpg), WAVE * a.wpg, lds, stream>>>(
+            a, static_cast<E*>(df));
     }
     if (dg) {
         const long items = (long)a.N * ((a.U + 3) / 4);
-        k_joint_bwd_fg<E, ACT, true><<<blocks_for(items, a.wpg), WAVE * a.wpg, lds, stream>>>(a, static_cast<E*>(dg));
+        k_joint_bwd_fg<E, ACT, true, DROP><<<blocks_for(items, a.wpg), WAVE * a.wpg, lds, stream>>>(
+            a, static_cast<E*>(dg));
     }
     if (dweight || dbias) {
-        JointArgs b = a;
+        jargs_t<DROP> b = a;
         b.wpg = waves_per_group<E>(CG<E>, a.H);
         const size_t lw = (size_t)b.wpg * CG<E> * (a.H + EPF<E>) * sizeof(E);
         const long cells = (long)a.N * a.T * a.U, groups = (cells + CG<E> - 1) / CG<E>;
         const long per = (groups + splits - 1) / splits;
         const long items = (long)((a.V + 15) / 16) * ((a.H + HC_W - 1) / HC_W) * splits;
-        k_joint_bwd_w<E, ACT><<<blocks_for(items, b.wpg), WAVE * b.wpg, lw, stream>>>(b, splits, per, dw_part, db_part);
+        k_joint_bwd_w<E, ACT, DROP><<<blocks_for(items, b.wpg), WAVE * b.wpg, lw, stream>>>(b, splits, per, dw_part,
+                                                                                          db_part);
         const long vh = (long)a.V * a.H;
         k_joint_reduce_w<<<(unsigned)((vh + 255) / 256), 256, 0, stream>>>(dw_part, db_part, splits, a.V, a.Vp, a.H,
                                                                            dweight, dbias);
     }
     return hipGetLastError();
+}
+
+template <bool DROP> jargs_t<DROP> drop_args(const JointArgs& a, float p, const uint64_t* seed) {
+    if constexpr (DROP)
+        return JointDropArgs{a, reinterpret_cast<const unsigned long long*>(seed), dropout_threshold(p), dropout_scale(p),
+                             (float)(1.0 - (double)p)};
+    else
+        return a;
+}
+
+template <bool DROP> hipError_t fwd_drop(hipStream_t stream, int dtype, int act, jargs_t<DROP> a) {
+    const bool tanh_ = act == RNNT_ACT_TANH;
+#define RNNT_JOINT_FWD(E, A) fwd_typed<E, A, DROP>(stream, a)
+    switch (dtype) {
+        case RNNT_DTYPE_F32: return tanh_ ? RNNT_JOINT_FWD(float, RNNT_ACT_TANH) : RNNT_JOINT_FWD(float, RNNT_ACT_RELU);
+        case RNNT_DTYPE_BF16: return tanh_ ? RNNT_JOINT_FWD(__bf16, RNNT_ACT_TANH) : RNNT_JOINT_FWD(__bf16, RNNT_ACT_RELU);
+        default: return tanh_ ? RNNT_JOINT_FWD(_Float16, RNNT_ACT_TANH) : RNNT_JOINT_FWD(_Float16, RNNT_ACT_RELU);
+    }
+#undef RNNT_JOINT_FWD
+}
+
+template <bool DROP>
+hipError_t bwd_drop(hipStream_t stream, int dtype, int act, jargs_t<DROP> a, void* wt, float* dw_part, float* db_part,
+                    int splits, void* df, void* dg, float* dweight, float* dbias) {
+    const bool tanh_ = act == RNNT_ACT_TANH;
+#define RNNT_JOINT_BWD(E, A) bwd_typed<E, A, DROP>(stream, a, wt, dw_part, db_part, splits, df, dg, dweight, dbias)
+    switch (dtype) {
+        case RNNT_DTYPE_F32: return tanh_ ? RNNT_JOINT_BWD(float, RNNT_ACT_TANH) : RNNT_JOINT_BWD(float, RNNT_ACT_RELU);
+        case RNNT_DTYPE_BF16: return tanh_ ? RNNT_JOINT_BWD(__bf16, RNNT_ACT_TANH) : RNNT_JOINT_BWD(__bf16, RNNT_ACT_RELU);
+        default: return tanh_ ? RNNT_JOINT_BWD(_Float16, RNNT_ACT_TANH) : RNNT_JOINT_BWD(_Float16, RNNT_ACT_RELU);
+    }
+#undef RNNT_JOINT_BWD
 }
 
 }  // namespace
@@ -543,34 +656,26 @@ int joint_w_splits(int N, int T, int U, int H, int V, int dtype) {
     return s < 1 ? 1 : (int)s;
 }
 
+// p > 0: the dropout kernels with the mask of (seed, p) (philox.h; seed a device word); p == 0: the kernels without
 hipError_t launch_joint_fwd(hipStream_t stream, int dtype, int act, const void* f, const void* g, const void* w,
                             const float* bias, const int* labels, const int* xn, const int* yn, float* pairs,
-                            float* lse, int N, int T, int U, int H, int V, int blank) {
+                            float* lse, int N, int T, int U, int H, int V, int blank, float p, const uint64_t* seed) {
     JointArgs a{f, g, w, nullptr, bias, labels, xn, yn, nullptr, nullptr, reinterpret_cast<float2*>(pairs),
                 reinterpret_cast<float2*>(lse), N, T, U, H, V, joint_vpad(V), blank, 1};
-    const bool tanh_ = act == RNNT_ACT_TANH;
-    switch (dtype) {
-        case RNNT_DTYPE_F32: return tanh_ ? fwd_typed<float, RNNT_ACT_TANH>(stream, a) : fwd_typed<float, RNNT_ACT_RELU>(stream, a);
-        case RNNT_DTYPE_BF16: return tanh_ ? fwd_typed<__bf16, RNNT_ACT_TANH>(stream, a) : fwd_typed<__bf16, RNNT_ACT_RELU>(stream, a);
-        default: return tanh_ ? fwd_typed<_Float16, RNNT_ACT_TANH>(stream, a) : fwd_typed<_Float16, RNNT_ACT_RELU>(stream, a);
-    }
+    return p > 0.0f ? fwd_drop<true>(stream, dtype, act, drop_args<true>(a, p, seed))
+                    : fwd_drop<false>(stream, dtype, act, a);
 }
 
 hipError_t launch_joint_bwd(hipStream_t stream, int dtype, int act, const void* f, const void* g, const void* w,
                             const float* bias, const int* labels, const int* xn, const int* yn, const float* lse,
                             const float* grads, const float* grad_costs, void* wt, float* dw_part, float* db_part,
                             int splits, void* df, void* dg, float* dweight, float* dbias, int N, int T, int U, int H,
-                            int V, int blank) {
+                            int V, int blank, float p, const uint64_t* seed) {
     JointArgs a{f, g, w, nullptr, bias, labels, xn, yn, reinterpret_cast<const float2*>(grads), grad_costs, nullptr,
                 reinterpret_cast<float2*>(const_cast<float*>(lse)), N, T, U, H, V, joint_vpad(V), blank, 1};
-    const bool tanh_ = act == RNNT_ACT_TANH;
-#define RNNT_JOINT_BWD(E, A) bwd_typed<E, A>(stream, a, wt, dw_part, db_part, splits, df, dg, dweight, dbias)
-    switch (dtype) {
-        case RNNT_DTYPE_F32: return tanh_ ? RNNT_JOINT_BWD(float, RNNT_ACT_TANH) : RNNT_JOINT_BWD(float, RNNT_ACT_RELU);
-        case RNNT_DTYPE_BF16: return tanh_ ? RNNT_JOINT_BWD(__bf16, RNNT_ACT_TANH) : RNNT_JOINT_BWD(__bf16, RNNT_ACT_RELU);
-        default: return tanh_ ? RNNT_JOINT_BWD(_Float16, RNNT_ACT_TANH) : RNNT_JOINT_BWD(_Float16, RNNT_ACT_RELU);
-    }
-#undef RNNT_JOINT_BWD
+    return p > 0.0f ? bwd_drop<true>(stream, dtype, act, drop_args<true>(a, p, seed), wt, dw_part, db_part, splits, df,
+                                     dg, dweight, dbias)
+                    : bwd_drop<false>(stream, dtype, act, a, wt, dw_part, db_part, splits, df, dg, dweight, dbias);
 }
 
 }  // namespace rnnt

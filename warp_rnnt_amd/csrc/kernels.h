@@ -145,18 +145,19 @@ hipError_t launch_scatter_compact(hipStream_t stream, const float* grad_cost, co
                                   const int64_t* loc, const int* cum_lens, float* out, int64_t STU, int N,
                                   int V, int blank);
 // the joint network fused into the loss (joint.hip): dtype RNNT_DTYPE_*, act RNNT_ACT_*; `pairs` = the workspace's
-// diagonal-major pair plane, lse (N,T,U,2) = (max, log sum of exp(z - max)) per cell or nullptr
+// diagonal-major pair plane, lse (N,T,U,2) = (max, log sum of exp(z - max)) per cell or nullptr.  p > 0: dropout between
+// activation and projection with the mask of philox.h under the device word *seed; p == 0: the kernels without (seed unread)
 int joint_vpad(int V);
 int joint_w_splits(int N, int T, int U, int H, int V, int dtype);
 hipError_t launch_joint_fwd(hipStream_t stream, int dtype, int act, const void* f, const void* g, const void* w,
                             const float* bias, const int* labels, const int* xn, const int* yn, float* pairs,
-                            float* lse, int N, int T, int U, int H, int V, int blank);
+                            float* lse, int N, int T, int U, int H, int V, int blank, float p, const uint64_t* seed);
 // wt: (H, joint_vpad(V)) elements of dtype; dw_part / db_part: splits x joint_vpad(V) x H and splits x joint_vpad(V) fp32
 hipError_t launch_joint_bwd(hipStream_t stream, int dtype, int act, const void* f, const void* g, const void* w,
                             const float* bias, const int* labels, const int* xn, const int* yn, const float* lse,
                             const float* grads, const float* grad_costs, void* wt, float* dw_part, float* db_part,
                             int splits, void* df, void* dg, float* dweight, float* dbias, int N, int T, int U, int H,
-                            int V, int blank);
+                            int V, int blank, float p, const uint64_t* seed);
 // The forward log-softmax family (lsm.h; lsm_f32.hip holds these launchers) for logits of any RNNT_DTYPE_*
 // (hipErrorInvalidValue for another dtype): fp32 arithmetic from the load on, pairs and log-probs in fp32, d/d logits in
 // the logits' type.  Which kernel, in which shape: lsm_plan.h decides once per call, the launchers switch on its plan.

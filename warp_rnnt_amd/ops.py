@@ -476,11 +476,23 @@ def log_softmax_backward(grad_out, out, grad_in=None):
 ACTIVATIONS = {"tanh": _lib.ACT_TANH, "relu": _lib.ACT_RELU}
 
 
-def joint_loss(f, g, weight, bias, labels, xn, yn, activation="tanh", blank=0, fastemit_lambda=0.0, with_grads=True):
+def _dropout_args(dropout, seed):
+    """(p, seed pointer) of the *_dropout entries: seed an int64 tensor of one element on the device, read by the kernels
+    when they run."""
+    if seed is None or seed.dtype != torch.int64 or seed.numel() != 1:
+        raise RuntimeError("dropout > 0 needs seed: an int64 tensor of one element on the device of f")
+    return float(dropout), seed.data_ptr()
+
+
+def joint_loss(f, g, weight, bias, labels, xn, yn, activation="tanh", blank=0, fastemit_lambda=0.0, with_grads=True,
+               dropout=0.0, seed=None):
     """The joint network fused into the loss: f (N,T,H), g (N,U,H), weight (V,H) of one dtype (fp32 / bf16 / fp16),
     bias (V,) fp32 or None; validated by the caller.  Returns costs (N,) fp32 and, with_grads, lse (N,T,U,2) fp32 -- the
     log-normaliser of every cell as (max, log sum of exp(z - max)), never added up in fp32 -- and the
-    gradient pairs (N,T,U,2) in the diagonal-major layout -- what :func:`joint_backward` reads (else None, None)."""
+    gradient pairs (N,T,U,2) in the diagonal-major layout -- what :func:`joint_backward` reads (else None, None).
+    dropout > 0: dropout between the activation and the projection, the mask a function of ``seed`` (an int64 tensor of
+    one element on the device, read at run time) -- include/warp_rnnt_amd_joint_dropout.h; hand :func:`joint_backward` the
+    same two."""
     L = _lib.load()
     N, T, H = f.shape
     U = g.shape[1]
@@ -494,17 +506,20 @@ def joint_loss(f, g, weight, bias, labels, xn, yn, activation="tanh", blank=0, f
         if N == 0:
             return costs, lse, grads
         ws = _workspace(dev, L.rnnt_amd_joint_workspace_size, "N T U H V", N, T, U, H, V)
-        _check(L.rnnt_amd_joint_loss(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[f.dtype], ACTIVATIONS[activation],
-                                     f.data_ptr(), g.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(labels),
-                                     xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(lse), _ptr(grads),
-                                     N, T, U, H, V, blank, float(fastemit_lambda)))
+        args = (_stream(dev), ws.data_ptr(), LOGITS_DTYPES[f.dtype], ACTIVATIONS[activation], f.data_ptr(), g.data_ptr(),
+                weight.data_ptr(), _ptr(bias), _ptr(labels), xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(lse),
+                _ptr(grads), N, T, U, H, V, blank, float(fastemit_lambda))
+        if dropout > 0:
+            _check(L.rnnt_amd_joint_loss_dropout(*args, *_dropout_args(dropout, seed)))
+        else:
+            _check(L.rnnt_amd_joint_loss(*args))
     return costs, lse, grads
 
 
 def joint_backward(f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs, activation="tanh", blank=0,
-                   need_f=True, need_g=True, need_weight=True, need_bias=True):
+                   need_f=True, need_g=True, need_weight=True, need_bias=True, dropout=0.0, seed=None):
     """d(sum_n grad_costs[n]*cost[n]) / d(f, g, weight, bias) of :func:`joint_loss`: df / dg in f's dtype, dweight /
-    dbias fp32; None for what is not asked for."""
+    dbias fp32; None for what is not asked for.  dropout, seed: those of the forward."""
     L = _lib.load()
     N, T, H = f.shape
     U = g.shape[1]
@@ -521,9 +536,11 @@ def joint_backward(f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs, a
                     t.zero_()
             return df, dg, dw, db
         ws = _workspace(dev, L.rnnt_amd_joint_workspace_size, "N T U H V", N, T, U, H, V)
-        _check(L.rnnt_amd_joint_backward(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[f.dtype], ACTIVATIONS[activation],
-                                         f.data_ptr(), g.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(labels),
-                                         xn.data_ptr(), yn.data_ptr(), lse.data_ptr(), grads.data_ptr(),
-                                         _ptr(grad_costs), _ptr(df), _ptr(dg), _ptr(dw), _ptr(db), N, T, U, H, V,
-                                         blank))
+        args = (_stream(dev), ws.data_ptr(), LOGITS_DTYPES[f.dtype], ACTIVATIONS[activation], f.data_ptr(), g.data_ptr(),
+                weight.data_ptr(), _ptr(bias), _ptr(labels), xn.data_ptr(), yn.data_ptr(), lse.data_ptr(),
+                grads.data_ptr(), _ptr(grad_costs), _ptr(df), _ptr(dg), _ptr(dw), _ptr(db), N, T, U, H, V, blank)
+        if dropout > 0:
+            _check(L.rnnt_amd_joint_backward_dropout(*args, *_dropout_args(dropout, seed)))
+        else:
+            _check(L.rnnt_amd_joint_backward(*args))
     return df, dg, dw, db
