@@ -46,7 +46,7 @@ def test_reference_golden_compact():
     (5, 40, 12, 9, 0.0, 0),
     (3, 70, 90, 5, 0.02, 2),      # two waves, ragged
     (4, 9, 1, 4, 0.0, 0),         # no labels at all
-    (2, 33, 140, 6, 0.0, 1),      # V % 4 != 0 -> scalar scatter path
+    (2, 33, 140, 6, 0.0, 1),      # V % 4 != 0: still k_expand_small (V <= 1024), rows that start off 16-byte alignment
 ])
 def test_compact_vs_oracle(N, Tm, Um, V, lam, blank):
     import warp_rnnt._C as core
