@@ -16,8 +16,7 @@ LIB = os.path.join(HERE, "libwarp_rnnt_amd.so")
 SOURCES = ["api.hip", "lattice.hip", "lattice_ws.hip", "lattice_wd.hip", "grads.hip", "lsm_f32.hip", "lsm_bf16.hip",
            "lsm_f16.hip", "lsm_backward.hip", "to_diagonal.hip", "compact.hip", "expand.hip", "joint.hip"]
 HEADERS = ["common.h", "kernels.h", "lattice_plan.h", "lattice_launch.h", "lattice_step.h", "lattice_wd_body.h",
-           "lattice_single.h", "grads_cell.h", "streaming.h", "lsm_plan.h", "lsm.h", "lsm_body_small.h", "lsm_body_large.h", "lsm_body_generic.h", "lsm_body_rows.h",
-           "philox.h",
+           "lattice_single.h", "grads_cell.h", "streaming.h", "lsm_plan.h", "lsm.h", "philox.h",
            os.path.join("..", "..", "include", "warp_rnnt_amd.h"), os.path.join("..", "..", "include", "warp_rnnt_amd_clamp.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_joint_dropout.h")]
 ARCH = "gfx950"

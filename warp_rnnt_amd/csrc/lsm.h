@@ -30,14 +30,26 @@ __device__ __forceinline__ float lsm_log_sum(float log_s, float mx, float mb) {
     return __builtin_fmaf(__builtin_fmaf(-mx, LOG2E, -mb), LN2, log_s);
 }
 
-// The row -> cell map of the fused log-softmax kernels is a policy, passed by value and chosen by a template parameter.
+// The row -> cell map of the fused log-softmax kernels is a policy, chosen by a template parameter.  A kernel builds its
+// map with Map::make(head, tail) from two arguments of its own, which the launch takes from the host's map: head(), tail(blank).
+// Head sits behind `out` and Tail behind V in every kernel's argument list -- where the labels or the packed rows, and T, U
+// and the blank index, have always been: Tail ENDS with the blank, so that a map with nothing else to say (the compact one)
+// adds no argument -- an empty struct would still take a slot, move `blank` and LsmBwd, and with them the scalar
+// registers of the row-per-workgroup kernels, which have none to spare.  DenseMap's Head is the labels as
+// `const int* __restrict__`: carried inside a by-value struct the qualifier is lost, and the dense fused kernels then
+// fetch labels again that they already hold.
 // chunk(first, last) is called by every wave of a kernel, wave-uniformly, before at() is asked for rows in [first, last];
 // pair() and scale() read the backward's gradient pair and upstream scale of a mapped row, put() stores the gather's pair.
 //   DenseMap: the (N,T,U,V) tensor, map_cell -- what the dense kernels have always done.
 struct DenseMap {
     static constexpr bool COMPACT = false;
+    using Head = const int* __restrict__;
+    struct Tail { int T, U, blank; };
     const int* labels;
     int T, U;
+    static __device__ __forceinline__ DenseMap make(Head labels, Tail s) { return {labels, s.T, s.U}; }
+    Head head() const { return labels; }
+    Tail tail(int blank) const { return {T, U, blank}; }
     __device__ __forceinline__ void chunk(int64_t, int64_t) {}
     __device__ __forceinline__ CellMap at(size_t cell, int V, int blank) const {
         return map_cell(cell, labels, T, U, V, blank);
@@ -91,8 +103,13 @@ __device__ __forceinline__ void compact_owner_range(const int64_t* __restrict__ 
 template <bool SKEW>
 struct CompactMap {
     static constexpr bool COMPACT = true;
+    using Head = PackedRows;
+    struct Tail { int blank; };
     PackedRows r;
     int n0, n1;
+    static __device__ __forceinline__ CompactMap make(const Head& r, Tail) { return {r, 0, 0}; }
+    const Head& head() const { return r; }
+    Tail tail(int blank) const { return {blank}; }
     __device__ __forceinline__ void chunk(int64_t first, int64_t last) {
         compact_owner_range(r.offs, r.N, first, last, n0, n1);
         n1 = min(n1, r.N - 1);
@@ -162,9 +179,7 @@ struct CompactMap {
 // Written-through stores (sc1 / sc1 nt; round 6, after the dense gather gained from them): nothing at c4 in any mode of this
 // kernel, c3's row-per-workgroup kernel 0.658 -> 0.73-0.76 ms, the register kernel 480 -> 520-580 us -- they pay only where
 // every store instruction covers whole 128-byte lines (profiles/r06_lsm_store_policy.txt).
-#define RNNT_LSM_NT_MODE(MODE) ((MODE) != LSM_NORM)
-#define RNNT_LSM_LOAD(p) rnnt_load4<RNNT_LSM_NT_MODE(MODE)>(p)
-#define RNNT_LSM_STORE(p, v) rnnt_store4<RNNT_LSM_NT_MODE(MODE)>(p, v)
+constexpr bool lsm_nt(int mode) { return mode != LSM_NORM; }
 
 // Storage type E of the logits: float, or __bf16 / _Float16 (RNNT_DTYPE_BF16 / _F16; one unit each).  Half-precision
 // logits are converted to fp32 as they are loaded -- everything behind the load is the fp32 code -- and d/d logits (LSM_BWD)
@@ -203,7 +218,7 @@ struct LsmBwd {
     const float2* g2;    // diagonal-major gathered gradients (RNNT_GRADS_GATHERED_DIAGONAL)
     const float* scale;  // (N,) upstream gradient per utterance, or nullptr
     int xcd;             // row-per-workgroup kernel: 1 = every XCD streams a contiguous eighth of the rows
-    // The clamped backward kernels only (CLAMP below; > 0 there): d/d logits at unit upstream are limited to [-clamp, +clamp]
+    // The CLAMP instantiations of the backward kernels only (below; > 0 there): d/d logits at unit upstream are limited to [-clamp, +clamp]
     // elementwise, behind the two one-hot additions and IN FRONT of the upstream scale.  It belongs with `scale`; it sits
     // here, in what was padding, so that no other member moves and the unclamped kernels read their arguments where they did.
     float clamp;
@@ -217,9 +232,9 @@ struct LsmBwd {
 // The gradient clamp of the fused backward (torchaudio's and warp-transducer's `clamp`):
 //     u[v]  = [v==blank] gB + [v==label] gL - softmax(z)[v] (gB+gL)        (unit upstream)
 //     dz[v] = s_n * min(max(u[v], -c), +c)
-// CLAMP is a compile-time constant of every kernel that includes a body: false in the kernels that have always been here
-// (their code is what it was), true in the k_*_clamped twins, which exist for LSM_BWD only and which a call with c > 0
-// launches under the SAME plan.  The clamped bodies keep the unclamped operation order -- e_j * (gs / s), the two
+// CLAMP is a template parameter of the SMALL, LARGE and GENERIC kernels and of their bodies: false in the instantiations
+// that have always been here (their code is what it was), true in those a call with c > 0 launches under the SAME plan,
+// which exist for LSM_BWD only.  The clamped bodies keep the unclamped operation order -- e_j * (gs / s), the two
 // additions, then the clamp, then * s_n -- with the pair left unscaled, so at s_n = 1 and a clamp nothing reaches they give
 // the unclamped bits.
 __device__ __forceinline__ float lsm_clamp(float u, float c) { return __builtin_amdgcn_fmed3f(u, -c, c); }
@@ -262,40 +277,246 @@ __device__ __forceinline__ void wave_sync_lds() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <typename E, int L, int MODE, bool WP>
-__global__ void __launch_bounds__(SM_THREADS)
-k_lsm_small(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
-            int64_t rows, int V, int R, int q, int T, int U, int blank, LsmBwd bw) {
-    constexpr bool CLAMP = false;
-    DenseMap map{labels, T, U};
-#include "lsm_body_small.h"
+// The three per-element formulas of this kernel, written once for its two row forms (straight-line, and the run-time loops
+// of q <= 8) and for the row-per-workgroup kernel.  `v` is the logit, mb = -max * LOG2E (rounded: lsm_log_sum), gq =
+// (gB + gL) / s.  The row epilogues around them stay written out per form: folded into one callable they compile to one
+// branch block and one v_mov less in three L = 1 kernels per unit, and this family changes by no instruction count.
+__device__ __forceinline__ float lsm_norm_el(float v, float mx, float ls) { return (v - mx) - ls; }
+__device__ __forceinline__ float lsm_bwd_el(float v, float mb, float gq) {
+    return -__builtin_amdgcn_exp2f(__builtin_fmaf(v, LOG2E, mb)) * gq;      // -p_j (gB + gL), p_j = e_j / s
 }
-template <typename E, int L, int MODE, bool WP>
-__global__ void __launch_bounds__(SM_THREADS)
-k_lsm_small_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int R, int q, int blank,
-                    LsmBwd bw) {
-    constexpr bool CLAMP = false;
-    CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
-#include "lsm_body_small.h"
+__device__ __forceinline__ float lsm_bwd_el_clamped(float v, float mb, float gq, float c, float sc) {
+    return lsm_clamp(lsm_bwd_el(v, mb, gq), c) * sc;
 }
-// (the clamped twins: LSM_BWD only)
-template <typename E, int L, int MODE, bool WP>
-__global__ void __launch_bounds__(SM_THREADS)
-k_lsm_small_clamped(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
-                    int64_t rows, int V, int R, int q, int T, int U, int blank, LsmBwd bw) {
-    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
-    constexpr bool CLAMP = true;
-    DenseMap map{labels, T, U};
-#include "lsm_body_small.h"
+
+template <typename E, int L, int MODE, bool WP, bool CLAMP, class Map>
+__device__ __forceinline__ void lsm_small_body(const E* x, LsmOut<MODE, E>* out, Map map, int64_t rows, int V, int R, int q,
+                                               int blank, LsmBwd bw) {
+    constexpr bool GATHER = MODE == LSM_GATHER, NT = lsm_nt(MODE);
+    extern __shared__ __attribute__((aligned(16))) float tile[];
+    float2* stat = reinterpret_cast<float2*>(tile + (size_t)R * V);   // GATHER: (max, log-sum) per row
+    const int tid = threadIdx.x;
+    const int64_t row0 = (int64_t)stream_block() * R;
+    if (row0 >= rows) return;
+    const int nrows = (int)min((int64_t)R, rows - row0);
+    map.chunk(row0, row0 + nrows - 1);
+    const int nel = nrows * V;                      // floats in this chunk
+    const E* src = x + row0 * V;                    // vector aligned: R % 4 == 0 (out may alias x)
+    // wave-private view of the same tile: rows [wr0, wr0 + wn) of the chunk
+    constexpr int RW = (WAVE / L) > 0 ? (WAVE / L) : 1;
+    const int lane = tid & (WAVE - 1);
+    const int wr0 = (tid >> 6) * RW;
+    const int wn = min(max(nrows - wr0, 0), RW);
+    const int wel = wn * V, wvec = wel >> 2;
+    float* wtile = tile + wr0 * V;
+
+    // ---- stage: the tile is a plain copy of the chunk ----
+    const int nvec = nel >> 2;
+    // fused backward: the gradient pair (and scale) of the row this thread works on first, requested before the tile
+    [[maybe_unused]] CellMap pm = {0, 0, 0};
+    [[maybe_unused]] float2 pg = make_float2(0.0f, 0.0f);
+    [[maybe_unused]] float psc = 1.0f;
+    if constexpr (MODE == LSM_BWD) {
+        pm = map.at((size_t)(row0 + min(tid / L, nrows - 1)), V, blank);
+        pg = map.pair(bw, pm);
+        psc = map.scale(bw, pm);
+    }
+    // LOADS FIRST (round 5).  Written as `for (i ...) tile[i] = load(src + i)` the compiler emits load, s_waitcnt vmcnt(0),
+    // ds_write per iteration: a wave had ONE 16-byte load per lane in flight at a time and paid the memory latency three
+    // to four times per tile -- 1 KB per wave in flight, 32 KB per CU, which at ~1.5 us of loaded latency is the 5.2 TB/s
+    // the fused gather ran at (read-only streams reach 7.0, tools/ubench/copy_rate.hip).  A tile is at most four passes
+    // of the threads that stage it (SM_FLOATS, and V <= 16 L for the wave-private form): all of a lane's loads are
+    // issued before the first of them is written to LDS -- unconditionally, at an index clamped into the tile, and so are
+    // the LDS writes (lanes past the end rewrite the tile's last 16 bytes with the bytes that are there).  A predicate per
+    // load comes out as a branch per load with a conservative wait at every join; predicates on the writes alone and the
+    // compiler sinks the loads into them.
+    constexpr int STAGE_UN = WP ? 4 : (sm_floats<E, MODE>() / 4 + SM_THREADS - 1) / SM_THREADS;   // (3200 floats, 256 threads: 4)
+    if constexpr (WP) {
+        const E* wsrc = src + (size_t)wr0 * V;
+        for (int base = lane; base < wvec; base += STAGE_UN * WAVE) {
+            float4 sv[STAGE_UN];
+#pragma unroll
+            for (int k = 0; k < STAGE_UN; ++k) sv[k] = lsm_ld4<NT>(wsrc, min(base + k * WAVE, wvec - 1));
+#pragma unroll
+            for (int k = 0; k < STAGE_UN; ++k)
+                reinterpret_cast<float4*>(wtile)[min(base + k * WAVE, wvec - 1)] = sv[k];
+        }
+        for (int e = (wvec << 2) + lane; e < wel; e += WAVE) wtile[e] = lsm_ld1(wsrc + e);
+        wave_sync_lds();
+    } else {
+        for (int base = tid; base < nvec; base += STAGE_UN * SM_THREADS) {
+            float4 sv[STAGE_UN];
+#pragma unroll
+            for (int k = 0; k < STAGE_UN; ++k) sv[k] = lsm_ld4<NT>(src, min(base + k * SM_THREADS, nvec - 1));
+#pragma unroll
+            for (int k = 0; k < STAGE_UN; ++k)
+                reinterpret_cast<float4*>(tile)[min(base + k * SM_THREADS, nvec - 1)] = sv[k];
+        }
+        for (int e = (nvec << 2) + tid; e < nel; e += SM_THREADS) tile[e] = lsm_ld1(src + e);   // last chunk only
+        __syncthreads();
+    }
+
+    // ---- per-row max / sum(exp) / normalise: L lanes per row, lane h owns columns h, h+L, ... ----
+    constexpr int RPP = SM_THREADS / L;             // rows per pass
+    const int h = tid % L, rr = tid / L;
+    const int ctail = h + (q - 1) * L;              // this lane's last column, may be >= V
+    const bool tail_ok = ctail < V;
+    // One row: the lane's q values are read ONCE into registers by a straight-line sequence (all LDS reads in flight
+    // together), reduced, and -- in the modes that rewrite the row -- written back from the registers.  QC = q as a
+    // compile-time constant (9 ... 16: what the launcher's choice of L gives for V > 16); the run-time loops of the first
+    // version waited for every LDS read of the max pass on its own (~9 instructions and one LDS latency per element) and
+    // read every element a second time for the sum.
+    auto one_row = [&](auto QC, const int r) {
+        constexpr int Q = decltype(QC)::value;
+        float* row = tile + r * V;
+        float v[Q];
+#pragma unroll
+        for (int i = 0; i < Q - 1; ++i) v[i] = row[h + i * L];
+        v[Q - 1] = tail_ok ? row[ctail] : -__builtin_inff();
+        float mx = v[0];
+#pragma unroll
+        for (int i = 1; i < Q; ++i) mx = fmaxf(mx, v[i]);
+        mx = group_max<L>(mx);
+        const float mb = -mx * LOG2E;
+        float s = 0.0f;
+#pragma unroll
+        for (int i = 0; i < Q; ++i) s += __builtin_amdgcn_exp2f(__builtin_fmaf(v[i], LOG2E, mb));   // (exp2(-inf) = 0)
+        s = group_sum<L>(s);
+        const float ls = lsm_log_sum(__builtin_amdgcn_logf(s) * LN2, mx, mb);
+        if constexpr (GATHER) {
+            if (h == 0) stat[r] = make_float2(mx, ls);
+        } else if constexpr (MODE == LSM_BWD) {
+            const bool first = r == rr;                // (the row whose pair was requested up front)
+            const CellMap m = first ? pm : map.at((size_t)(row0 + r), V, blank);
+            const float sc = first ? psc : map.scale(bw, m);
+            const float2 g = first ? pg : map.pair(bw, m);
+            if constexpr (CLAMP) {
+                // the clamp behind the sum and in front of the scale: the pair stays unscaled, every lane clamps and scales
+                // what it writes, and lane 0 forms the two one-hot entries whole -- from the logits still in the tile --
+                // and puts them over the row's behind the row pass (lsm_hot_clamped)
+                const float gB = g.x, gL = g.y, gs = gB + gL;
+                const float gq = gs * __builtin_amdgcn_rcpf(s);
+                float hb = 0.0f, hl = 0.0f;
+                if (h == 0) lsm_hot_clamped(row[blank], row[m.label], m.label == blank, mb, gq, gB, gL, bw.clamp, sc, hb, hl);
+#pragma unroll
+                for (int i = 0; i < Q - 1; ++i) row[h + i * L] = lsm_bwd_el_clamped(v[i], mb, gq, bw.clamp, sc);
+                if (tail_ok) row[ctail] = lsm_bwd_el_clamped(v[Q - 1], mb, gq, bw.clamp, sc);
+                if (h == 0) { row[blank] = hb; row[m.label] = hl; }
+            } else {
+                const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
+                const float gq = gs * __builtin_amdgcn_rcpf(s);      // p_j = e_j / s (lsm_log_sum)
+#pragma unroll
+                for (int i = 0; i < Q - 1; ++i) row[h + i * L] = lsm_bwd_el(v[i], mb, gq);
+                if (tail_ok) row[ctail] = lsm_bwd_el(v[Q - 1], mb, gq);
+                // the L lanes of a row sit in one wave and LDS operations of a wave retire in order
+                if (h == 0) { row[blank] += gB; row[m.label] += gL; }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < Q - 1; ++i) row[h + i * L] = lsm_norm_el(v[i], mx, ls);
+            if (tail_ok) row[ctail] = lsm_norm_el(v[Q - 1], mx, ls);
+        }
+    };
+    auto all_rows = [&](auto QC) {
+        for (int r = rr; r < nrows; r += RPP) one_row(QC, r);
+    };
+    switch (q) {
+#define LSM_Q(QQ) case QQ: all_rows(std::integral_constant<int, QQ>{}); break;
+        LSM_Q(9) LSM_Q(10) LSM_Q(11) LSM_Q(12) LSM_Q(13) LSM_Q(14) LSM_Q(15) LSM_Q(16)
+#undef LSM_Q
+        default:      // q <= 8 (V <= 16, or rows shorter than the lane cover): run-time loops
+            for (int r = rr; r < nrows; r += RPP) {
+                float* row = tile + r * V;
+                float mx = -__builtin_inff();
+                for (int i = 0, c = h; i < q - 1; ++i, c += L) mx = fmaxf(mx, row[c]);
+                if (tail_ok) mx = fmaxf(mx, row[ctail]);
+                mx = group_max<L>(mx);
+                const float mb = -mx * LOG2E;
+                float s = 0.0f;
+                for (int i = 0, c = h; i < q - 1; ++i, c += L) s += __builtin_amdgcn_exp2f(__builtin_fmaf(row[c], LOG2E, mb));
+                if (tail_ok) s += __builtin_amdgcn_exp2f(__builtin_fmaf(row[ctail], LOG2E, mb));
+                s = group_sum<L>(s);
+                const float ls = lsm_log_sum(__builtin_amdgcn_logf(s) * LN2, mx, mb);
+                if constexpr (GATHER) {
+                    if (h == 0) stat[r] = make_float2(mx, ls);
+                } else if constexpr (MODE == LSM_BWD) {
+                    const CellMap m = map.at((size_t)(row0 + r), V, blank);
+                    const float sc = map.scale(bw, m);
+                    const float2 g = map.pair(bw, m);
+                    if constexpr (CLAMP) {       // (as in the straight-line form above)
+                        const float gB = g.x, gL = g.y, gs = gB + gL;
+                        const float gq = gs * __builtin_amdgcn_rcpf(s);
+                        float hb = 0.0f, hl = 0.0f;
+                        if (h == 0) lsm_hot_clamped(row[blank], row[m.label], m.label == blank, mb, gq, gB, gL, bw.clamp, sc, hb, hl);
+                        for (int i = 0, c = h; i < q - 1; ++i, c += L) row[c] = lsm_bwd_el_clamped(row[c], mb, gq, bw.clamp, sc);
+                        if (tail_ok) row[ctail] = lsm_bwd_el_clamped(row[ctail], mb, gq, bw.clamp, sc);
+                        if (h == 0) { row[blank] = hb; row[m.label] = hl; }
+                    } else {
+                        const float gB = g.x * sc, gL = g.y * sc, gs = gB + gL;
+                        const float gq = gs * __builtin_amdgcn_rcpf(s);      // p_j = e_j / s (lsm_log_sum)
+                        for (int i = 0, c = h; i < q - 1; ++i, c += L) row[c] = lsm_bwd_el(row[c], mb, gq);
+                        if (tail_ok) row[ctail] = lsm_bwd_el(row[ctail], mb, gq);
+                        // the L lanes of a row sit in one wave and LDS operations of a wave retire in order
+                        if (h == 0) { row[blank] += gB; row[m.label] += gL; }
+                    }
+                } else {
+                    for (int i = 0, c = h; i < q - 1; ++i, c += L) row[c] = lsm_norm_el(row[c], mx, ls);
+                    if (tail_ok) row[ctail] = lsm_norm_el(row[ctail], mx, ls);
+                }
+            }
+    }
+    if constexpr (GATHER && WP) {
+        wave_sync_lds();
+        for (int r = wr0 + lane; r < wr0 + wn; r += WAVE) {
+            const CellMap m = map.at((size_t)(row0 + r), V, blank);
+            const float2 st = stat[r];
+            const float* row = tile + r * V;
+            map.put(out, m, make_float2((row[blank] - st.x) - st.y, (row[m.label] - st.x) - st.y));
+        }
+    } else if constexpr (GATHER) {
+        // one lane per row with all lanes busy (the per-row index arithmetic costs ~60 instructions;
+        // doing it inside the L-lane row loop ran it with a quarter of the lanes)
+        __syncthreads();
+        for (int r = tid; r < nrows; r += SM_THREADS) {
+            const CellMap m = map.at((size_t)(row0 + r), V, blank);
+            const float2 st = stat[r];
+            const float* row = tile + r * V;
+            const float2 pr = make_float2((row[blank] - st.x) - st.y, (row[m.label] - st.x) - st.y);
+            // (written through, sc1: +38 us at c4 -- scattered 8-byte stores need L2 to merge them.  Timing probes that sent
+            // the pairs into a 64 KB region that stays in L2, or stored them in row-major order as coalesced 512-byte runs:
+            // the gather's stores cost 40-55 us in any shape)
+            map.put(out, m, pr);
+        }
+    } else if constexpr (WP) {
+        wave_sync_lds();
+        // the column plane (LsmBwd::col_out): the wave's rows are consecutive, so is its slice of the plane
+        if constexpr (MODE == LSM_NORM) {
+            if (bw.col_out)
+                for (int r = lane; r < wn; r += WAVE) bw.col_out[row0 + wr0 + r] = wtile[r * V + bw.col];
+        }
+        LsmOut<MODE, E>* wdst = out + (row0 + wr0) * V;
+        for (int i = lane; i < wvec; i += WAVE) lsm_st4<NT>(wdst, i, reinterpret_cast<const float4*>(wtile)[i]);
+        for (int e = (wvec << 2) + lane; e < wel; e += WAVE) lsm_st1(wdst + e, wtile[e]);
+    } else {
+        __syncthreads();
+        if constexpr (MODE == LSM_NORM) {      // the column plane: one contiguous run per workgroup
+            if (bw.col_out)
+                for (int r = tid; r < nrows; r += SM_THREADS) bw.col_out[row0 + r] = tile[r * V + bw.col];
+        }
+        LsmOut<MODE, E>* dst = out + row0 * V;
+        for (int i = tid; i < nvec; i += SM_THREADS) lsm_st4<NT>(dst, i, reinterpret_cast<const float4*>(tile)[i]);
+        for (int e = (nvec << 2) + tid; e < nel; e += SM_THREADS) lsm_st1(dst + e, tile[e]);
+    }
 }
-template <typename E, int L, int MODE, bool WP>
+
+// The kernels of the fused families are one template each over the map policy and CLAMP; the body is a function above its
+// kernel, and takes LsmBwd by value as the kernel does (by reference the dense clamped kernels gain a branch per q).
+template <typename E, int L, int MODE, bool WP, bool CLAMP, class Map>
 __global__ void __launch_bounds__(SM_THREADS)
-k_lsm_small_compact_clamped(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int R, int q, int blank,
-                            LsmBwd bw) {
-    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
-    constexpr bool CLAMP = true;
-    CompactMap<false> map{cr, 0, 0};
-#include "lsm_body_small.h"
+k_lsm_small(const E* x, LsmOut<MODE, E>* out, typename Map::Head head, int64_t rows, int V, int R, int q,
+            typename Map::Tail tail, LsmBwd bw) {
+    static_assert(!CLAMP || MODE == LSM_BWD, "the clamp is the backward's");
+    lsm_small_body<E, L, MODE, WP, CLAMP>(x, out, Map::make(head, tail), rows, V, R, q, tail.blank, bw);
 }
 
 // ---------------------------------------------------------------------------
@@ -312,73 +533,194 @@ k_lsm_small_compact_clamped(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int
 // place, 288 GB of traffic) 57.4 -> 51.3 ms per step, c3 (V=5000) 0.708 -> 0.695 ms; loads alone are WORSE (c3 0.733),
 // stores alone neutral (profiles/r03_lg_nt_ab.txt).  The same policy in the fused gather / backward modes: c3 fused forward
 // 0.336 -> 0.325 ms, fused training step 1.051 -> 1.018 ms (profiles/r03_lg_fused_nt_ab.txt)
-template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
-__global__ void __launch_bounds__(LG_THREADS)
-k_lsm_large(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
-            int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
-    constexpr bool CLAMP = false;
-    DenseMap map{labels, T, U};
-#include "lsm_body_large.h"
+template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC, bool CLAMP, class Map>
+__device__ __forceinline__ void lsm_large_body(const E* x, LsmOut<MODE, E>* out, Map map, int64_t rows, int V, int blank,
+                                               LsmBwd bw) {
+    constexpr bool GATHER = MODE == LSM_GATHER;
+    __shared__ float red[LG_THREADS / WAVE];
+    // bw.xcd: every XCD (workgroups go to them by blockIdx mod 8; the grid is a multiple of 8) streams a contiguous
+    // eighth of the rows instead of every eighth row -- see dispatch_lsm
+    const size_t per_xcd = ((size_t)rows + 7) / 8;
+    const size_t items = bw.xcd ? per_xcd * 8 : (size_t)rows;
+    for (size_t it = blockIdx.x; it < items; it += gridDim.x) {
+        const size_t row = bw.xcd ? (it & 7) * per_xcd + (it >> 3) : it;
+        if (row >= (size_t)rows) continue;
+        const E* src = x + row * V;
+        const int nvec = V >> 2;
+        // How a lane's LG_MAXVEC loads are issued (round 5).  As first written -- load and running maximum together under
+        // `if (j < nvec)` -- every load sits in a branch of its own with an s_waitcnt vmcnt(0) behind it: LG_MAXVEC memory
+        // round trips per row, one after the other.  Measured against two loads-first forms (tools/ab_kernels.py, three
+        // interleaved rounds, profiles/r05_loads_first_ab.txt):
+        //   * the read-mostly FUSED modes gain 5-7 % from all loads issued unconditionally at an index clamped into the row,
+        //     what lies beyond the row replaced by -inf afterwards (c3: fused forward 317 -> 300 us, fused backward 739 -> 689);
+        //   * the plain log-softmax -- a read and a write stream at the rate of a copy -- does not: V = 5000 629 -> 647 us,
+        //     4096 596 -> 606, 2048 590 -> 594, nothing at 1000, 3000, 8192; only the three-pass covers of 768 threads and more
+        //     gain (c5's V = 10000: 693 -> 674 clamped, -> 665 with the loads alone under their predicates and the maxima
+        //     behind them), so those take the predicated form and everything else stays as it was.
+        constexpr bool CLAMPED = MODE != LSM_NORM;      // (the load index, not the gradient)
+        constexpr bool PREDICATED = MODE == LSM_NORM && LG_THREADS >= 768;
+        float4 v[LG_MAXVEC];
+        float mx = -__builtin_inff();
+        if constexpr (CLAMPED || PREDICATED) {
+#pragma unroll
+            for (int i = 0; i < LG_MAXVEC; ++i) {
+                const int j = (int)threadIdx.x + i * LG_THREADS;
+                if constexpr (CLAMPED) {
+                    v[i] = lsm_ld4<true>(src, min(j, nvec - 1));
+                } else {
+                    if (j < nvec) v[i] = lsm_ld4<true>(src, j);
+                }
+            }
+        }
+        // what the fused modes need besides the row, requested behind it instead of after the reductions
+        [[maybe_unused]] CellMap m = {0, 0, 0};
+        [[maybe_unused]] float2 side = make_float2(0.0f, 0.0f);      // GATHER: the row's (blank, label) logits; BWD: its gradient pair
+        [[maybe_unused]] float sc = 1.0f;
+        if constexpr (MODE != LSM_NORM) {
+            map.chunk((int64_t)row, (int64_t)row);      // (compact rows: one search per row)
+            m = map.at(row, V, blank);
+            if constexpr (GATHER) {
+                const E* xr = x + row * V;
+                side = make_float2(lsm_ld1(xr + blank), lsm_ld1(xr + m.label));
+            } else {
+                side = map.pair(bw, m);
+                sc = map.scale(bw, m);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < LG_MAXVEC; ++i) {
+            const int j = (int)threadIdx.x + i * LG_THREADS;
+            if constexpr (CLAMPED || PREDICATED) {
+                if (j >= nvec) {
+                    const float ninf = -__builtin_inff();
+                    v[i] = make_float4(ninf, ninf, ninf, ninf);
+                }
+                mx = fmaxf(fmaxf(mx, fmaxf(v[i].x, v[i].y)), fmaxf(v[i].z, v[i].w));
+            } else {
+                if (j < nvec) {
+                    v[i] = lsm_ld4<true>(src, j);
+                    mx = fmaxf(fmaxf(mx, fmaxf(v[i].x, v[i].y)), fmaxf(v[i].z, v[i].w));
+                }
+            }
+        }
+        mx = block_reduce<LG_THREADS>(mx, true, red);
+        const float mb = -mx * LOG2E;
+        float s = 0.0f;
+#pragma unroll
+        for (int i = 0; i < LG_MAXVEC; ++i) {
+            const int j = threadIdx.x + i * LG_THREADS;
+            if (j < nvec)
+                s += (__builtin_amdgcn_exp2f(__builtin_fmaf(v[i].x, LOG2E, mb)) + __builtin_amdgcn_exp2f(__builtin_fmaf(v[i].y, LOG2E, mb))) +
+                     (__builtin_amdgcn_exp2f(__builtin_fmaf(v[i].z, LOG2E, mb)) + __builtin_amdgcn_exp2f(__builtin_fmaf(v[i].w, LOG2E, mb)));
+        }
+        s = block_reduce<LG_THREADS>(s, false, red);
+        const float ls = lsm_log_sum(logf(s), mx, mb);
+        if constexpr (GATHER) {
+            if (threadIdx.x == 0) map.put(out, m, make_float2((side.x - mx) - ls, (side.y - mx) - ls));
+        } else if constexpr (MODE == LSM_BWD) {
+            const float2 g = side;
+            // CLAMP: the pair stays unscaled -- the row is clamped behind the two additions and scaled behind the clamp
+            const float gB = CLAMP ? g.x : g.x * sc, gL = CLAMP ? g.y : g.y * sc, gs = gB + gL;
+            const float gq = gs / s;                                 // p_j = e_j / s (lsm_log_sum)
+            LsmOut<MODE, E>* dst = out + row * V;
+#pragma unroll
+            for (int i = 0; i < LG_MAXVEC; ++i) {
+                const int j = threadIdx.x + i * LG_THREADS;
+                if (j < nvec) {
+                    float o[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+#pragma unroll
+                    for (int cc = 0; cc < 4; ++cc) {
+                        const int e = 4 * j + cc;
+                        float d = lsm_bwd_el(o[cc], mb, gq);
+                        d += (e == blank) ? gB : 0.0f;
+                        d += (e == m.label) ? gL : 0.0f;
+                        if constexpr (CLAMP) d = lsm_clamp_scale(d, bw.clamp, sc);
+                        o[cc] = d;
+                    }
+                    lsm_st4<true>(dst, j, make_float4(o[0], o[1], o[2], o[3]));
+                }
+            }
+        } else {
+            float* dst = out + row * V;
+#pragma unroll
+            for (int i = 0; i < LG_MAXVEC; ++i) {
+                const int j = threadIdx.x + i * LG_THREADS;
+                if (j < nvec) {
+                    const float4 r = make_float4(lsm_norm_el(v[i].x, mx, ls), lsm_norm_el(v[i].y, mx, ls),
+                                                 lsm_norm_el(v[i].z, mx, ls), lsm_norm_el(v[i].w, mx, ls));
+                    lsm_st4<true>(dst, j, r);
+                    // the column plane (LsmBwd::col_out): the one lane that holds the column stores it (a row per workgroup:
+                    // 4 bytes beside 4V)
+                    if (bw.col_out && j == (bw.col >> 2)) {
+                        const int c = bw.col & 3;
+                        bw.col_out[row] = c == 0 ? r.x : (c == 1 ? r.y : (c == 2 ? r.z : r.w));
+                    }
+                }
+            }
+        }
+    }
 }
-template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
-__global__ void __launch_bounds__(LG_THREADS)
-k_lsm_large_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
-    constexpr bool CLAMP = false;
-    CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
-#include "lsm_body_large.h"
-}
-template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
-__global__ void __launch_bounds__(LG_THREADS)
-k_lsm_large_clamped(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
-                    int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
-    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
-    constexpr bool CLAMP = true;
-    DenseMap map{labels, T, U};
-#include "lsm_body_large.h"
-}
-template <typename E, int MODE, int LG_THREADS, int LG_MAXVEC>
-__global__ void __launch_bounds__(LG_THREADS)
-k_lsm_large_compact_clamped(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
-    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
-    constexpr bool CLAMP = true;
-    CompactMap<false> map{cr, 0, 0};
-#include "lsm_body_large.h"
+template <typename E, int MODE, int TH, int NV, bool CLAMP, class Map>
+__global__ void __launch_bounds__(TH)
+k_lsm_large(const E* x, LsmOut<MODE, E>* out, typename Map::Head head, int64_t rows, int V,
+            typename Map::Tail tail, LsmBwd bw) {
+    static_assert(!CLAMP || MODE == LSM_BWD, "the clamp is the backward's");
+    lsm_large_body<E, MODE, TH, NV, CLAMP>(x, out, Map::make(head, tail), rows, V, tail.blank, bw);
 }
 
 // ---------------------------------------------------------------------------
 // Generic fallback (any V, any alignment): one wave per row, three passes.
 // ---------------------------------------------------------------------------
-template <typename E, int MODE>
-__global__ void __launch_bounds__(256)
-k_lsm_generic(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
-              int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
-    constexpr bool CLAMP = false;
-    DenseMap map{labels, T, U};
-#include "lsm_body_generic.h"
+template <typename E, int MODE, bool CLAMP, class Map>
+__device__ __forceinline__ void lsm_generic_body(const E* x, LsmOut<MODE, E>* out, Map map, int64_t rows, int V, int blank,
+                                                 LsmBwd bw) {
+    constexpr bool GATHER = MODE == LSM_GATHER;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    if constexpr (Map::COMPACT) map.chunk(row, row);
+    const E* xr = x + row * V;
+    float mx = -__builtin_inff();
+    for (int c = lane; c < V; c += WAVE) mx = fmaxf(mx, lsm_ld1(xr + c));
+    mx = group_max<WAVE>(mx);
+    float s = 0.0f;
+    for (int c = lane; c < V; c += WAVE) s += expf(lsm_ld1(xr + c) - mx);
+    s = group_sum<WAVE>(s);
+    const float ls = logf(s);
+    if constexpr (GATHER) {
+        if (lane == 0) {
+            const CellMap m = map.at((size_t)row, V, blank);
+            map.put(out, m, make_float2((lsm_ld1(xr + blank) - mx) - ls, (lsm_ld1(xr + m.label) - mx) - ls));
+        }
+    } else if constexpr (MODE == LSM_BWD) {
+        const CellMap m = map.at((size_t)row, V, blank);
+        const float sc = map.scale(bw, m);
+        const float2 g = map.pair(bw, m);
+        // CLAMP: the pair stays unscaled -- the row is clamped behind the two additions and scaled behind the clamp
+        const float gB = CLAMP ? g.x : g.x * sc, gL = CLAMP ? g.y : g.y * sc, gs = gB + gL;
+        LsmOut<MODE, E>* o = out + row * V;
+        for (int c = lane; c < V; c += WAVE) {
+            float d = -expf((lsm_ld1(xr + c) - mx) - ls) * gs;
+            d += (c == blank) ? gB : 0.0f;
+            d += (c == m.label) ? gL : 0.0f;
+            if constexpr (CLAMP) d = lsm_clamp_scale(d, bw.clamp, sc);
+            lsm_st1(o + c, d);
+        }
+    } else {
+        float* o = out + row * V;
+        for (int c = lane; c < V; c += WAVE) {
+            const float r = (lsm_ld1(xr + c) - mx) - ls;
+            o[c] = r;
+            if (bw.col_out && c == bw.col) bw.col_out[row] = r;      // the column plane (LsmBwd::col_out)
+        }
+    }
 }
-template <typename E, int MODE>
+template <typename E, int MODE, bool CLAMP, class Map>
 __global__ void __launch_bounds__(256)
-k_lsm_generic_compact(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
-    constexpr bool CLAMP = false;
-    CompactMap<MODE == LSM_GATHER> map{cr, 0, 0};
-#include "lsm_body_generic.h"
-}
-template <typename E, int MODE>
-__global__ void __launch_bounds__(256)
-k_lsm_generic_clamped(const E* x, LsmOut<MODE, E>* out, const int* __restrict__ labels,
-                      int64_t rows, int V, int T, int U, int blank, LsmBwd bw) {
-    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
-    constexpr bool CLAMP = true;
-    DenseMap map{labels, T, U};
-#include "lsm_body_generic.h"
-}
-template <typename E, int MODE>
-__global__ void __launch_bounds__(256)
-k_lsm_generic_compact_clamped(const E* x, LsmOut<MODE, E>* out, PackedRows cr, int64_t rows, int V, int blank, LsmBwd bw) {
-    static_assert(MODE == LSM_BWD, "the clamp is the backward's");
-    constexpr bool CLAMP = true;
-    CompactMap<false> map{cr, 0, 0};
-#include "lsm_body_generic.h"
+k_lsm_generic(const E* x, LsmOut<MODE, E>* out, typename Map::Head head, int64_t rows, int V,
+              typename Map::Tail tail, LsmBwd bw) {
+    static_assert(!CLAMP || MODE == LSM_BWD, "the clamp is the backward's");
+    lsm_generic_body<E, MODE, CLAMP>(x, out, Map::make(head, tail), rows, V, tail.blank, bw);
 }
 
 // ---------------------------------------------------------------------------
@@ -610,7 +952,7 @@ __device__ __forceinline__ void lsm_rows_stats(const E* const (&src)[RowsShape<L
 #pragma unroll
         for (int i = 0; i < Q; ++i) {
             const unsigned off = i < Q - 1 ? i * L : last_off;
-            const float4 t = lsm_ld4<RNNT_LSM_NT_MODE(MODE)>(src[p], off);
+            const float4 t = lsm_ld4<lsm_nt(MODE)>(src[p], off);
             v[p][i][0] = t.x; v[p][i][1] = t.y; v[p][i][2] = t.z; v[p][i][3] = t.w;
         }
     }
@@ -655,17 +997,48 @@ __device__ __forceinline__ void lsm_rows_stats_of_lane(int lane, const float (&m
 }
 
 // consecutive rows per wave
-template <typename E, int L, int Q>
-__global__ void __launch_bounds__(256)
-k_lsm_rows(const E* x, float* out, const int* __restrict__ labels, int64_t rows, int V, int T, int U, int blank) {
-    DenseMap map{labels, T, U};
-#include "lsm_body_rows.h"
+template <typename E, int L, int Q, class Map>
+__device__ __forceinline__ void lsm_rows_body(const E* x, float* out, Map map, int64_t rows, int V, int blank) {
+    constexpr int MODE = LSM_GATHER, VEC = 4;
+    constexpr int UN = RowsShape<L>::UN, RW = RowsShape<L>::RW, RPW = RowsShape<L>::RPW;
+    const int lane = threadIdx.x & 63, h = lane % L, rr = lane / L;
+    // wave-uniform values kept in scalar registers (the 64-bit row arithmetic runs on the scalar unit)
+    const int64_t row0 = ((int64_t)stream_block() * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * RPW;
+    if (row0 >= rows) return;
+    const bool last_ok = (h + (Q - 1) * L) * VEC < V;   // the lane's last float4 is part of the row
+    const bool whole = row0 + RPW <= rows;              // (uniform) every row of this wave exists
+    if constexpr (Map::COMPACT) map.chunk(row0, min(row0 + RPW, rows) - 1);
+    const E* const wave_src = x + row0 * V;
+    const unsigned lane_off = (unsigned)rr * (unsigned)V + (unsigned)h * VEC;      // floats inside a pass
+    // lane l < RPW owns the pair of row row0 + l.  Its two logits are requested FIRST, next to the row loads that bring
+    // the same lines (asked for after the rows have streamed through, they are fetched a second time: forward 252 vs 216
+    // us at V = 128, profiles/r04_lsm_rows_ab.txt)
+    CellMap cm = {0, 0, 0};
+    float xb = 0.0f, xl = 0.0f;
+    const bool own = lane < RPW && row0 + lane < rows;
+    if (own) {
+        cm = map.at((size_t)(row0 + lane), V, blank);
+        const E* xr = x + (row0 + lane) * V;
+        xb = lsm_ld1(xr + blank);
+        xl = lsm_ld1(xr + cm.label);
+    }
+    const E* src[UN];
+#pragma unroll
+    for (int p = 0; p < UN; ++p) {
+        src[p] = wave_src + (size_t)(p * RW) * V + lane_off;
+        // (rows past the end of the tensor -- last wave only -- re-read the last row and are dropped at the stores)
+        if (!whole && row0 + p * RW + rr >= rows) src[p] = x + (rows - 1) * V + h * VEC;
+    }
+    float mx[UN], ls[UN];
+    lsm_rows_stats<E, L, Q, MODE>(src, last_ok, mx, ls);
+    float m, lg;
+    lsm_rows_stats_of_lane<L>(lane, mx, ls, m, lg);
+    if (own) map.put(out, cm, make_float2((xb - m) - lg, (xl - m) - lg));
 }
-template <typename E, int L, int Q>
+template <typename E, int L, int Q, class Map>
 __global__ void __launch_bounds__(256)
-k_lsm_rows_compact(const E* x, float* out, PackedRows cr, int64_t rows, int V, int blank) {
-    CompactMap<true> map{cr, 0, 0};
-#include "lsm_body_rows.h"
+k_lsm_rows(const E* x, float* out, typename Map::Head head, int64_t rows, int V, typename Map::Tail tail) {
+    lsm_rows_body<E, L, Q>(x, out, Map::make(head, tail), rows, V, tail.blank);
 }
 
 // Along the diagonals (rows that are one or two whole 128-byte lines: V = 32, 64; T >= 16): a wave takes the 16 cells
@@ -716,65 +1089,18 @@ k_lsm_rows_diag(const E* x, float* out, const int* __restrict__ labels, int V, i
     if (own) reinterpret_cast<float2*>(out)[(plane + r) * U + u0 + lane] = make_float2((xb - m) - lg, (xl - m) - lg);
 }
 
-// One launch of a fused log-softmax kernel family, dense or compact by the map policy; CLAMP (LSM_BWD only): the clamped
-// twin of the same kernel, in the same launch shape.
-template <typename E, int L, int MODE, bool WP, bool CLAMP, class Map>
-static void launch_lsm_small(unsigned grid, size_t lds, hipStream_t stream, const E* x, LsmOut<MODE, E>* out,
-                             const Map& map, int64_t rows, int V, int R, int q, int blank, LsmBwd bw) {
-    if constexpr (CLAMP && Map::COMPACT)
-        k_lsm_small_compact_clamped<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.r, rows, V, R, q, blank,
-                                                                                       bw);
-    else if constexpr (CLAMP)
-        k_lsm_small_clamped<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.labels, rows, V, R, q, map.T,
-                                                                               map.U, blank, bw);
-    else if constexpr (Map::COMPACT)
-        k_lsm_small_compact<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.r, rows, V, R, q, blank, bw);
-    else
-        k_lsm_small<E, L, MODE, WP><<<grid, SM_THREADS, lds, stream>>>(x, out, map.labels, rows, V, R, q, map.T, map.U,
-                                                                       blank, bw);
-}
-template <typename E, int MODE, int TH, int NV, bool CLAMP, class Map>
-static void launch_lsm_large(unsigned grid, hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const Map& map,
-                             int64_t rows, int V, int blank, LsmBwd bw) {
-    if constexpr (CLAMP && Map::COMPACT)
-        k_lsm_large_compact_clamped<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
-    else if constexpr (CLAMP)
-        k_lsm_large_clamped<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
-    else if constexpr (Map::COMPACT)
-        k_lsm_large_compact<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
-    else
-        k_lsm_large<E, MODE, TH, NV><<<grid, TH, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
-}
-template <typename E, int MODE, bool CLAMP, class Map>
-static void launch_lsm_generic(unsigned grid, hipStream_t stream, const E* x, LsmOut<MODE, E>* out, const Map& map,
-                               int64_t rows, int V, int blank, LsmBwd bw) {
-    if constexpr (CLAMP && Map::COMPACT)
-        k_lsm_generic_compact_clamped<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
-    else if constexpr (CLAMP)
-        k_lsm_generic_clamped<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
-    else if constexpr (Map::COMPACT)
-        k_lsm_generic_compact<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.r, rows, V, blank, bw);
-    else
-        k_lsm_generic<E, MODE><<<grid, 256, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank, bw);
-}
-template <typename E, int L, int Q, class Map>
-static void launch_lsm_rows(unsigned grid, hipStream_t stream, const E* x, float* out, const Map& map, int64_t rows,
-                            int V, int blank) {
-    if constexpr (Map::COMPACT)
-        k_lsm_rows_compact<E, L, Q><<<grid, 256, 0, stream>>>(x, out, map.r, rows, V, blank);
-    else
-        k_lsm_rows<E, L, Q><<<grid, 256, 0, stream>>>(x, out, map.labels, rows, V, map.T, map.U, blank);
-}
-
 // What the plan says, launched: a switch on the family and on its template selectors, nothing decided here.
 // E: the storage type of x (and of out in LSM_BWD).  Map: the row -> cell policy (DenseMap, CompactMap).  CLAMP: the clamped
-// twins of the plan's kernel (LSM_BWD, whose plans name SMALL, LARGE or GENERIC).
+// instantiation of the plan's kernel (LSM_BWD, whose plans name SMALL, LARGE or GENERIC), in the same launch shape.
 template <int MODE, typename E, bool CLAMP, class Map>
 static hipError_t launch_lsm_plan(hipStream_t stream, const LsmPlan& p, const E* x, LsmOut<MODE, E>* out, const Map& map,
                                   int64_t rows, int V, int blank, LsmBwd bw) {
     bw.xcd = p.xcd;
-#define LSM_LARGE(TH_, NV_) \
-    if (p.TH == TH_ && p.NV == NV_) launch_lsm_large<E, MODE, TH_, NV_, CLAMP>(p.grid, stream, x, out, map, rows, V, blank, bw);
+    const typename Map::Head head = map.head();
+    const typename Map::Tail tail = map.tail(blank);
+#define LSM_LARGE(TH_, NV_)         \
+    if (p.TH == TH_ && p.NV == NV_) \
+        k_lsm_large<E, MODE, TH_, NV_, CLAMP, Map><<<p.grid, TH_, 0, stream>>>(x, out, head, rows, V, tail, bw);
     switch (p.family) {
         case LsmFamily::REGS:
             if constexpr (MODE == LSM_NORM) {
@@ -799,7 +1125,7 @@ static hipError_t launch_lsm_plan(hipStream_t stream, const LsmPlan& p, const E*
         case LsmFamily::ROWS:
             if constexpr (MODE == LSM_GATHER) {
 #define LSM_ROWS(LL, QQ) \
-    if (p.L == LL && p.Q == QQ) launch_lsm_rows<E, LL, QQ>(p.grid, stream, x, out, map, rows, V, blank);
+    if (p.L == LL && p.Q == QQ) k_lsm_rows<E, LL, QQ, Map><<<p.grid, 256, 0, stream>>>(x, out, head, rows, V, tail);
 #define LSM_ROWS_L(LL) LSM_ROWS(LL, 1) LSM_ROWS(LL, 2) LSM_ROWS(LL, 3) LSM_ROWS(LL, 4)
                 LSM_ROWS_L(8) LSM_ROWS_L(16) LSM_ROWS_L(32) LSM_ROWS_L(64)
 #undef LSM_ROWS_L
@@ -814,18 +1140,20 @@ static hipError_t launch_lsm_plan(hipStream_t stream, const LsmPlan& p, const E*
             }
             break;
         case LsmFamily::SMALL:
-#define LSM_SMALL(LL)                                                                                            \
-    case LL:                                                                                                     \
-        if (p.WP)                                                                                                \
-            launch_lsm_small<E, LL, MODE, (LL <= 16), CLAMP>(p.grid, p.lds_bytes, stream, x, out, map, rows, V, p.R, p.q, blank, bw); \
-        else                                                                                                     \
-            launch_lsm_small<E, LL, MODE, false, CLAMP>(p.grid, p.lds_bytes, stream, x, out, map, rows, V, p.R, p.q, blank, bw);     \
+#define LSM_SMALL_WP(LL, WP_)                                                                                  \
+    k_lsm_small<E, LL, MODE, WP_, CLAMP, Map><<<p.grid, SM_THREADS, p.lds_bytes, stream>>>(x, out, head, rows, V, p.R, p.q, \
+                                                                                           tail, bw)
+#define LSM_SMALL(LL)                          \
+    case LL:                                   \
+        if (p.WP) LSM_SMALL_WP(LL, (LL <= 16)); \
+        else LSM_SMALL_WP(LL, false);          \
         break;
             switch (p.L) {
                 LSM_SMALL(1) LSM_SMALL(2) LSM_SMALL(4) LSM_SMALL(8) LSM_SMALL(16) LSM_SMALL(32)
                 LSM_SMALL(64)
             }
 #undef LSM_SMALL
+#undef LSM_SMALL_WP
             break;
         case LsmFamily::LARGE:
             if constexpr (MODE == LSM_NORM) {
@@ -836,7 +1164,7 @@ static hipError_t launch_lsm_plan(hipStream_t stream, const LsmPlan& p, const E*
             }
             break;
         case LsmFamily::GENERIC:
-            launch_lsm_generic<E, MODE, CLAMP>(p.grid, stream, x, out, map, rows, V, blank, bw);
+            k_lsm_generic<E, MODE, CLAMP, Map><<<p.grid, 256, 0, stream>>>(x, out, head, rows, V, tail, bw);
             break;
     }
 #undef LSM_LARGE
@@ -885,7 +1213,7 @@ template <typename E> struct LsmOps {
                                         int col);
     static hipError_t gather(hipStream_t stream, const E* logits, const int* labels, float* ws2, int N, int T, int U, int V,
                              int blank);
-    // clamp > 0: the clamped twins (LsmBwd::clamp); 0: the kernels that have always been here
+    // clamp > 0: the CLAMP instantiations (LsmBwd::clamp); 0: the kernels that have always been here
     static hipError_t backward(hipStream_t stream, const E* logits, const int* labels, const float* g2_diagonal,
                                const float* scale, E* dlogits, int N, int T, int U, int V, int blank, float clamp);
     static hipError_t gather_compact(hipStream_t stream, const E* logits, float* ws2, const PackedRows& cr, int V, int blank);
