@@ -95,8 +95,15 @@ DROPOUT_SYMBOLS = {
     "rnnt_amd_joint_backward_dropout": (_i, SYMBOLS["rnnt_amd_joint_backward"][1] + [_f, _vp]),
     "rnnt_amd_joint_dropout_mask_host": (_i, [_u64, _f, _i, _i, _i, _i, _vp]),
 }
+# every symbol include/warp_rnnt_amd_hat.h declares (the factorised-blank loss on the fused path; additive: it did not move
+# the version): the forward is rnnt_amd_loss_logits without its grads_kind, the backward rnnt_amd_logits_backward_typed
+HAT_SYMBOLS = {
+    "rnnt_amd_hat_loss_logits": (_i, [_vp, _vp, _i] + [_vp] * 6 + [_i] * 5 + [_f]),
+    "rnnt_amd_hat_logits_backward": (_i, [_vp, _i] + [_vp] * 5 + [_i] * 5),
+}
 # additive tables: (symbols, the header that declares them)
-ADDITIVE = ((CLAMP_SYMBOLS, "warp_rnnt_amd_clamp.h"), (DROPOUT_SYMBOLS, "warp_rnnt_amd_joint_dropout.h"))
+ADDITIVE = ((CLAMP_SYMBOLS, "warp_rnnt_amd_clamp.h"), (DROPOUT_SYMBOLS, "warp_rnnt_amd_joint_dropout.h"),
+            (HAT_SYMBOLS, "warp_rnnt_amd_hat.h"))
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to

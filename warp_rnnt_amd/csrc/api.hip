@@ -3,11 +3,13 @@
 #include "../../include/warp_rnnt_amd.h"
 #include "../../include/warp_rnnt_amd_clamp.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
+#include "../../include/warp_rnnt_amd_hat.h"
 
 #include <cstdio>
 #include <cstdlib>
 
 #include "common.h"
+#include "hat.h"
 #include "kernels.h"
 #include "philox.h"
 
@@ -745,6 +747,36 @@ rnntStatus_t rnnt_amd_logits_backward(rnntStream_t stream, const float* logits, 
                                       int N, int T, int U, int V, int blank) {
     return rnnt_amd_logits_backward_typed(stream, RNNT_DTYPE_F32, logits, labels, grads_diagonal, grad_costs, dlogits, N, T,
                                           U, V, blank);
+}
+
+// include/warp_rnnt_amd_hat.h: the factorised-blank (HAT) loss.  joint_loss's shape below: a producer of its own (hat.hip)
+// fills the pair plane, the sweeps and the gradient pairs are the standard ones; the backward is one streaming launch.
+rnntStatus_t rnnt_amd_hat_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                      const int* labels, const int* xn, const int* yn, float* costs, float* grads, int N,
+                                      int T, int U, int V, int blank, float fastemit_lambda) {
+    if (!dtype_ok(dtype) || !dims_ok(N, T, U) || V < 2 || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !logits || !xn || !yn || !costs || (U > 1 && !labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Workspace w;
+    carve(workspace, N, T, U, &w);
+    if (launch_hat_gather_skewed(stream, dtype, logits, labels, w.ws2, N, T, U, V, blank) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    return sweeps_and_pair_grads(stream, w, xn, yn, costs, grads ? grads : w.ws2, WRITE_SKEWED2, N, T, U, nullptr,
+                                 fastemit_lambda);
+}
+
+rnntStatus_t rnnt_amd_hat_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* labels,
+                                          const float* grads_diagonal, const float* grad_costs, void* dlogits, int N,
+                                          int T, int U, int V, int blank) {
+    if (!dtype_ok(dtype) || !dims_ok(N, T, U) || V < 2 || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!logits || !grads_diagonal || !aligned(grads_diagonal, 8) || !dlogits || (U > 1 && !labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    if (launch_hat_logits_backward(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
+        hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
 }
 
 // The joint network fused into the loss (joint.hip).  Workspace: rnnt_amd_workspace_size's carve, then W^T (H,Vp) for

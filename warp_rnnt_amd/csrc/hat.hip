@@ -1,0 +1,377 @@
+// The factorised-blank (HAT) transducer loss, Variani et al. 2020: the two streaming kernels that stand where the fused
+// log-softmax + gather and the fused d/d logits stand in the standard loss (hat.h).  The lattice between
+// them -- sweeps, costs, gradient pairs -- is the standard one.
+//
+// Per lattice cell, logits z[0..V), b = blank, sp(x) = max(x,0) + log1p(exp(-|x|)):
+//     lpB   = -sp(-z_b)                       log sigmoid(z_b)
+//     lnb   = -sp( z_b)                       log(1 - sigmoid(z_b))
+//     m     = max_{v != b} z_v,  s = sum_{v != b} exp(z_v - m)
+//     lp[v] = ((z_v - m) - log s) + lnb       v != b
+// and from the gradient pair (gB, gL) of the cell, sig = sigmoid(z_b), q_v = exp((z_v - m) - log s):
+//     u_b = gB (1 - sig) - gL sig,    u_v = gL ([v == label] - q_v),    dz = scale_n * u, rounded once to the logits' type.
+// z_v - m is formed first and alone, so nothing but z_b moves under a shift of the non-blank logits.
+//
+// One map from the elements of a row to lanes and registers at every storage type and every access width: the row is
+// cut into chunks of 8 elements, chunk c of a row is held by lane c mod G of the row's group, in ascending order of c; a
+// lane adds its elements up in ascending order and the lanes are combined by the xor butterfly of streaming.h.  An element
+// at or past V, the blank and a masked logit (-inf) all enter the maximum as -inf and the sum as +0.  So a row's bits are
+// a function of the row, V, the blank and the label (the backward: its pair and scale as well) -- not of the storage type
+// (bf16 / fp16 rows give the bits of their fp32 upcast), not of the access width, not of where the row lies.
+//   rows of up to 1024 elements: a group of G = 16, 32 or 64 lanes per row (the smallest with V <= 16 G), the row read
+//   once into 16 registers per lane, reduction and output pass from the registers;
+//   longer rows: a wave per row, running maximum and sum in one pass, the backward reads the row a second time for its
+//   output pass (20 KB at V = 5000: from L2).
+// A chunk is one 16-byte access (two for fp32) where the row pitch V * sizeof(E) and the tensors' addresses are multiples
+// of 16; otherwise accesses of 8, 4 or 2 bytes, the widest that pitch and addresses allow (V = 50 in fp32: 8 bytes).
+// No LDS, no atomics, nothing between workgroups.
+#include <type_traits>
+
+#include "hat.h"
+#include "streaming.h"
+#include "../../include/warp_rnnt_amd.h"
+
+// every product and sum below is rounded on its own: no fused multiply-add is formed, the same source gives the same bits
+// at the three storage types, and a bf16 / fp16 result is the fp32 result rounded once (hat_store8 has the one exception
+// the compiler makes to that, and what stops it)
+#pragma clang fp contract(off)
+
+namespace rnnt {
+namespace {
+
+constexpr int HAT_THREADS = 256;
+constexpr int HAT_CHUNK = 8;             // elements per chunk
+constexpr int HAT_SMALL_V = 1024;        // rows up to here are held in registers: 2 chunks per lane, 64 lanes at the most
+constexpr float HAT_NEG_INF = -__builtin_inff();
+
+// An access moves ACC bytes = NV elements: 16, 8, 4 (or, in half precision, 2) -- the largest power of two that divides the
+// row pitch V * sizeof(E) and the tensors' addresses, so every access of a row is aligned and lies below V whole or not
+// at all.  Which elements a lane holds does not depend on it.
+template <typename T, int NV> struct HatVec { typedef T type __attribute__((ext_vector_type(NV))); };
+template <typename T> struct HatVec<T, 1> { typedef T type; };
+template <typename T, int NV> using hat_vec_t = typename HatVec<T, NV>::type;
+
+// Elements e0 .. e0+7 of the row at xr as floats; -inf at and past V
+template <typename E, int ACC, bool NT>
+__device__ __forceinline__ void hat_load8(const E* __restrict__ xr, int e0, int V, float (&z)[HAT_CHUNK]) {
+    constexpr int NV = ACC / (int)sizeof(E);
+    static_assert(NV == 1 || NV == 2 || NV == 4 || NV == 8, "2 to 16 bytes, whole elements");
+#pragma unroll
+    for (int k = 0; k < HAT_CHUNK; k += NV) {
+        if constexpr (NV == 1) {
+            z[k] = e0 + k < V ? (float)xr[e0 + k] : HAT_NEG_INF;
+        } else {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) z[k + i] = HAT_NEG_INF;
+            if (e0 + k < V) {
+                const hat_vec_t<E, NV>* p = reinterpret_cast<const hat_vec_t<E, NV>*>(xr + e0 + k);
+                hat_vec_t<E, NV> h;
+                if constexpr (NT) h = __builtin_nontemporal_load(p); else h = *p;
+                const hat_vec_t<float, NV> v = __builtin_convertvector(h, hat_vec_t<float, NV>);
+#pragma unroll
+                for (int i = 0; i < NV; ++i) z[k + i] = v[i];
+            }
+        }
+    }
+}
+
+// ... and d[0..7] to elements e0 .. e0+7 of the row at o, below V only, converted to E (round to nearest even) as stored
+template <typename E, int ACC>
+__device__ __forceinline__ void hat_store8(E* __restrict__ o, int e0, int V, const float (&d)[HAT_CHUNK]) {
+    constexpr int NV = ACC / (int)sizeof(E);
+#pragma unroll
+    for (int k = 0; k < HAT_CHUNK; k += NV) {
+        if (e0 + k >= V) continue;
+        if constexpr (NV > 1) {
+            hat_vec_t<float, NV> v;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) v[i] = d[k + i];
+            __builtin_nontemporal_store(__builtin_convertvector(v, hat_vec_t<E, NV>),
+                                        reinterpret_cast<hat_vec_t<E, NV>*>(o + e0 + k));
+        } else if constexpr (std::is_same_v<E, float>) {
+            o[e0 + k] = d[k];
+        } else {
+            // (the median of d, d, d is d: an instruction between the multiply that made d and the cast.  Without it a
+            //  scalar fp16 cast takes that multiply with it -- v_fma_mixlo_f16, one rounding of the exact product -- and
+            //  a half result is no longer the fp32 result rounded once.  The packed conversions above take none.)
+            o[e0 + k] = (E)__builtin_amdgcn_fmed3f(d[k], d[k], d[k]);
+        }
+    }
+}
+
+__device__ __forceinline__ float hat_exp(float d) { return __builtin_amdgcn_exp2f(d * LOG2E); }   // d <= 0; exp(-inf) = +0
+__device__ __forceinline__ float hat_softplus(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
+
+// What the forward stores for a cell: lpB, and lp[label] -- lpB again where the label channel is the blank's (the last
+// column; a padded label), as the standard gather does
+__device__ __forceinline__ float2 hat_pair(float zb, float zl, int label, int blank, float m, float ls) {
+    const float lpB = -hat_softplus(-zb);
+    const float lnb = -hat_softplus(zb);
+    return make_float2(lpB, label == blank ? lpB : ((zl - m) - ls) + lnb);
+}
+
+// What the backward needs of a cell behind its row statistics
+struct HatCellGrad {
+    float ub;      // scale * u_b
+    float gL, sc;
+    int label;
+};
+__device__ __forceinline__ HatCellGrad hat_cell_grad(float zb, float2 g, float sc, int label) {
+    const float e = expf(-fabsf(zb)), den = 1.0f + e;
+    const float big = 1.0f / den, small = e / den;            // sigmoid(|z_b|), sigmoid(-|z_b|)
+    const float sig = zb >= 0.0f ? big : small, nsig = zb >= 0.0f ? small : big;
+    return {sc * (g.x * nsig - g.y * sig), g.y, sc, label};
+}
+__device__ __forceinline__ float hat_dz(const HatCellGrad& c, float z, int idx, int blank, float m, float ls) {
+    const float q = hat_exp((z - m) - ls);                    // (z = -inf at the blank, past V and at masked logits: q = +0)
+    const float u = c.gL * ((idx == c.label ? 1.0f : 0.0f) - q);
+    return idx == blank ? c.ub : c.sc * u;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Rows of up to 1024 elements: a group of G lanes per row, chunks `lane` and `G + lane` in 16 registers
+// ---------------------------------------------------------------------------------------------------------
+// (a row of up to 8 G elements has no second chunk in any lane: it is neither loaded nor worked on -- what it would add,
+//  -inf to the maximum and +0 to the sum, changes no bit)
+template <int G> __device__ __forceinline__ int hat_small_chunks(int V) { return V > G * HAT_CHUNK ? 2 : 1; }
+
+template <typename E, int G, int ACC>
+__device__ __forceinline__ void hat_small_stats(const E* __restrict__ xr, int lane, int V, int blank, float (&z)[2][HAT_CHUNK],
+                                                float& m, float& ls) {
+    const int chunks = hat_small_chunks<G>(V);
+    hat_load8<E, ACC, true>(xr, lane * HAT_CHUNK, V, z[0]);
+    if (chunks > 1) hat_load8<E, ACC, true>(xr, (G + lane) * HAT_CHUNK, V, z[1]);
+    m = HAT_NEG_INF;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (k < chunks) {
+#pragma unroll
+            for (int i = 0; i < HAT_CHUNK; ++i) {
+                if ((k * G + lane) * HAT_CHUNK + i == blank) z[k][i] = HAT_NEG_INF;
+                m = fmaxf(m, z[k][i]);
+            }
+        }
+    }
+    m = group_max<G>(m);
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (k < chunks) {
+#pragma unroll
+            for (int i = 0; i < HAT_CHUNK; ++i) s += hat_exp(z[k][i] - m);
+        }
+    }
+    ls = logf(group_sum<G>(s));
+}
+
+template <typename E, int G, int ACC>
+__global__ void __launch_bounds__(HAT_THREADS)
+k_hat_gather_small(const E* __restrict__ x, const int* __restrict__ labels, float2* __restrict__ ws2, size_t rows, int T,
+                   int U, int V, int blank) {
+    const size_t row = (size_t)blockIdx.x * (HAT_THREADS / G) + threadIdx.x / G;
+    if (row >= rows) return;
+    const int lane = threadIdx.x % G;
+    const E* xr = x + row * (size_t)V;
+    // (the cell's label and its two logits are asked for in front of the row, not behind its reduction: three memory
+    //  round trips that then overlap the row's)
+    const CellMap c = map_cell(row, labels, T, U, V, blank);
+    const float zb = (float)xr[blank], zl = (float)xr[c.label];
+    float z[2][HAT_CHUNK], m, ls;
+    hat_small_stats<E, G, ACC>(xr, lane, V, blank, z, m, ls);
+    if (lane == 0) ws2[c.sk] = hat_pair(zb, zl, c.label, blank, m, ls);
+}
+
+template <typename E, int G, int ACC>
+__global__ void __launch_bounds__(HAT_THREADS)
+k_hat_backward_small(const E* __restrict__ x, const int* __restrict__ labels, const float2* __restrict__ g2,
+                     const float* __restrict__ scale, E* __restrict__ out, size_t rows, int T, int U, int V, int blank) {
+    const size_t row = (size_t)blockIdx.x * (HAT_THREADS / G) + threadIdx.x / G;
+    if (row >= rows) return;
+    const int lane = threadIdx.x % G;
+    const E* xr = x + row * (size_t)V;
+    const CellMap c = map_cell(row, labels, T, U, V, blank);          // (in front of the row: as in the gather)
+    const float zb = (float)xr[blank], sc = scale ? scale[c.n] : 1.0f;
+    const float2 g = g2[c.sk];
+    float z[2][HAT_CHUNK], m, ls;
+    hat_small_stats<E, G, ACC>(xr, lane, V, blank, z, m, ls);
+    const HatCellGrad cg = hat_cell_grad(zb, g, sc, c.label);
+    E* o = out + row * (size_t)V;
+    const int chunks = hat_small_chunks<G>(V);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (k >= chunks) break;
+        const int e0 = (k * G + lane) * HAT_CHUNK;
+        float d[HAT_CHUNK];
+#pragma unroll
+        for (int i = 0; i < HAT_CHUNK; ++i) d[i] = hat_dz(cg, z[k][i], e0 + i, blank, m, ls);
+        hat_store8<E, ACC>(o, e0, V, d);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Longer rows: a wave per row, chunks lane, 64 + lane, ...; running maximum and sum per lane in one pass
+// ---------------------------------------------------------------------------------------------------------
+template <typename E, int ACC, bool NT>
+__device__ __forceinline__ void hat_wave_stats(const E* __restrict__ xr, int lane, int V, int blank, float& m, float& ls) {
+    float ml = HAT_NEG_INF, s = 0.0f;
+    for (int e0 = lane * HAT_CHUNK; e0 < V; e0 += WAVE * HAT_CHUNK) {
+        float z[HAT_CHUNK];
+        hat_load8<E, ACC, NT>(xr, e0, V, z);
+        float mn = ml;
+#pragma unroll
+        for (int i = 0; i < HAT_CHUNK; ++i) {
+            if (e0 + i == blank) z[i] = HAT_NEG_INF;
+            mn = fmaxf(mn, z[i]);
+        }
+        if (mn > HAT_NEG_INF) {               // (a lane that has seen nothing but -inf keeps s = 0)
+            s = s * hat_exp(ml - mn);         // exp(0) = 1 exactly where the maximum stays; 0 * exp(-inf) = 0 at the start
+#pragma unroll
+            for (int i = 0; i < HAT_CHUNK; ++i) s += hat_exp(z[i] - mn);
+            ml = mn;
+        }
+    }
+    m = group_max<WAVE>(ml);
+    ls = logf(group_sum<WAVE>(s * hat_exp(ml - m)));
+}
+
+template <typename E, int ACC>
+__global__ void __launch_bounds__(HAT_THREADS)
+k_hat_gather_wave(const E* __restrict__ x, const int* __restrict__ labels, float2* __restrict__ ws2, size_t rows, int T,
+                  int U, int V, int blank) {
+    const size_t row = (size_t)blockIdx.x * (HAT_THREADS / WAVE) + threadIdx.x / WAVE;
+    if (row >= rows) return;
+    const int lane = threadIdx.x % WAVE;
+    const E* xr = x + row * (size_t)V;
+    const CellMap c = map_cell(row, labels, T, U, V, blank);
+    const float zb = (float)xr[blank], zl = (float)xr[c.label];
+    float m, ls;
+    hat_wave_stats<E, ACC, true>(xr, lane, V, blank, m, ls);
+    if (lane == 0) ws2[c.sk] = hat_pair(zb, zl, c.label, blank, m, ls);
+}
+
+template <typename E, int ACC>
+__global__ void __launch_bounds__(HAT_THREADS)
+k_hat_backward_wave(const E* __restrict__ x, const int* __restrict__ labels, const float2* __restrict__ g2,
+                    const float* __restrict__ scale, E* __restrict__ out, size_t rows, int T, int U, int V, int blank) {
+    const size_t row = (size_t)blockIdx.x * (HAT_THREADS / WAVE) + threadIdx.x / WAVE;
+    if (row >= rows) return;
+    const int lane = threadIdx.x % WAVE;
+    const E* xr = x + row * (size_t)V;
+    const CellMap c = map_cell(row, labels, T, U, V, blank);
+    const float zb = (float)xr[blank], sc = scale ? scale[c.n] : 1.0f;
+    const float2 g = g2[c.sk];
+    float m, ls;
+    hat_wave_stats<E, ACC, false>(xr, lane, V, blank, m, ls);      // (plain loads: the output pass reads the row again)
+    const HatCellGrad cg = hat_cell_grad(zb, g, sc, c.label);
+    E* o = out + row * (size_t)V;
+    for (int e0 = lane * HAT_CHUNK; e0 < V; e0 += WAVE * HAT_CHUNK) {
+        float z[HAT_CHUNK], d[HAT_CHUNK];
+        hat_load8<E, ACC, true>(xr, e0, V, z);
+#pragma unroll
+        for (int i = 0; i < HAT_CHUNK; ++i) d[i] = hat_dz(cg, e0 + i == blank ? HAT_NEG_INF : z[i], e0 + i, blank, m, ls);
+        hat_store8<E, ACC>(o, e0, V, d);
+    }
+}
+
+// The form of a call, a function of V alone: lanes per row (0: a wave per row, the long form) and workgroups
+struct HatShape {
+    int G;
+    unsigned grid;
+};
+inline HatShape hat_shape(size_t rows, int V) {
+    const int G = V > HAT_SMALL_V ? 0 : V <= 16 * 16 ? 16 : V <= 16 * 32 ? 32 : 64;
+    const size_t per = HAT_THREADS / (G ? G : WAVE);
+    return {G, (unsigned)((rows + per - 1) / per)};        // rows < 2^32 (the C ABI's dims_ok): at most 2^28 workgroups
+}
+
+// The widest access of hat_load8 / hat_store8 that the row pitch and the addresses allow
+template <typename E> inline int hat_access(int V, const void* a, const void* b) {
+    const uintptr_t bits = (uintptr_t)V * sizeof(E) | reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | 16;
+    return (int)(bits & (~bits + 1));          // lowest set bit: 16, 8, 4 or 2 (1 is not a tensor of E)
+}
+
+// launch(kernel) with the instantiation of the call's form and access out of K_SMALL<E, G, ACC> / K_WAVE<E, ACC>
+#define HAT_FORMS(ACC)                                                   \
+    switch (sh.G) {                                                      \
+        case 16: launch(K_SMALL(16, ACC)); break;                        \
+        case 32: launch(K_SMALL(32, ACC)); break;                        \
+        case 64: launch(K_SMALL(64, ACC)); break;                        \
+        default: launch(K_WAVE(ACC)); break;                             \
+    }
+#define HAT_DISPATCH()                                                   \
+    switch (acc) {                                                       \
+        case 16: HAT_FORMS(16) break;                                    \
+        case 8: HAT_FORMS(8) break;                                      \
+        case 4: HAT_FORMS(4) break;                                      \
+        case 2: if constexpr (sizeof(E) == 2) { HAT_FORMS(2) break; }    \
+        default: return hipErrorInvalidValue;                            \
+    }
+
+template <typename E>
+hipError_t hat_gather(hipStream_t stream, const E* x, const int* labels, float* ws2, int N, int T, int U, int V, int blank) {
+    const size_t rows = (size_t)N * T * U;
+    if (rows == 0) return hipSuccess;
+    const int acc = hat_access<E>(V, x, nullptr);
+    const HatShape sh = hat_shape(rows, V);
+    float2* out = reinterpret_cast<float2*>(ws2);
+    const auto launch = [&](auto kernel) { kernel<<<sh.grid, HAT_THREADS, 0, stream>>>(x, labels, out, rows, T, U, V, blank); };
+#define K_SMALL(G, ACC) k_hat_gather_small<E, G, ACC>
+#define K_WAVE(ACC) k_hat_gather_wave<E, ACC>
+    HAT_DISPATCH()
+#undef K_SMALL
+#undef K_WAVE
+    return hipGetLastError();
+}
+
+template <typename E>
+hipError_t hat_backward(hipStream_t stream, const E* x, const int* labels, const float* g2_diagonal, const float* scale,
+                        E* dx, int N, int T, int U, int V, int blank) {
+    const size_t rows = (size_t)N * T * U;
+    if (rows == 0) return hipSuccess;
+    const int acc = hat_access<E>(V, x, dx);
+    const HatShape sh = hat_shape(rows, V);
+    const float2* g2 = reinterpret_cast<const float2*>(g2_diagonal);
+    const auto launch = [&](auto kernel) {
+        kernel<<<sh.grid, HAT_THREADS, 0, stream>>>(x, labels, g2, scale, dx, rows, T, U, V, blank);
+    };
+#define K_SMALL(G, ACC) k_hat_backward_small<E, G, ACC>
+#define K_WAVE(ACC) k_hat_backward_wave<E, ACC>
+    HAT_DISPATCH()
+#undef K_SMALL
+#undef K_WAVE
+    return hipGetLastError();
+}
+#undef HAT_DISPATCH
+#undef HAT_FORMS
+
+}  // namespace
+
+hipError_t launch_hat_gather_skewed(hipStream_t stream, int dtype, const void* logits, const int* labels, float* ws2,
+                                    int N, int T, int U, int V, int blank) {
+    if (V < 2 || blank < 0 || blank >= V) return hipErrorInvalidValue;
+    switch (dtype) {
+        case RNNT_DTYPE_F32: return hat_gather(stream, static_cast<const float*>(logits), labels, ws2, N, T, U, V, blank);
+        case RNNT_DTYPE_BF16: return hat_gather(stream, static_cast<const __bf16*>(logits), labels, ws2, N, T, U, V, blank);
+        case RNNT_DTYPE_F16: return hat_gather(stream, static_cast<const _Float16*>(logits), labels, ws2, N, T, U, V, blank);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_hat_logits_backward(hipStream_t stream, int dtype, const void* logits, const int* labels,
+                                      const float* g2_diagonal, const float* scale, void* dlogits, int N, int T, int U,
+                                      int V, int blank) {
+    if (V < 2 || blank < 0 || blank >= V) return hipErrorInvalidValue;
+    switch (dtype) {
+        case RNNT_DTYPE_F32:
+            return hat_backward(stream, static_cast<const float*>(logits), labels, g2_diagonal, scale,
+                                static_cast<float*>(dlogits), N, T, U, V, blank);
+        case RNNT_DTYPE_BF16:
+            return hat_backward(stream, static_cast<const __bf16*>(logits), labels, g2_diagonal, scale,
+                                static_cast<__bf16*>(dlogits), N, T, U, V, blank);
+        case RNNT_DTYPE_F16:
+            return hat_backward(stream, static_cast<const _Float16*>(logits), labels, g2_diagonal, scale,
+                                static_cast<_Float16*>(dlogits), N, T, U, V, blank);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace rnnt

@@ -544,3 +544,41 @@ def joint_backward(f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs, a
         else:
             _check(L.rnnt_amd_joint_backward(*args))
     return df, dg, dw, db
+
+
+def hat_loss(logits, labels, xn, yn, blank=0, fastemit_lambda=0.0, with_grads=True):
+    """The factorised-blank (HAT) loss on the fused path (include/warp_rnnt_amd_hat.h): logits (N,T,U,V) fp32 / bf16 /
+    fp16, validated by the caller.  Returns costs (N,) fp32 and, with_grads, the gradient pairs (N,T,U,2) fp32 in the
+    diagonal-major layout -- what :func:`hat_logits_backward` reads (else None)."""
+    L = _lib.load()
+    N, T, U, V = logits.shape
+    dev = logits.device
+    if V < 2 or not 0 <= blank < V:
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the HAT loss needs V >= 2 and a blank "
+                           f"that is a vocabulary index (V={V}, blank={blank})")
+    _mismatch.poll(dev)
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        grads = torch.empty((N, T, U, 2), dtype=torch.float32, device=dev) if with_grads else None
+        if N == 0:
+            return costs, grads
+        ws = _workspace(dev, L.rnnt_amd_workspace_size, "N T U", N, T, U)
+        _check(L.rnnt_amd_hat_loss_logits(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
+                                          _ptr(labels), xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(grads),
+                                          N, T, U, V, blank, float(fastemit_lambda)))
+    return costs, grads
+
+
+def hat_logits_backward(logits, labels, grads, grad_costs, blank=0):
+    """d(sum_n grad_costs[n]*cost[n]) / d(logits) of :func:`hat_loss`, in the logits' dtype (the fp32 result rounded
+    once); grads: the pairs the forward returned."""
+    L = _lib.load()
+    N, T, U, V = logits.shape
+    dev = logits.device
+    with torch.cuda.device(dev):
+        out = torch.empty_like(logits)
+        if N == 0:
+            return out
+        _check(L.rnnt_amd_hat_logits_backward(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(), _ptr(labels),
+                                              grads.data_ptr(), _ptr(grad_costs), out.data_ptr(), N, T, U, V, blank))
+    return out
