@@ -101,9 +101,17 @@ HAT_SYMBOLS = {
     "rnnt_amd_hat_loss_logits": (_i, [_vp, _vp, _i] + [_vp] * 6 + [_i] * 5 + [_f]),
     "rnnt_amd_hat_logits_backward": (_i, [_vp, _i] + [_vp] * 5 + [_i] * 5),
 }
+# every symbol include/warp_rnnt_amd_align.h declares (best-path alignments from the loss lattice; additive: it did not move
+# the version): the size is rnnt_amd_workspace_size's, the call is (stream, workspace, input_kind, dtype, input, labels,
+# xn, yn, scores, emit_frames, N, T, U, V, blank)
+ALIGN_IN_HAT_LOGITS = 3      # input_kind of rnnt_amd_align beside the three IN_* above
+ALIGN_SYMBOLS = {
+    "rnnt_amd_align_workspace_size": (_sz, [_i, _i, _i]),
+    "rnnt_amd_align": (_i, [_vp, _vp, _i, _i] + [_vp] * 6 + [_i] * 5),
+}
 # additive tables: (symbols, the header that declares them)
 ADDITIVE = ((CLAMP_SYMBOLS, "warp_rnnt_amd_clamp.h"), (DROPOUT_SYMBOLS, "warp_rnnt_amd_joint_dropout.h"),
-            (HAT_SYMBOLS, "warp_rnnt_amd_hat.h"))
+            (HAT_SYMBOLS, "warp_rnnt_amd_hat.h"), (ALIGN_SYMBOLS, "warp_rnnt_amd_align.h"))
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to

@@ -4,10 +4,12 @@
 #include "../../include/warp_rnnt_amd_clamp.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
 #include "../../include/warp_rnnt_amd_hat.h"
+#include "../../include/warp_rnnt_amd_align.h"
 
 #include <cstdio>
 #include <cstdlib>
 
+#include "align.h"
 #include "common.h"
 #include "hat.h"
 #include "kernels.h"
@@ -776,6 +778,67 @@ rnntStatus_t rnnt_amd_hat_logits_backward(rnntStream_t stream, int dtype, const 
     if (launch_hat_logits_backward(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
         hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_align.h: best-path alignments.  A producer of the loss fills the pair plane -- and leaves it
+// filled -- the max-plus sweep and the trace of align.hip take the place of the alpha / beta sweeps.  Workspace:
+// rnnt_amd_workspace_size's carve, then the decision words, then the columns parked between column stripes.
+namespace {
+struct AlignWorkspace {
+    unsigned long long* words;
+    float* park;
+};
+size_t carve_align(void* base, int N, int T, int U, AlignWorkspace* aw) {
+    size_t off = carve(base, N, T, U, nullptr);
+    char* p = static_cast<char*>(base);
+    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return p ? p + o : nullptr; };
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(take(align_word_count(N, T, U) * 8));
+    float* park = reinterpret_cast<float*>(take(align_park_count(N, T, U) * sizeof(float)));
+    if (aw) *aw = AlignWorkspace{words, park};
+    return off;
+}
+}  // namespace
+
+size_t rnnt_amd_align_workspace_size(int N, int T, int U) {
+    if (!dims_ok(N, T, U)) return 0;
+    return carve_align(nullptr, N, T, U, nullptr);
+}
+
+rnntStatus_t rnnt_amd_align(rnntStream_t stream, void* workspace, int input_kind, int dtype, const void* input,
+                            const int* labels, const int* xn, const int* yn, float* scores, int* emit_frames, int N, int T,
+                            int U, int V, int blank) {
+    const bool log_probs = input_kind == RNNT_IN_LOG_PROBS_DENSE || input_kind == RNNT_IN_LOG_PROBS_GATHERED;
+    if (!log_probs && input_kind != RNNT_IN_LOGITS_DENSE && input_kind != RNNT_ALIGN_IN_HAT_LOGITS)
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dtype_ok(dtype) || (log_probs && dtype != RNNT_DTYPE_F32)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dims_ok(N, T, U) || !workspace_ok(workspace)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!input || !xn || !yn || !scores || (U > 1 && !emit_frames)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (input_kind != RNNT_IN_LOG_PROBS_GATHERED &&
+        (!vocab_ok(V, blank) || (input_kind == RNNT_ALIGN_IN_HAT_LOGITS && V < 2) || (U > 1 && !labels)))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+
+    Workspace w;
+    carve(workspace, N, T, U, &w);
+    AlignWorkspace aw;
+    carve_align(workspace, N, T, U, &aw);
+    hipError_t e;
+    switch (input_kind) {
+        case RNNT_IN_LOG_PROBS_DENSE:
+            e = launch_gather(stream, static_cast<const float*>(input), labels, w.ws2, N, T, U, V, blank, true); break;
+        case RNNT_IN_LOG_PROBS_GATHERED:
+            e = launch_reskew(stream, static_cast<const float*>(input), w.ws2, N, T, U); break;
+        case RNNT_IN_LOGITS_DENSE:
+            e = launch_log_softmax_gather_skewed(stream, dtype, input, labels, w.ws2, N, T, U, V, blank); break;
+        default:
+            e = launch_hat_gather_skewed(stream, dtype, input, labels, w.ws2, N, T, U, V, blank); break;
+    }
+    if (e != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
+    if (launch_align_sweep(stream, w.ws2, xn, yn, aw.words, aw.park, scores, N, T, U) != hipSuccess)
+        return RNNT_STATUS_WARP_FAILED;
+    if (launch_align_trace(stream, aw.words, xn, yn, scores, emit_frames, N, T, U) != hipSuccess)
+        return RNNT_STATUS_WARP_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
 

@@ -582,3 +582,34 @@ def hat_logits_backward(logits, labels, grads, grad_costs, blank=0):
         _check(L.rnnt_amd_hat_logits_backward(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(), _ptr(labels),
                                               grads.data_ptr(), _ptr(grad_costs), out.data_ptr(), N, T, U, V, blank))
     return out
+
+
+ALIGN_IN_HAT_LOGITS = _lib.ALIGN_IN_HAT_LOGITS
+
+
+def align(input, labels, xn, yn, input_kind, blank=0):
+    """Best-path alignments from the loss lattice (include/warp_rnnt_amd_align.h): ``input`` as :func:`loss` takes it for
+    IN_LOG_PROBS_DENSE / IN_LOG_PROBS_GATHERED / IN_LOGITS_DENSE, or logits read the HAT way for ALIGN_IN_HAT_LOGITS;
+    validated by the caller.  Returns scores (N,) fp32 -- the log-probability of the best path -- and emit_frames (N,U-1)
+    int32: the frame at which label u is emitted, -1 behind yn[n]."""
+    L = _lib.load()
+    N, T, U, V = input.shape
+    dev = input.device
+    if input_kind == IN_LOG_PROBS_GATHERED:
+        blank = 0          # channel 0 of the 2-channel layout
+    elif input_kind == ALIGN_IN_HAT_LOGITS and (V < 2 or not 0 <= blank < V):
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the HAT loss needs V >= 2 and a blank "
+                           f"that is a vocabulary index (V={V}, blank={blank})")
+    elif not 0 <= blank < V:
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): blank={blank} is not a "
+                           f"vocabulary index of xs (V={V})")
+    with torch.cuda.device(dev):
+        scores = torch.empty((N,), dtype=torch.float32, device=dev)
+        emit_frames = torch.empty((N, U - 1), dtype=torch.int32, device=dev)
+        if N == 0:
+            return scores, emit_frames
+        ws = _workspace(dev, L.rnnt_amd_align_workspace_size, "N T U", N, T, U)
+        _check(L.rnnt_amd_align(_stream(dev), ws.data_ptr(), input_kind, LOGITS_DTYPES[input.dtype], input.data_ptr(),
+                                _ptr(labels), xn.data_ptr(), yn.data_ptr(), scores.data_ptr(),
+                                emit_frames.data_ptr(), N, T, U, V, blank))
+    return scores, emit_frames
