@@ -13,7 +13,7 @@ bit (tests/test_gpu_dense_layout.py names its one exception).
 """
 import numpy as np
 
-ALIGN = 256           # every plane of the workspace starts on a multiple of this many bytes (api.hip)
+ALIGN = 256           # every plane of the workspace starts on a multiple of this many bytes (api_common.h)
 INT_MIN = -2 ** 31
 
 
@@ -123,7 +123,7 @@ def label_equals_blank(labels, N, T, U, V, blank):
 # The workspace
 # ---------------------------------------------------------------------------------------------------------------------
 def workspace_offsets(N, T, U):
-    """Byte offsets of the planes rnnt_amd_loss carves out of its workspace (include/warp_rnnt_amd.h, api.hip): alphas,
+    """Byte offsets of the planes rnnt_amd_loss carves out of its workspace (include/warp_rnnt_amd.h, api_common.h: loss_layout): alphas,
     betas (4 bytes per cell each), the diagonal-major pair plane (8 per cell), the N log-likelihoods, the N mismatch
     words; every plane on a multiple of 256 bytes."""
     cells = int(N) * int(T) * int(U)

@@ -2,7 +2,7 @@
 """Generates tests/golden/host_decisions.json: what the C ABI decides on the host alone.
 
 Two tables, recorded from a build of the library (the in-tree one, or the path given as the first argument):
-  sizes  every workspace size / offset entry over a grid of shapes -- padded, compact, bounded, joint; valid and invalid,
+  sizes  every workspace size / offset entry over a grid of shapes -- padded, compact, bounded, joint, align; valid and invalid,
          including both sides of each limit of the size checks;
   calls  for every status-returning entry the calls it answers WITHOUT launching anything: each reason it has to reject a
          call, one at a time (status 5), and its early successes (N == 0, STU == 0 where that is one, nothing requested).
@@ -42,7 +42,8 @@ JOINT = [(2, 5, 3, 64, 8), (16, 150, 40, 640, 1024), (1, 1, 1, 32, 2), (1, 1, 1,
          (2, 5, 3, 64, (1 << 24) + 1), (16, 1 << 14, 1 << 14, 64, 8)]
 SIZES = [("rnnt_amd_workspace_size", PADDED), ("rnnt_amd_workspace_mismatch_offset", PADDED),
          ("rnnt_amd_debug_redo_offset", PADDED), ("rnnt_amd_workspace_size_compact", COMPACT),
-         ("rnnt_amd_workspace_size_compact_bounded", COMPACT), ("rnnt_amd_joint_workspace_size", JOINT)]
+         ("rnnt_amd_workspace_size_compact_bounded", COMPACT), ("rnnt_amd_joint_workspace_size", JOINT),
+         ("rnnt_amd_align_workspace_size", PADDED)]
 
 BAD_DIMS = [dict(N=-1), dict(T=0), dict(U=0), dict(N=65536), dict(T=1 << 15, U=1 << 14), dict(N=16, T=1 << 14, U=1 << 14)]
 BAD_COMPACT_DIMS = [dict(N=-1), dict(N=65536), dict(STU=-1), dict(STU=1 << 32), dict(Tmax=1 << 15, Umax=1 << 14),
@@ -192,9 +193,10 @@ ENTRIES = {
 
 def load(path):
     L = ctypes.CDLL(path)
-    for name, (res, args) in _lib.SYMBOLS.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = res, args
+    for table in [_lib.SYMBOLS] + [t for t, _ in _lib.ADDITIVE]:
+        for name, (res, args) in table.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
     return L
 
 

@@ -240,7 +240,7 @@ def test_reference_named_compact_entry_points():
 def test_reference_named_compact_entry_points_staged(N, Tm, Um, V, kernel):
     """From 2^20 cells of launch bound on run_warp_rnnt_compact turns the row-major pairs into per-utterance
     diagonal-major planes inside the caller's `grads`, sweeps on the tuned kernels and turns the gradient pairs back
-    (csrc/api.hip).  Against the oracle, ragged, FastEmit; bit-equal to the native compact entry, which runs the same
+    (csrc/api_reference.hip).  Against the oracle, ragged, FastEmit; bit-equal to the native compact entry, which runs the same
     kernels on 64-bit offsets."""
     import warp_rnnt_amd
     import warp_rnnt._C as core

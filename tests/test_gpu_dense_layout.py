@@ -41,7 +41,7 @@ DEV = "cuda:0"
 GUARD = 64                   # floats in front of and behind every output
 GUARD_VALUE = -77.0
 NAN_BITS = 0x7FC00000        # what torch.full(..., nan) writes
-STAGED_FROM_CELLS = 1 << 20  # api.hip: from here on the gathered gradients are turned through LDS tiles
+STAGED_FROM_CELLS = 1 << 20  # api_common.h: from here on the gathered gradients are turned through LDS tiles
 IN_DENSE, IN_GATHERED = 0, 1
 GRADS_GATHERED, GRADS_DIAGONAL, GRADS_DENSE = 0, 1, 2
 
@@ -256,7 +256,7 @@ def ragged(N, T, U):
 # ---------------------------------------------------------------------------------------------------------------------
 def relayout(N, T, U, seed):
     """RNNT_IN_LOG_PROBS_GATHERED with RNNT_GRADS_GATHERED_DIAGONAL: the only kind whose gradients go straight to the caller
-    (api.hip: every other kind of >= 2^20 cells, and NONE and DENSE at any size, produce theirs in the pair plane), so the
+    (api_loss.hip: every other kind of >= 2^20 cells, and NONE and DENSE at any size, produce theirs in the pair plane), so the
     plane k_to_diagonal<false> wrote is still there when the call is over."""
     lp2 = real_pairs(N, T, U, seed)
     xn, yn = ragged(N, T, U)

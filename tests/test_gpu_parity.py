@@ -162,7 +162,7 @@ def test_seeded_vs_oracle_all_entry_points(N, T, U, V, ragged, lam, blank):
 
 
 def test_staged_forms_of_the_entry_points_from_a_million_cells_on():
-    """From 2^20 lattice cells on (csrc/api.hip: STAGED_FROM_CELLS) the reference-named C entry points stage the pairs
+    """From 2^20 lattice cells on (csrc/api_common.h: STAGED_FROM_CELLS) the reference-named C entry points stage the pairs
     in the caller's `grads`, sweep on the tuned kernels, park the gradient pairs in alphas / betas and turn the layout
     through LDS tiles (gathered) or expand whole dense rows (dense, which then no longer depends on the caller's
     zero-fill); the native gathered-gradient form takes the tiled turn as well.  All of them against the fp32 oracle,
@@ -720,7 +720,7 @@ def test_masked_log_probs_nan_pattern_equals_the_oracles(N, T, U, V):
 
 
 def test_the_reference_named_entry_points_give_one_utterance_the_same_bits_in_any_batch():
-    """csrc/api.hip: run_warp_rnnt / run_warp_rnnt_gather take the staged forms from 2^20 cells on and the direct ones
+    """csrc/api_reference.hip: run_warp_rnnt / run_warp_rnnt_gather take the staged forms from 2^20 cells on and the direct ones
     below -- different kernels (the tuned column-block kernels on a staged plane / the single-role kernel on the
     caller's layout), one arithmetic: an utterance's costs and gradients do not depend on the batch it came in."""
     T, U, V, lam = 300, 200, 5, 0.01

@@ -1,16 +1,12 @@
-"""The gradient clamp of the fused path, without a GPU: the two C entries of include/warp_rnnt_amd_clamp.h (declared in a
-header and bound in a table of their own, exported, refusing bad arguments before any HIP call, answering what their
-unclamped twins answer without a launch) and the device-free parts of warp_rnnt_amd.compat."""
+"""The gradient clamp of the fused path, without a GPU: the two C entries of include/warp_rnnt_amd_clamp.h (their twins'
+argument lists and a float, refusing bad arguments before any HIP call, answering what their unclamped twins answer without
+a launch) and the device-free parts of warp_rnnt_amd.compat."""
 import ctypes
 import math
-import os
-import re
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"rnnt_amd_logits_backward_clamped", "rnnt_amd_compact_logits_backward_clamped"}
 INVALID, SUCCESS = 5, 0
 
@@ -22,53 +18,20 @@ def _lib():
     return warp_rnnt_amd.load()
 
 
-def _declared():
-    hdr = open(os.path.join(ROOT, "include", "warp_rnnt_amd_clamp.h")).read()
-    return set(re.findall(r"\b(run_[a-z_]+|rnnt_amd_[a-z_]+)\s*\(", hdr))
-
-
-def test_clamp_header_declares_what_the_table_binds_and_the_library_exports():
-    import warp_rnnt_amd
-    from warp_rnnt_amd import _build, _lib as lib
-    L = _lib()
-    declared = _declared()
-    assert declared == ENTRIES
-    assert declared == set(lib.CLAMP_SYMBOLS)
-    assert not declared & set(lib.SYMBOLS)
-    main = open(os.path.join(ROOT, "include", "warp_rnnt_amd.h")).read()
-    for name in declared:
-        assert name not in main                       # a header of their own
-    assert '#include "warp_rnnt_amd.h"' in open(os.path.join(ROOT, "include", "warp_rnnt_amd_clamp.h")).read()
-    syms = subprocess.check_output(["nm", "-D", "--defined-only", warp_rnnt_amd.lib_path()]).decode()
-    for name in declared:
-        assert re.search(r"\bT " + name + r"\b", syms), name
-        fn = getattr(L, name)
-        res, args = lib.CLAMP_SYMBOLS[name]
-        assert fn.restype is res and list(fn.argtypes) == list(args)      # bound by load()
-        assert args[-1] is ctypes.c_float
-    # the arguments of the twin and a float behind them
+def test_clamped_entries_take_the_arguments_of_their_twins_and_a_float_behind_them():
+    """(What every additive header owes -- declared, bound, exported, a stale library refused: test_host_additive_abi.py.)"""
+    from warp_rnnt_amd import _lib as lib
+    assert set(lib.CLAMP_SYMBOLS) == ENTRIES
+    for name in ENTRIES:
+        assert lib.CLAMP_SYMBOLS[name][1][-1] is ctypes.c_float
     assert lib.CLAMP_SYMBOLS["rnnt_amd_logits_backward_clamped"][1][:-1] == lib.SYMBOLS["rnnt_amd_logits_backward_typed"][1]
     assert (lib.CLAMP_SYMBOLS["rnnt_amd_compact_logits_backward_clamped"][1][:-1] ==
             lib.SYMBOLS["rnnt_amd_compact_logits_backward"][1])
-    # part of the build's fingerprint
-    assert any(os.path.basename(h) == "warp_rnnt_amd_clamp.h" for h in _build.HEADERS)
-    for h in _build.HEADERS:
-        assert os.path.exists(os.path.join(_build.CSRC, h)), h
 
 
 def test_clamp_entries_do_not_move_the_abi_version():
     from warp_rnnt_amd import _lib as lib
     assert _lib().rnnt_amd_version() == lib.ABI_VERSION == 110
-
-
-def test_library_without_the_clamp_entries_is_refused_with_the_rebuild_message(monkeypatch):
-    """A stale library (same version number, built before the entries existed) must not surface as an AttributeError."""
-    from warp_rnnt_amd import _lib as lib
-    _lib()
-    monkeypatch.setattr(lib, "_lib", None)
-    monkeypatch.setitem(lib.CLAMP_SYMBOLS, "rnnt_amd_no_such_entry_clamped", (ctypes.c_int, [ctypes.c_float]))
-    with pytest.raises(RuntimeError, match="rebuild it"):
-        lib.load()
 
 
 def test_clamped_entries_refuse_before_any_hip_call():

@@ -1,6 +1,7 @@
 """The host-side decisions of the C ABI, replayed from tests/golden/host_decisions.json (tests/golden/make_host_decisions.py
-wrote it from a build of the commit before api.hip's entries were folded onto one workspace, one tail and one compact core):
-every workspace size and offset over a grid of shapes, and for every status-returning entry the calls it answers without a
+wrote it from a build of the commit before the C ABI's entries were folded onto one workspace, one tail and one compact
+core; the rows of rnnt_amd_align_workspace_size from the commit before the host layer was split by entry family): every
+workspace size and offset over a grid of shapes, and for every status-returning entry the calls it answers without a
 launch -- each rejection reason one at a time, and the early successes."""
 import json
 import os
@@ -27,7 +28,8 @@ def test_sizes_offsets_and_launch_free_answers_are_the_recorded_ones():
                "rnnt_amd_debug_get_lattice_kernel", "rnnt_amd_debug_last_lattice_kernel",
                "rnnt_amd_debug_lattice_plan", "rnnt_amd_debug_lsm_plan"}     # (no status, or no arguments)
     assert {row[0] for row in table["calls"]} == entries - no_rows
-    assert {row[0] for row in table["sizes"]} == {fn for fn, (res, _) in _lib.SYMBOLS.items() if res is _lib._sz}
+    tables = [_lib.SYMBOLS] + [t for t, _ in _lib.ADDITIVE]       # (the size entries of the additive headers as well)
+    assert {row[0] for row in table["sizes"]} == {fn for t in tables for fn, (res, _) in t.items() if res is _lib._sz}
     wrong = [(fn, args, want, getattr(L, fn)(*args)) for fn, args, want in table["sizes"]
              if getattr(L, fn)(*args) != want]
     assert not wrong, wrong

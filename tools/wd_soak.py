@@ -76,7 +76,7 @@ def child(seconds, seed):
     def planes(c):
         cells = c["N"] * c["T"] * c["U"]
         w = c["ws"]
-        return w[:4 * cells].view(torch.float32), w[4 * cells:8 * cells].view(torch.float32)   # alphas, betas (api.hip: carve)
+        return w[:4 * cells].view(torch.float32), w[4 * cells:8 * cells].view(torch.float32)   # alphas, betas (api_common.h: loss_layout)
 
     def same(a, b):      # bit equality that takes NaN == NaN of the same payload (the planes of ragged batches hold padding)
         return torch.equal(a.view(torch.int32), b.view(torch.int32))

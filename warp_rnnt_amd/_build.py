@@ -13,10 +13,10 @@ from . import _isa_check
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwarp_rnnt_amd.so")
-SOURCES = ["api.hip", "lattice.hip", "lattice_ws.hip", "lattice_wd.hip", "grads.hip", "lsm_f32.hip", "lsm_bf16.hip",
-           "lsm_f16.hip", "lsm_backward.hip", "to_diagonal.hip", "compact.hip", "expand.hip", "joint.hip", "hat.hip",
-           "align.hip"]
-HEADERS = ["common.h", "kernels.h", "lattice_plan.h", "lattice_launch.h", "lattice_step.h", "lattice_wd_body.h",
+SOURCES = ["api_loss.hip", "api_compact.hip", "api_reference.hip", "api_fused.hip", "lattice.hip", "lattice_ws.hip",
+           "lattice_wd.hip", "grads.hip", "lsm_f32.hip", "lsm_bf16.hip", "lsm_f16.hip", "lsm_backward.hip", "to_diagonal.hip",
+           "compact.hip", "expand.hip", "joint.hip", "hat.hip", "align.hip"]
+HEADERS = ["api_common.h", "common.h", "kernels.h", "lattice_plan.h", "lattice_launch.h", "lattice_step.h", "lattice_wd_body.h",
            "lattice_single.h", "grads_cell.h", "streaming.h", "lsm_plan.h", "lsm.h", "philox.h", "hat.h", "align.h",
            os.path.join("..", "..", "include", "warp_rnnt_amd.h"), os.path.join("..", "..", "include", "warp_rnnt_amd_clamp.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_joint_dropout.h"),

@@ -1,0 +1,239 @@
+// C ABI of libwarp_rnnt_amd.so, the fused family: a producer of its own in front of the loss's sweeps -- or a sweep of its
+// own behind one of the loss's producers.  The joint network (include/warp_rnnt_amd.h) and its dropout
+// (include/warp_rnnt_amd_joint_dropout.h), the factorised-blank loss (include/warp_rnnt_amd_hat.h), best-path alignments
+// (include/warp_rnnt_amd_align.h).  Host-side orchestration only: argument checks, workspace carving, launches.
+#include "../../include/warp_rnnt_amd_align.h"
+#include "../../include/warp_rnnt_amd_hat.h"
+#include "../../include/warp_rnnt_amd_joint_dropout.h"
+
+#include "align.h"
+#include "api_common.h"
+#include "hat.h"
+#include "philox.h"
+
+using namespace rnnt;
+
+namespace {
+
+// The joint network fused into the loss (joint.hip).  Behind the loss layout: W^T (H,Vp) for the backward, then the
+// weight kernel's fp32 partials (splits x Vp x H and splits x Vp), splits sized for fp32 (the most a dtype takes).
+struct JointWorkspace {
+    void* wt;
+    float* dw_part;
+    float* db_part;
+};
+JointWorkspace joint_layout(Carver& c, int N, int T, int U, int H, int V) {
+    const size_t vp = (size_t)joint_vpad(V), splits = (size_t)joint_w_splits(N, T, U, H, V, RNNT_DTYPE_F32);
+    JointWorkspace jw;
+    jw.wt = c.take<float>((size_t)H * vp);
+    jw.dw_part = c.take<float>(splits * vp * H);
+    jw.db_part = c.take<float>(splits * vp);
+    return jw;
+}
+bool joint_args_ok(int dtype, int activation, int N, int T, int U, int H, int V, int blank) {
+    return dtype_ok(dtype) && (activation == RNNT_ACT_TANH || activation == RNNT_ACT_RELU) && dims_ok(N, T, U) &&
+           H >= 32 && H <= 1024 && H % 32 == 0 && V >= 2 && V <= (1 << 24) && vocab_ok(V, blank);
+}
+// f, g and the weight are read in 16-byte words, the bias (optional) as floats
+inline bool joint_inputs_aligned(const void* f, const void* g, const void* weight, const float* bias) {
+    return aligned(f, 16) && aligned(g, 16) && aligned(weight, 16) && aligned(bias, 4);
+}
+
+// p, seed: the dropout of include/warp_rnnt_amd_joint_dropout.h (p == 0: none, seed unread)
+rnntStatus_t joint_loss(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f, const void* g,
+                        const void* weight, const float* bias, const int* labels, const int* xn, const int* yn,
+                        float* costs, float* lse, float* grads, int N, int T, int U, int H, int V, int blank,
+                        float fastemit_lambda, float p, const uint64_t* seed) {
+    if (!joint_args_ok(dtype, activation, N, T, U, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !f || !g || !weight || !xn || !yn || !costs || labels_missing(U, labels) ||
+        (grads && !lse))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!joint_inputs_aligned(f, g, weight, bias) || !aligned(lse, 8)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const Workspace w = loss_layout(c, N, T, U);
+    // 1. z tile by tile: the (blank,label) log-prob pairs into the pair plane (launch_log_softmax_gather_skewed's
+    //    layout), (max, log sum) per cell
+    if (launch_joint_fwd(stream, dtype, activation, f, g, weight, bias, labels, xn, yn, w.ws2, grads ? lse : nullptr, N,
+                         T, U, H, V, blank, p, seed) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    // 2. + 3. as rnnt_amd_loss_logits(RNNT_GRADS_GATHERED_DIAGONAL or RNNT_GRADS_NONE)
+    return sweeps_and_pair_grads(stream, w, xn, yn, costs, grads ? grads : w.ws2, WRITE_SKEWED2, N, T, U, nullptr,
+                                 fastemit_lambda);
+}
+
+rnntStatus_t joint_backward(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                            const void* g, const void* weight, const float* bias, const int* labels, const int* xn,
+                            const int* yn, const float* lse, const float* grads, const float* grad_costs, void* df,
+                            void* dg, float* dweight, float* dbias, int N, int T, int U, int H, int V, int blank, float p,
+                            const uint64_t* seed) {
+    if (!joint_args_ok(dtype, activation, N, T, U, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !f || !g || !weight || !xn || !yn || !lse || !grads || labels_missing(U, labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!joint_inputs_aligned(f, g, weight, bias) || !aligned(grads, 8) || !aligned(lse, 8))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0 || (!df && !dg && !dweight && !dbias)) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    loss_layout(c, N, T, U);
+    const JointWorkspace jw = joint_layout(c, N, T, U, H, V);
+    if (launch_joint_bwd(stream, dtype, activation, f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs, jw.wt,
+                         jw.dw_part, jw.db_part, joint_w_splits(N, T, U, H, V, dtype), df, dg, dweight, dbias, N, T, U,
+                         H, V, blank, p, seed) != hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// the dropout of the *_dropout entries: p in [0,1) (false for a NaN); p > 0 needs the device word
+inline bool dropout_ok(float p, const uint64_t* seed) {
+    return p >= 0.0f && p < 1.0f && (p == 0.0f || (seed && aligned(seed, 8)));
+}
+
+// Best-path alignments.  Behind the loss layout: the decision words, then the columns parked between column stripes.
+struct AlignWorkspace {
+    unsigned long long* words;
+    float* park;
+};
+AlignWorkspace align_layout(Carver& c, int N, int T, int U) {
+    AlignWorkspace aw;
+    aw.words = c.take<unsigned long long>(align_word_count(N, T, U));
+    aw.park = c.take<float>(align_park_count(N, T, U));
+    return aw;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t rnnt_amd_joint_workspace_size(int N, int T, int U, int H, int V) {
+    if (!joint_args_ok(RNNT_DTYPE_F32, RNNT_ACT_TANH, N, T, U, H, V, 0)) return 0;
+    Carver c(nullptr);
+    loss_layout(c, N, T, U);
+    joint_layout(c, N, T, U, H, V);
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_joint_loss(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                 const void* g, const void* weight, const float* bias, const int* labels, const int* xn,
+                                 const int* yn, float* costs, float* lse, float* grads, int N, int T, int U, int H, int V,
+                                 int blank, float fastemit_lambda) {
+    return joint_loss(stream, workspace, dtype, activation, f, g, weight, bias, labels, xn, yn, costs, lse, grads, N, T, U,
+                      H, V, blank, fastemit_lambda, 0.0f, nullptr);
+}
+
+rnntStatus_t rnnt_amd_joint_backward(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                     const void* g, const void* weight, const float* bias, const int* labels,
+                                     const int* xn, const int* yn, const float* lse, const float* grads,
+                                     const float* grad_costs, void* df, void* dg, float* dweight, float* dbias, int N,
+                                     int T, int U, int H, int V, int blank) {
+    return joint_backward(stream, workspace, dtype, activation, f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs,
+                          df, dg, dweight, dbias, N, T, U, H, V, blank, 0.0f, nullptr);
+}
+
+// include/warp_rnnt_amd_joint_dropout.h: the same with dropout between the activation and the projection.  p == 0 IS the
+// entry above (seed unread).
+rnntStatus_t rnnt_amd_joint_loss_dropout(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                         const void* g, const void* weight, const float* bias, const int* labels,
+                                         const int* xn, const int* yn, float* costs, float* lse, float* grads, int N,
+                                         int T, int U, int H, int V, int blank, float fastemit_lambda, float p,
+                                         const uint64_t* seed) {
+    if (!dropout_ok(p, seed)) return RNNT_STATUS_INVALID_ARGUMENT;
+    return joint_loss(stream, workspace, dtype, activation, f, g, weight, bias, labels, xn, yn, costs, lse, grads, N, T, U,
+                      H, V, blank, fastemit_lambda, p, p > 0.0f ? seed : nullptr);
+}
+
+rnntStatus_t rnnt_amd_joint_backward_dropout(rnntStream_t stream, void* workspace, int dtype, int activation,
+                                             const void* f, const void* g, const void* weight, const float* bias,
+                                             const int* labels, const int* xn, const int* yn, const float* lse,
+                                             const float* grads, const float* grad_costs, void* df, void* dg,
+                                             float* dweight, float* dbias, int N, int T, int U, int H, int V, int blank,
+                                             float p, const uint64_t* seed) {
+    if (!dropout_ok(p, seed)) return RNNT_STATUS_INVALID_ARGUMENT;
+    return joint_backward(stream, workspace, dtype, activation, f, g, weight, bias, labels, xn, yn, lse, grads, grad_costs,
+                          df, dg, dweight, dbias, N, T, U, H, V, blank, p, p > 0.0f ? seed : nullptr);
+}
+
+// The keep mask of those entries on the host (philox.h is one definition for both sides): no HIP call.
+rnntStatus_t rnnt_amd_joint_dropout_mask_host(uint64_t seed, float p, int N, int T, int U, int H, unsigned char* keep) {
+    if (!(p >= 0.0f && p < 1.0f) || N < 0 || T < 0 || U < 0 || H < 0 || !keep) return RNNT_STATUS_INVALID_ARGUMENT;
+    const uint32_t thr = dropout_threshold(p);
+    for (int n = 0; n < N; ++n)
+        for (int t = 0; t < T; ++t)
+            for (int u = 0; u < U; ++u) {
+                unsigned char* row = keep + (((size_t)n * T + t) * U + u) * H;
+                for (int k = 0; k < H; k += 4) {
+                    const Philox4 r = dropout_words(seed, n, t, u, k >> 2);
+                    for (int j = 0; j < 4 && k + j < H; ++j) row[k + j] = r.w[j] < thr;
+                }
+            }
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_hat.h: the factorised-blank (HAT) loss.  joint_loss's shape above: a producer of its own (hat.hip)
+// fills the pair plane, the sweeps and the gradient pairs are the standard ones; the backward is one streaming launch.
+rnntStatus_t rnnt_amd_hat_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                      const int* labels, const int* xn, const int* yn, float* costs, float* grads, int N,
+                                      int T, int U, int V, int blank, float fastemit_lambda) {
+    if (!dtype_ok(dtype) || !dims_ok(N, T, U) || V < 2 || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !logits || !xn || !yn || !costs || labels_missing(U, labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const Workspace w = loss_layout(c, N, T, U);
+    const PairSource src{RNNT_ALIGN_IN_HAT_LOGITS, dtype, logits, nullptr};
+    if (fill_pair_plane(stream, src, labels, w.ws2, N, T, U, V, blank, nullptr) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    return sweeps_and_pair_grads(stream, w, xn, yn, costs, grads ? grads : w.ws2, WRITE_SKEWED2, N, T, U, nullptr,
+                                 fastemit_lambda);
+}
+
+rnntStatus_t rnnt_amd_hat_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* labels,
+                                          const float* grads_diagonal, const float* grad_costs, void* dlogits, int N,
+                                          int T, int U, int V, int blank) {
+    if (!dtype_ok(dtype) || !dims_ok(N, T, U) || V < 2 || !vocab_ok(V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!logits || !grads_diagonal || !aligned(grads_diagonal, 8) || !dlogits || labels_missing(U, labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    if (launch_hat_logits_backward(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
+        hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_align.h: best-path alignments.  A producer of the loss fills the pair plane -- and leaves it
+// filled -- the max-plus sweep and the trace of align.hip take the place of the alpha / beta sweeps.
+size_t rnnt_amd_align_workspace_size(int N, int T, int U) {
+    if (!dims_ok(N, T, U)) return 0;
+    Carver c(nullptr);
+    loss_layout(c, N, T, U);
+    align_layout(c, N, T, U);
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_align(rnntStream_t stream, void* workspace, int input_kind, int dtype, const void* input,
+                            const int* labels, const int* xn, const int* yn, float* scores, int* emit_frames, int N, int T,
+                            int U, int V, int blank) {
+    const bool log_probs = input_kind == RNNT_IN_LOG_PROBS_DENSE || input_kind == RNNT_IN_LOG_PROBS_GATHERED;
+    if (!log_probs && input_kind != RNNT_IN_LOGITS_DENSE && input_kind != RNNT_ALIGN_IN_HAT_LOGITS)
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dtype_ok(dtype) || (log_probs && dtype != RNNT_DTYPE_F32)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dims_ok(N, T, U) || !workspace_ok(workspace)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!input || !xn || !yn || !scores || (U > 1 && !emit_frames)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (input_kind != RNNT_IN_LOG_PROBS_GATHERED &&
+        (!vocab_ok(V, blank) || (input_kind == RNNT_ALIGN_IN_HAT_LOGITS && V < 2) || labels_missing(U, labels)))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+
+    Carver c(workspace);
+    const Workspace w = loss_layout(c, N, T, U);
+    const AlignWorkspace aw = align_layout(c, N, T, U);
+    if (fill_pair_plane(stream, PairSource{input_kind, dtype, input, nullptr}, labels, w.ws2, N, T, U, V, blank, nullptr) !=
+        hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    if (launch_align_sweep(stream, w.ws2, xn, yn, aw.words, aw.park, scores, N, T, U) != hipSuccess)
+        return RNNT_STATUS_WARP_FAILED;
+    if (launch_align_trace(stream, aw.words, xn, yn, scores, emit_frames, N, T, U) != hipSuccess)
+        return RNNT_STATUS_WARP_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+}  // extern "C"
