@@ -109,9 +109,20 @@ ALIGN_SYMBOLS = {
     "rnnt_amd_align_workspace_size": (_sz, [_i, _i, _i]),
     "rnnt_amd_align": (_i, [_vp, _vp, _i, _i] + [_vp] * 6 + [_i] * 5),
 }
-# additive tables: (symbols, the header that declares them)
+# every symbol include/warp_rnnt_amd_tdt.h declares (the token-and-duration loss; additive: it did not move the version):
+# the size is a function of (N, T, U, D); the forward is (stream, workspace, dtype, logits, labels, xn, yn, durations, D,
+# costs, grads, N, T, U, V, blank, sigma, fastemit_lambda) with durations in host memory; the backward is (stream, dtype,
+# logits, labels, grads, grad_costs, dlogits, N, T, U, V, D, blank)
+TDT_SYMBOLS = {
+    "rnnt_amd_tdt_workspace_size": (_sz, [_i, _i, _i, _i]),
+    "rnnt_amd_tdt_loss_logits": (_i, [_vp, _vp, _i] + [_vp] * 5 + [_i, _vp, _vp] + [_i] * 5 + [_f, _f]),
+    "rnnt_amd_tdt_logits_backward": (_i, [_vp, _i] + [_vp] * 5 + [_i] * 6),
+}
+# additive tables: (symbols, the header that declares them).  ADDITIVE: the families that modify the standard lattice's
+# calls; ADDITIVE_LATTICES: the families with a lattice of their own.  load() walks both.
 ADDITIVE = ((CLAMP_SYMBOLS, "warp_rnnt_amd_clamp.h"), (DROPOUT_SYMBOLS, "warp_rnnt_amd_joint_dropout.h"),
             (HAT_SYMBOLS, "warp_rnnt_amd_hat.h"), (ALIGN_SYMBOLS, "warp_rnnt_amd_align.h"))
+ADDITIVE_LATTICES = ((TDT_SYMBOLS, "warp_rnnt_amd_tdt.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -149,7 +160,7 @@ def load():
         raise RuntimeError(f"{path} reports C-ABI version {L.rnnt_amd_version()}, this package binds version "
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
-    for table, header in ADDITIVE:
+    for table, header in ADDITIVE + ADDITIVE_LATTICES:
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

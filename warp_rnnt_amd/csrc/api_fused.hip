@@ -1,15 +1,18 @@
 // C ABI of libwarp_rnnt_amd.so, the fused family: a producer of its own in front of the loss's sweeps -- or a sweep of its
 // own behind one of the loss's producers.  The joint network (include/warp_rnnt_amd.h) and its dropout
 // (include/warp_rnnt_amd_joint_dropout.h), the factorised-blank loss (include/warp_rnnt_amd_hat.h), best-path alignments
-// (include/warp_rnnt_amd_align.h).  Host-side orchestration only: argument checks, workspace carving, launches.
+// (include/warp_rnnt_amd_align.h), the token-and-duration loss (include/warp_rnnt_amd_tdt.h: producer, sweeps and
+// gradient kernel all its own).  Host-side orchestration only: argument checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd_align.h"
 #include "../../include/warp_rnnt_amd_hat.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
+#include "../../include/warp_rnnt_amd_tdt.h"
 
 #include "align.h"
 #include "api_common.h"
 #include "hat.h"
 #include "philox.h"
+#include "tdt.h"
 
 using namespace rnnt;
 
@@ -99,6 +102,29 @@ AlignWorkspace align_layout(Carver& c, int N, int T, int U) {
     aw.park = c.take<float>(align_park_count(N, T, U));
     return aw;
 }
+
+// The token-and-duration loss (tdt.hip): the plane of 2 + D channels, alpha, beta, the log-likelihoods.
+struct TdtWorkspace {
+    float* plane;
+    float* alphas;
+    float* betas;
+    float* ll;
+};
+TdtWorkspace tdt_layout(Carver& c, int N, int T, int U, int D) {
+    const size_t cells = (size_t)N * T * U;
+    TdtWorkspace tw;
+    tw.plane = c.take<float>(cells * (size_t)(2 + D));
+    tw.alphas = c.take<float>(cells);
+    tw.betas = c.take<float>(cells);
+    tw.ll = c.take<float>((size_t)N);
+    return tw;
+}
+// the shape of a TDT call: the loss's sizes, a lattice that fits one workgroup, D durations and V tokens with the blank
+inline bool tdt_shape_ok(int dtype, int N, int T, int U, int V, int D, int blank) {
+    return dtype_ok(dtype) && dims_ok(N, T, U) && U <= TDT_MAX_U && D >= 1 && D <= TDT_MAX_D && V >= 2 && V <= (1 << 24) &&
+           vocab_ok(V, blank);
+}
+inline size_t dtype_size(int dtype) { return dtype == RNNT_DTYPE_F32 ? 4 : 2; }
 
 }  // namespace
 
@@ -233,6 +259,57 @@ rnntStatus_t rnnt_amd_align(rnntStream_t stream, void* workspace, int input_kind
         return RNNT_STATUS_WARP_FAILED;
     if (launch_align_trace(stream, aw.words, xn, yn, scores, emit_frames, N, T, U) != hipSuccess)
         return RNNT_STATUS_WARP_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_tdt.h: the token-and-duration (TDT) loss.  Nothing of the standard lattice serves: tdt.hip's
+// producer fills a plane of 2 + D channels, its sweeps write alpha, beta and the costs, its gradient kernel the 2 + D sums
+// per cell that the backward -- one streaming launch -- turns into d/d logits.
+size_t rnnt_amd_tdt_workspace_size(int N, int T, int U, int D) {
+    if (!tdt_shape_ok(RNNT_DTYPE_F32, N, T, U, 2, D, 0)) return 0;
+    Carver c(nullptr);
+    tdt_layout(c, N, T, U, D);
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_tdt_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                      const int* labels, const int* xn, const int* yn, const int* durations, int D,
+                                      float* costs, float* grads, int N, int T, int U, int V, int blank, float sigma,
+                                      float fastemit_lambda) {
+    if (!tdt_shape_ok(dtype, N, T, U, V, D, blank) || !tdt_durations_ok(durations, D)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!(sigma >= 0.0f && sigma <= 3.402823466e+38f)) return RNNT_STATUS_INVALID_ARGUMENT;      // (false for a NaN)
+    if (!workspace_ok(workspace) || !logits || !xn || !yn || !costs || labels_missing(U, labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!aligned(logits, dtype_size(dtype)) || !aligned(costs, 4) || !aligned(grads, 4) || !aligned(labels, 4) ||
+        !aligned(xn, 4) || !aligned(yn, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const TdtWorkspace tw = tdt_layout(c, N, T, U, D);
+    const TdtDurations dur = tdt_durations(durations, D);
+    if (launch_tdt_plane(stream, dtype, logits, labels, tw.plane, N, T, U, V, D, blank, sigma) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    if (launch_tdt_sweeps(stream, tw.plane, xn, yn, tw.alphas, grads ? tw.betas : nullptr, tw.ll, costs, dur, N, T, U) !=
+        hipSuccess)
+        return RNNT_STATUS_WARP_FAILED;
+    if (grads && launch_tdt_grads(stream, tw.plane, tw.alphas, tw.betas, tw.ll, xn, yn, grads, dur, N, T, U,
+                                  fastemit_lambda) != hipSuccess)
+        return RNNT_STATUS_GRADS_BLANK_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_tdt_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* labels,
+                                          const float* grads, const float* grad_costs, void* dlogits, int N, int T, int U,
+                                          int V, int D, int blank) {
+    if (!tdt_shape_ok(dtype, N, T, U, V, D, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!logits || !grads || !dlogits || labels_missing(U, labels)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!aligned(logits, dtype_size(dtype)) || !aligned(dlogits, dtype_size(dtype)) || !aligned(grads, 4) ||
+        !aligned(grad_costs, 4) || !aligned(labels, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    if (launch_tdt_logits_backward(stream, dtype, logits, labels, grads, grad_costs, dlogits, N, T, U, V, D, blank) !=
+        hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
 

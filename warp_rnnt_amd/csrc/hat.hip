@@ -23,15 +23,13 @@
 //   output pass (20 KB at V = 5000: from L2).
 // A chunk is one 16-byte access (two for fp32) where the row pitch V * sizeof(E) and the tensors' addresses are multiples
 // of 16; otherwise accesses of 8, 4 or 2 bytes, the widest that pitch and addresses allow (V = 50 in fp32: 8 bytes).
-// No LDS, no atomics, nothing between workgroups.
-#include <type_traits>
-
+// (row_chunks.h: the load and the store of a chunk, shared with tdt.hip.)  No LDS, no atomics, nothing between workgroups.
 #include "hat.h"
-#include "streaming.h"
+#include "row_chunks.h"
 #include "../../include/warp_rnnt_amd.h"
 
 // every product and sum below is rounded on its own: no fused multiply-add is formed, the same source gives the same bits
-// at the three storage types, and a bf16 / fp16 result is the fp32 result rounded once (hat_store8 has the one exception
+// at the three storage types, and a bf16 / fp16 result is the fp32 result rounded once (row_store8 has the one exception
 // the compiler makes to that, and what stops it)
 #pragma clang fp contract(off)
 
@@ -39,66 +37,8 @@ namespace rnnt {
 namespace {
 
 constexpr int HAT_THREADS = 256;
-constexpr int HAT_CHUNK = 8;             // elements per chunk
 constexpr int HAT_SMALL_V = 1024;        // rows up to here are held in registers: 2 chunks per lane, 64 lanes at the most
-constexpr float HAT_NEG_INF = -__builtin_inff();
 
-// An access moves ACC bytes = NV elements: 16, 8, 4 (or, in half precision, 2) -- the largest power of two that divides the
-// row pitch V * sizeof(E) and the tensors' addresses, so every access of a row is aligned and lies below V whole or not
-// at all.  Which elements a lane holds does not depend on it.
-template <typename T, int NV> struct HatVec { typedef T type __attribute__((ext_vector_type(NV))); };
-template <typename T> struct HatVec<T, 1> { typedef T type; };
-template <typename T, int NV> using hat_vec_t = typename HatVec<T, NV>::type;
-
-// Elements e0 .. e0+7 of the row at xr as floats; -inf at and past V
-template <typename E, int ACC, bool NT>
-__device__ __forceinline__ void hat_load8(const E* __restrict__ xr, int e0, int V, float (&z)[HAT_CHUNK]) {
-    constexpr int NV = ACC / (int)sizeof(E);
-    static_assert(NV == 1 || NV == 2 || NV == 4 || NV == 8, "2 to 16 bytes, whole elements");
-#pragma unroll
-    for (int k = 0; k < HAT_CHUNK; k += NV) {
-        if constexpr (NV == 1) {
-            z[k] = e0 + k < V ? (float)xr[e0 + k] : HAT_NEG_INF;
-        } else {
-#pragma unroll
-            for (int i = 0; i < NV; ++i) z[k + i] = HAT_NEG_INF;
-            if (e0 + k < V) {
-                const hat_vec_t<E, NV>* p = reinterpret_cast<const hat_vec_t<E, NV>*>(xr + e0 + k);
-                hat_vec_t<E, NV> h;
-                if constexpr (NT) h = __builtin_nontemporal_load(p); else h = *p;
-                const hat_vec_t<float, NV> v = __builtin_convertvector(h, hat_vec_t<float, NV>);
-#pragma unroll
-                for (int i = 0; i < NV; ++i) z[k + i] = v[i];
-            }
-        }
-    }
-}
-
-// ... and d[0..7] to elements e0 .. e0+7 of the row at o, below V only, converted to E (round to nearest even) as stored
-template <typename E, int ACC>
-__device__ __forceinline__ void hat_store8(E* __restrict__ o, int e0, int V, const float (&d)[HAT_CHUNK]) {
-    constexpr int NV = ACC / (int)sizeof(E);
-#pragma unroll
-    for (int k = 0; k < HAT_CHUNK; k += NV) {
-        if (e0 + k >= V) continue;
-        if constexpr (NV > 1) {
-            hat_vec_t<float, NV> v;
-#pragma unroll
-            for (int i = 0; i < NV; ++i) v[i] = d[k + i];
-            __builtin_nontemporal_store(__builtin_convertvector(v, hat_vec_t<E, NV>),
-                                        reinterpret_cast<hat_vec_t<E, NV>*>(o + e0 + k));
-        } else if constexpr (std::is_same_v<E, float>) {
-            o[e0 + k] = d[k];
-        } else {
-            // (the median of d, d, d is d: an instruction between the multiply that made d and the cast.  Without it a
-            //  scalar fp16 cast takes that multiply with it -- v_fma_mixlo_f16, one rounding of the exact product -- and
-            //  a half result is no longer the fp32 result rounded once.  The packed conversions above take none.)
-            o[e0 + k] = (E)__builtin_amdgcn_fmed3f(d[k], d[k], d[k]);
-        }
-    }
-}
-
-__device__ __forceinline__ float hat_exp(float d) { return __builtin_amdgcn_exp2f(d * LOG2E); }   // d <= 0; exp(-inf) = +0
 __device__ __forceinline__ float hat_softplus(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
 
 // What the forward stores for a cell: lpB, and lp[label] -- lpB again where the label channel is the blank's (the last
@@ -122,7 +62,7 @@ __device__ __forceinline__ HatCellGrad hat_cell_grad(float zb, float2 g, float s
     return {sc * (g.x * nsig - g.y * sig), g.y, sc, label};
 }
 __device__ __forceinline__ float hat_dz(const HatCellGrad& c, float z, int idx, int blank, float m, float ls) {
-    const float q = hat_exp((z - m) - ls);                    // (z = -inf at the blank, past V and at masked logits: q = +0)
+    const float q = row_exp((z - m) - ls);                    // (z = -inf at the blank, past V and at masked logits: q = +0)
     const float u = c.gL * ((idx == c.label ? 1.0f : 0.0f) - q);
     return idx == blank ? c.ub : c.sc * u;
 }
@@ -132,21 +72,21 @@ __device__ __forceinline__ float hat_dz(const HatCellGrad& c, float z, int idx, 
 // ---------------------------------------------------------------------------------------------------------
 // (a row of up to 8 G elements has no second chunk in any lane: it is neither loaded nor worked on -- what it would add,
 //  -inf to the maximum and +0 to the sum, changes no bit)
-template <int G> __device__ __forceinline__ int hat_small_chunks(int V) { return V > G * HAT_CHUNK ? 2 : 1; }
+template <int G> __device__ __forceinline__ int hat_small_chunks(int V) { return V > G * ROW_CHUNK ? 2 : 1; }
 
 template <typename E, int G, int ACC>
-__device__ __forceinline__ void hat_small_stats(const E* __restrict__ xr, int lane, int V, int blank, float (&z)[2][HAT_CHUNK],
+__device__ __forceinline__ void hat_small_stats(const E* __restrict__ xr, int lane, int V, int blank, float (&z)[2][ROW_CHUNK],
                                                 float& m, float& ls) {
     const int chunks = hat_small_chunks<G>(V);
-    hat_load8<E, ACC, true>(xr, lane * HAT_CHUNK, V, z[0]);
-    if (chunks > 1) hat_load8<E, ACC, true>(xr, (G + lane) * HAT_CHUNK, V, z[1]);
-    m = HAT_NEG_INF;
+    row_load8<E, ACC, true>(xr, lane * ROW_CHUNK, V, z[0]);
+    if (chunks > 1) row_load8<E, ACC, true>(xr, (G + lane) * ROW_CHUNK, V, z[1]);
+    m = ROW_NEG_INF;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         if (k < chunks) {
 #pragma unroll
-            for (int i = 0; i < HAT_CHUNK; ++i) {
-                if ((k * G + lane) * HAT_CHUNK + i == blank) z[k][i] = HAT_NEG_INF;
+            for (int i = 0; i < ROW_CHUNK; ++i) {
+                if ((k * G + lane) * ROW_CHUNK + i == blank) z[k][i] = ROW_NEG_INF;
                 m = fmaxf(m, z[k][i]);
             }
         }
@@ -157,7 +97,7 @@ __device__ __forceinline__ void hat_small_stats(const E* __restrict__ xr, int la
     for (int k = 0; k < 2; ++k) {
         if (k < chunks) {
 #pragma unroll
-            for (int i = 0; i < HAT_CHUNK; ++i) s += hat_exp(z[k][i] - m);
+            for (int i = 0; i < ROW_CHUNK; ++i) s += row_exp(z[k][i] - m);
         }
     }
     ls = logf(group_sum<G>(s));
@@ -175,7 +115,7 @@ k_hat_gather_small(const E* __restrict__ x, const int* __restrict__ labels, floa
     //  round trips that then overlap the row's)
     const CellMap c = map_cell(row, labels, T, U, V, blank);
     const float zb = (float)xr[blank], zl = (float)xr[c.label];
-    float z[2][HAT_CHUNK], m, ls;
+    float z[2][ROW_CHUNK], m, ls;
     hat_small_stats<E, G, ACC>(xr, lane, V, blank, z, m, ls);
     if (lane == 0) ws2[c.sk] = hat_pair(zb, zl, c.label, blank, m, ls);
 }
@@ -191,7 +131,7 @@ k_hat_backward_small(const E* __restrict__ x, const int* __restrict__ labels, co
     const CellMap c = map_cell(row, labels, T, U, V, blank);          // (in front of the row: as in the gather)
     const float zb = (float)xr[blank], sc = scale ? scale[c.n] : 1.0f;
     const float2 g = g2[c.sk];
-    float z[2][HAT_CHUNK], m, ls;
+    float z[2][ROW_CHUNK], m, ls;
     hat_small_stats<E, G, ACC>(xr, lane, V, blank, z, m, ls);
     const HatCellGrad cg = hat_cell_grad(zb, g, sc, c.label);
     E* o = out + row * (size_t)V;
@@ -199,11 +139,11 @@ k_hat_backward_small(const E* __restrict__ x, const int* __restrict__ labels, co
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         if (k >= chunks) break;
-        const int e0 = (k * G + lane) * HAT_CHUNK;
-        float d[HAT_CHUNK];
+        const int e0 = (k * G + lane) * ROW_CHUNK;
+        float d[ROW_CHUNK];
 #pragma unroll
-        for (int i = 0; i < HAT_CHUNK; ++i) d[i] = hat_dz(cg, z[k][i], e0 + i, blank, m, ls);
-        hat_store8<E, ACC>(o, e0, V, d);
+        for (int i = 0; i < ROW_CHUNK; ++i) d[i] = hat_dz(cg, z[k][i], e0 + i, blank, m, ls);
+        row_store8<E, ACC>(o, e0, V, d);
     }
 }
 
@@ -212,25 +152,25 @@ k_hat_backward_small(const E* __restrict__ x, const int* __restrict__ labels, co
 // ---------------------------------------------------------------------------------------------------------
 template <typename E, int ACC, bool NT>
 __device__ __forceinline__ void hat_wave_stats(const E* __restrict__ xr, int lane, int V, int blank, float& m, float& ls) {
-    float ml = HAT_NEG_INF, s = 0.0f;
-    for (int e0 = lane * HAT_CHUNK; e0 < V; e0 += WAVE * HAT_CHUNK) {
-        float z[HAT_CHUNK];
-        hat_load8<E, ACC, NT>(xr, e0, V, z);
+    float ml = ROW_NEG_INF, s = 0.0f;
+    for (int e0 = lane * ROW_CHUNK; e0 < V; e0 += WAVE * ROW_CHUNK) {
+        float z[ROW_CHUNK];
+        row_load8<E, ACC, NT>(xr, e0, V, z);
         float mn = ml;
 #pragma unroll
-        for (int i = 0; i < HAT_CHUNK; ++i) {
-            if (e0 + i == blank) z[i] = HAT_NEG_INF;
+        for (int i = 0; i < ROW_CHUNK; ++i) {
+            if (e0 + i == blank) z[i] = ROW_NEG_INF;
             mn = fmaxf(mn, z[i]);
         }
-        if (mn > HAT_NEG_INF) {               // (a lane that has seen nothing but -inf keeps s = 0)
-            s = s * hat_exp(ml - mn);         // exp(0) = 1 exactly where the maximum stays; 0 * exp(-inf) = 0 at the start
+        if (mn > ROW_NEG_INF) {               // (a lane that has seen nothing but -inf keeps s = 0)
+            s = s * row_exp(ml - mn);         // exp(0) = 1 exactly where the maximum stays; 0 * exp(-inf) = 0 at the start
 #pragma unroll
-            for (int i = 0; i < HAT_CHUNK; ++i) s += hat_exp(z[i] - mn);
+            for (int i = 0; i < ROW_CHUNK; ++i) s += row_exp(z[i] - mn);
             ml = mn;
         }
     }
     m = group_max<WAVE>(ml);
-    ls = logf(group_sum<WAVE>(s * hat_exp(ml - m)));
+    ls = logf(group_sum<WAVE>(s * row_exp(ml - m)));
 }
 
 template <typename E, int ACC>
@@ -263,12 +203,12 @@ k_hat_backward_wave(const E* __restrict__ x, const int* __restrict__ labels, con
     hat_wave_stats<E, ACC, false>(xr, lane, V, blank, m, ls);      // (plain loads: the output pass reads the row again)
     const HatCellGrad cg = hat_cell_grad(zb, g, sc, c.label);
     E* o = out + row * (size_t)V;
-    for (int e0 = lane * HAT_CHUNK; e0 < V; e0 += WAVE * HAT_CHUNK) {
-        float z[HAT_CHUNK], d[HAT_CHUNK];
-        hat_load8<E, ACC, true>(xr, e0, V, z);
+    for (int e0 = lane * ROW_CHUNK; e0 < V; e0 += WAVE * ROW_CHUNK) {
+        float z[ROW_CHUNK], d[ROW_CHUNK];
+        row_load8<E, ACC, true>(xr, e0, V, z);
 #pragma unroll
-        for (int i = 0; i < HAT_CHUNK; ++i) d[i] = hat_dz(cg, e0 + i == blank ? HAT_NEG_INF : z[i], e0 + i, blank, m, ls);
-        hat_store8<E, ACC>(o, e0, V, d);
+        for (int i = 0; i < ROW_CHUNK; ++i) d[i] = hat_dz(cg, e0 + i == blank ? ROW_NEG_INF : z[i], e0 + i, blank, m, ls);
+        row_store8<E, ACC>(o, e0, V, d);
     }
 }
 
@@ -281,12 +221,6 @@ inline HatShape hat_shape(size_t rows, int V) {
     const int G = V > HAT_SMALL_V ? 0 : V <= 16 * 16 ? 16 : V <= 16 * 32 ? 32 : 64;
     const size_t per = HAT_THREADS / (G ? G : WAVE);
     return {G, (unsigned)((rows + per - 1) / per)};        // rows < 2^32 (the C ABI's dims_ok): at most 2^28 workgroups
-}
-
-// The widest access of hat_load8 / hat_store8 that the row pitch and the addresses allow
-template <typename E> inline int hat_access(int V, const void* a, const void* b) {
-    const uintptr_t bits = (uintptr_t)V * sizeof(E) | reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | 16;
-    return (int)(bits & (~bits + 1));          // lowest set bit: 16, 8, 4 or 2 (1 is not a tensor of E)
 }
 
 // launch(kernel) with the instantiation of the call's form and access out of K_SMALL<E, G, ACC> / K_WAVE<E, ACC>
@@ -310,7 +244,7 @@ template <typename E>
 hipError_t hat_gather(hipStream_t stream, const E* x, const int* labels, float* ws2, int N, int T, int U, int V, int blank) {
     const size_t rows = (size_t)N * T * U;
     if (rows == 0) return hipSuccess;
-    const int acc = hat_access<E>(V, x, nullptr);
+    const int acc = row_access<E>(V, x, nullptr);
     const HatShape sh = hat_shape(rows, V);
     float2* out = reinterpret_cast<float2*>(ws2);
     const auto launch = [&](auto kernel) { kernel<<<sh.grid, HAT_THREADS, 0, stream>>>(x, labels, out, rows, T, U, V, blank); };
@@ -327,7 +261,7 @@ hipError_t hat_backward(hipStream_t stream, const E* x, const int* labels, const
                         E* dx, int N, int T, int U, int V, int blank) {
     const size_t rows = (size_t)N * T * U;
     if (rows == 0) return hipSuccess;
-    const int acc = hat_access<E>(V, x, dx);
+    const int acc = row_access<E>(V, x, dx);
     const HatShape sh = hat_shape(rows, V);
     const float2* g2 = reinterpret_cast<const float2*>(g2_diagonal);
     const auto launch = [&](auto kernel) {

@@ -1,4 +1,5 @@
 """Torch-tensor front ends of the native entry points (device memory + streams only)."""
+import ctypes
 import os
 import warnings
 
@@ -581,6 +582,60 @@ def hat_logits_backward(logits, labels, grads, grad_costs, blank=0):
             return out
         _check(L.rnnt_amd_hat_logits_backward(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(), _ptr(labels),
                                               grads.data_ptr(), _ptr(grad_costs), out.data_ptr(), N, T, U, V, blank))
+    return out
+
+
+def _tdt_check(V, D, blank, durations, sigma):
+    """The refusals of include/warp_rnnt_amd_tdt.h that depend on values, with their reasons spelt out."""
+    ds = [int(d) for d in durations]
+    if not (1 <= len(ds) <= 9 and len(set(ds)) == len(ds) and all(0 <= d <= 8 for d in ds) and 1 in ds):
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the TDT loss needs durations that are "
+                           f"distinct integers in [0, 8] with 1 among them (durations={tuple(durations)})")
+    if D != len(ds) or V < 2 or not 0 <= blank < V:
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the TDT loss needs logits of V + D columns, "
+                           f"V >= 2, and a blank that is a token index (V={V}, D={len(ds)}, blank={blank})")
+    if not 0.0 <= sigma < float("inf"):
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the TDT loss needs a finite sigma >= 0 "
+                           f"(sigma={sigma})")
+    return ds
+
+
+def tdt_loss(logits, labels, xn, yn, durations, blank=0, sigma=0.0, fastemit_lambda=0.0, with_grads=True):
+    """The token-and-duration (TDT) loss on the fused path (include/warp_rnnt_amd_tdt.h): logits (N,T,U,V+D) fp32 / bf16 /
+    fp16 with D = len(durations), validated by the caller.  Returns costs (N,) fp32 and, with_grads, the per-cell sums
+    (2+D,N,T,U) fp32 -- G_b, G_l, G_dur as planes in the diagonal-major cell order -- what :func:`tdt_logits_backward`
+    reads (else None: no beta sweep runs and no such plane is produced)."""
+    L = _lib.load()
+    N, T, U, W = logits.shape
+    D = len(durations)
+    dev = logits.device
+    ds = _tdt_check(W - D, D, blank, durations, sigma)
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        grads = torch.empty((2 + D, N, T, U), dtype=torch.float32, device=dev) if with_grads else None
+        if N == 0:
+            return costs, grads
+        ws = _workspace(dev, L.rnnt_amd_tdt_workspace_size, "N T U D", N, T, U, D)
+        host_durations = (ctypes.c_int * D)(*ds)          # read during the call: nothing of it is needed afterwards
+        _check(L.rnnt_amd_tdt_loss_logits(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
+                                          _ptr(labels), xn.data_ptr(), yn.data_ptr(), host_durations, D, costs.data_ptr(),
+                                          _ptr(grads), N, T, U, W - D, blank, float(sigma), float(fastemit_lambda)))
+    return costs, grads
+
+
+def tdt_logits_backward(logits, labels, grads, grad_costs, num_durations, blank=0):
+    """d(sum_n grad_costs[n]*cost[n]) / d(logits) of :func:`tdt_loss`, in the logits' dtype (the fp32 result rounded
+    once); grads: the planes the forward returned."""
+    L = _lib.load()
+    N, T, U, W = logits.shape
+    dev = logits.device
+    with torch.cuda.device(dev):
+        out = torch.empty_like(logits)
+        if N == 0:
+            return out
+        _check(L.rnnt_amd_tdt_logits_backward(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(), _ptr(labels),
+                                              grads.data_ptr(), _ptr(grad_costs), out.data_ptr(), N, T, U,
+                                              W - num_durations, num_durations, blank))
     return out
 
 
