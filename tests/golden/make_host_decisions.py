@@ -2,7 +2,7 @@
 """Generates tests/golden/host_decisions.json: what the C ABI decides on the host alone.
 
 Two tables, recorded from a build of the library (the in-tree one, or the path given as the first argument):
-  sizes  every workspace size / offset entry over a grid of shapes -- padded, compact, bounded, joint, align; valid and invalid,
+  sizes  every workspace size / offset entry over a grid of shapes -- padded, compact, bounded, joint, align, TDT; valid and invalid,
          including both sides of each limit of the size checks;
   calls  for every status-returning entry the calls it answers WITHOUT launching anything: each reason it has to reject a
          call, one at a time (status 5), and its early successes (N == 0, STU == 0 where that is one, nothing requested).
@@ -40,10 +40,15 @@ COMPACT = [(0, 0, 0, 0), (2, 0, 5, 3), (2, 23, 5, 3), (2, 23, 0, 0), (16, 500000
 JOINT = [(2, 5, 3, 64, 8), (16, 150, 40, 640, 1024), (1, 1, 1, 32, 2), (1, 1, 1, 1024, 1 << 24), (3, 37, 65, 128, 100),
          (0, 5, 3, 64, 8), (65536, 5, 3, 64, 8), (2, 5, 3, 16, 8), (2, 5, 3, 48, 8), (2, 5, 3, 1056, 8), (2, 5, 3, 64, 1),
          (2, 5, 3, 64, (1 << 24) + 1), (16, 1 << 14, 1 << 14, 64, 8)]
+# (N, T, U, D): both sides of every limit of the TDT size check -- the padded ones with U <= 1024 on top (one workgroup's
+# columns: T * U < 2^29 and N * T * U < 2^32 are shown at U = 1024), and 1 <= D <= 9
+TDT = [(2, 5, 3, 5), (16, 1500, 300, 5), (3, 20, 7, 4), (3, 37, 65, 2), (0, 5, 3, 5), (65535, 1, 1, 5), (65536, 1, 1, 5),
+       (-1, 5, 3, 5), (2, 0, 3, 5), (2, 5, 0, 5), (1, 4, 1024, 5), (1, 4, 1025, 5), (2, 5, 3, 0), (2, 5, 3, 1), (2, 5, 3, 9),
+       (2, 5, 3, 10), (1, (1 << 19) - 1, 1024, 1), (1, 1 << 19, 1024, 1), (15, 1 << 18, 1024, 9), (16, 1 << 18, 1024, 9)]
 SIZES = [("rnnt_amd_workspace_size", PADDED), ("rnnt_amd_workspace_mismatch_offset", PADDED),
          ("rnnt_amd_debug_redo_offset", PADDED), ("rnnt_amd_workspace_size_compact", COMPACT),
          ("rnnt_amd_workspace_size_compact_bounded", COMPACT), ("rnnt_amd_joint_workspace_size", JOINT),
-         ("rnnt_amd_align_workspace_size", PADDED)]
+         ("rnnt_amd_align_workspace_size", PADDED), ("rnnt_amd_tdt_workspace_size", TDT)]
 
 BAD_DIMS = [dict(N=-1), dict(T=0), dict(U=0), dict(N=65536), dict(T=1 << 15, U=1 << 14), dict(N=16, T=1 << 14, U=1 << 14)]
 BAD_COMPACT_DIMS = [dict(N=-1), dict(N=65536), dict(STU=-1), dict(STU=1 << 32), dict(Tmax=1 << 15, Umax=1 << 14),

@@ -200,6 +200,30 @@ def test_bits_depend_on_the_utterance_alone(shape):
         assert (grad[n, :xn[n], :yn[n] + 1] != 0).any(), n
 
 
+@pytest.mark.parametrize("dname", ["f32", "bf16"])
+def test_an_address_that_narrows_the_access_moves_no_bit(dname):
+    """Rows of 59 + 5 = 64 elements are 16-byte rows at every type, so here it is the tensor's address alone that narrows
+    the access: the same logits in a tensor of their own, and in a contiguous view that starts one element into a larger
+    buffer.  The element map does not depend on the access: costs and d/d logits are equal bit for bit."""
+    from warp_rnnt_amd import ops
+    dtype = {"f32": torch.float32, "bf16": torch.bfloat16}[dname]
+    shape, blank = (2, 5, 3, 59, D5), 29
+    logits, labels, xn, yn = case(shape, blank)
+    own = dev(logits).to(dtype)
+    off = torch.empty(own.numel() + 1, dtype=dtype, device=DEV)[1:].view(own.shape)
+    off.copy_(own)
+    assert off.is_contiguous() and own.data_ptr() % 16 == 0 and off.data_ptr() % 16 == own.element_size()
+    tl, txn, tyn, go = dev(labels), dev(xn), dev(yn), dev(_go(shape[0]))
+
+    def both(x):
+        costs, planes = ops.tdt_loss(x, tl, txn, tyn, D5, blank, 0.05, 0.01)
+        return costs, ops.tdt_logits_backward(x, tl, planes, go, len(D5), blank)
+
+    (costs, dz), (costs_off, dz_off) = both(own), both(off)
+    assert torch.isfinite(costs).all() and torch.isfinite(dz.float()).all() and (dz != 0).any()
+    assert dz_off.dtype == dtype and torch.equal(costs, costs_off) and torch.equal(dz, dz_off)
+
+
 def test_an_utterance_with_lengths_out_of_range_is_nan_and_zero():
     shape, blank = (4, 9, 5, 6, D5), 5
     logits, labels, xn, yn = case(shape, blank)

@@ -1,5 +1,5 @@
 """The contract of an additive header of the C ABI, once for every family of warp_rnnt_amd._lib.ADDITIVE (gradient clamp,
-dropout in the joint, HAT loss, alignments): entries that came after version 110 and did not move it are declared in a
+dropout in the joint, HAT loss, alignments, TDT loss): entries that came after version 110 and did not move it are declared in a
 header of their own, bound in a table of their own, exported, and a library built before them is told apart by its exports.
 What is particular to a family -- how its argument lists relate to its twins', its constants, its sources -- is in that
 family's test_host_*.py."""
@@ -13,7 +13,8 @@ import pytest
 from warp_rnnt_amd import _lib as lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = ("warp_rnnt_amd_clamp.h", "warp_rnnt_amd_joint_dropout.h", "warp_rnnt_amd_hat.h", "warp_rnnt_amd_align.h")
+HEADERS = ("warp_rnnt_amd_clamp.h", "warp_rnnt_amd_joint_dropout.h", "warp_rnnt_amd_hat.h", "warp_rnnt_amd_align.h",
+           "warp_rnnt_amd_tdt.h")
 FAMILIES = pytest.mark.parametrize("table,header", lib.ADDITIVE, ids=[h[len("warp_rnnt_amd_"):-2] for _, h in lib.ADDITIVE])
 
 
@@ -25,7 +26,8 @@ def _load():
 
 
 def test_every_family_is_in_the_table_load_walks():
-    assert lib.ADDITIVE == tuple(zip((lib.CLAMP_SYMBOLS, lib.DROPOUT_SYMBOLS, lib.HAT_SYMBOLS, lib.ALIGN_SYMBOLS), HEADERS))
+    families = (lib.CLAMP_SYMBOLS, lib.DROPOUT_SYMBOLS, lib.HAT_SYMBOLS, lib.ALIGN_SYMBOLS, lib.TDT_SYMBOLS)
+    assert lib.ADDITIVE == tuple(zip(families, HEADERS)) and len(HEADERS) == 5
 
 
 @FAMILIES

@@ -1,6 +1,8 @@
 """The host-side decisions of the C ABI, replayed from tests/golden/host_decisions.json (tests/golden/make_host_decisions.py
 wrote it from a build of the commit before the C ABI's entries were folded onto one workspace, one tail and one compact
-core; the rows of rnnt_amd_align_workspace_size from the commit before the host layer was split by entry family): every
+core; the rows of rnnt_amd_align_workspace_size from the commit before the host layer was split by entry family, the
+rows of rnnt_amd_tdt_workspace_size from the commit before its table joined _lib.ADDITIVE, which is how this test reaches
+that entry): every
 workspace size and offset over a grid of shapes, and for every status-returning entry the calls it answers without a
 launch -- each rejection reason one at a time, and the early successes."""
 import json

@@ -118,11 +118,12 @@ TDT_SYMBOLS = {
     "rnnt_amd_tdt_loss_logits": (_i, [_vp, _vp, _i] + [_vp] * 5 + [_i, _vp, _vp] + [_i] * 5 + [_f, _f]),
     "rnnt_amd_tdt_logits_backward": (_i, [_vp, _i] + [_vp] * 5 + [_i] * 6),
 }
-# additive tables: (symbols, the header that declares them).  ADDITIVE: the families that modify the standard lattice's
-# calls; ADDITIVE_LATTICES: the families with a lattice of their own.  load() walks both.
+# the additive table: (symbols, the header that declares them) of every family that came after version 110 and did not
+# move it.  load() walks it; tests/test_host_additive_abi.py holds every family to the one contract, and
+# tests/test_host_decisions.py reaches their size entries through it.
 ADDITIVE = ((CLAMP_SYMBOLS, "warp_rnnt_amd_clamp.h"), (DROPOUT_SYMBOLS, "warp_rnnt_amd_joint_dropout.h"),
-            (HAT_SYMBOLS, "warp_rnnt_amd_hat.h"), (ALIGN_SYMBOLS, "warp_rnnt_amd_align.h"))
-ADDITIVE_LATTICES = ((TDT_SYMBOLS, "warp_rnnt_amd_tdt.h"),)
+            (HAT_SYMBOLS, "warp_rnnt_amd_hat.h"), (ALIGN_SYMBOLS, "warp_rnnt_amd_align.h"),
+            (TDT_SYMBOLS, "warp_rnnt_amd_tdt.h"))
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -160,7 +161,7 @@ def load():
         raise RuntimeError(f"{path} reports C-ABI version {L.rnnt_amd_version()}, this package binds version "
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
-    for table, header in ADDITIVE + ADDITIVE_LATTICES:
+    for table, header in ADDITIVE:
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

@@ -23,20 +23,22 @@
 //   output pass (20 KB at V = 5000: from L2).
 // A chunk is one 16-byte access (two for fp32) where the row pitch V * sizeof(E) and the tensors' addresses are multiples
 // of 16; otherwise accesses of 8, 4 or 2 bytes, the widest that pitch and addresses allow (V = 50 in fp32: 8 bytes).
-// (row_chunks.h: the load and the store of a chunk, shared with tdt.hip.)  No LDS, no atomics, nothing between workgroups.
+// (row_chunks.h, shared with tdt.hip: the load and the store of a chunk, the running pass of the long form, and the launch
+// side -- lanes per row, workgroups, the dispatch over access and storage type.  The register form is this unit's own.)
+// No LDS, no atomics, nothing between workgroups.
 #include "hat.h"
 #include "row_chunks.h"
 #include "../../include/warp_rnnt_amd.h"
 
 // every product and sum below is rounded on its own: no fused multiply-add is formed, the same source gives the same bits
 // at the three storage types, and a bf16 / fp16 result is the fp32 result rounded once (row_store8 has the one exception
-// the compiler makes to that, and what stops it)
+// the compiler makes to that, and what stops it).  (row_chunks.h sets the same for its own functions, which this line,
+// behind the includes, does not reach.)
 #pragma clang fp contract(off)
 
 namespace rnnt {
 namespace {
 
-constexpr int HAT_THREADS = 256;
 constexpr int HAT_SMALL_V = 1024;        // rows up to here are held in registers: 2 chunks per lane, 64 lanes at the most
 
 __device__ __forceinline__ float hat_softplus(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
@@ -104,10 +106,10 @@ __device__ __forceinline__ void hat_small_stats(const E* __restrict__ xr, int la
 }
 
 template <typename E, int G, int ACC>
-__global__ void __launch_bounds__(HAT_THREADS)
+__global__ void __launch_bounds__(ROW_THREADS)
 k_hat_gather_small(const E* __restrict__ x, const int* __restrict__ labels, float2* __restrict__ ws2, size_t rows, int T,
                    int U, int V, int blank) {
-    const size_t row = (size_t)blockIdx.x * (HAT_THREADS / G) + threadIdx.x / G;
+    const size_t row = (size_t)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
     if (row >= rows) return;
     const int lane = threadIdx.x % G;
     const E* xr = x + row * (size_t)V;
@@ -121,10 +123,10 @@ k_hat_gather_small(const E* __restrict__ x, const int* __restrict__ labels, floa
 }
 
 template <typename E, int G, int ACC>
-__global__ void __launch_bounds__(HAT_THREADS)
+__global__ void __launch_bounds__(ROW_THREADS)
 k_hat_backward_small(const E* __restrict__ x, const int* __restrict__ labels, const float2* __restrict__ g2,
                      const float* __restrict__ scale, E* __restrict__ out, size_t rows, int T, int U, int V, int blank) {
-    const size_t row = (size_t)blockIdx.x * (HAT_THREADS / G) + threadIdx.x / G;
+    const size_t row = (size_t)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
     if (row >= rows) return;
     const int lane = threadIdx.x % G;
     const E* xr = x + row * (size_t)V;
@@ -150,34 +152,17 @@ k_hat_backward_small(const E* __restrict__ x, const int* __restrict__ labels, co
 // ---------------------------------------------------------------------------------------------------------
 // Longer rows: a wave per row, chunks lane, 64 + lane, ...; running maximum and sum per lane in one pass
 // ---------------------------------------------------------------------------------------------------------
+// (row_stats of row_chunks.h at G = 64 over the whole row, the blank masked)
 template <typename E, int ACC, bool NT>
 __device__ __forceinline__ void hat_wave_stats(const E* __restrict__ xr, int lane, int V, int blank, float& m, float& ls) {
-    float ml = ROW_NEG_INF, s = 0.0f;
-    for (int e0 = lane * ROW_CHUNK; e0 < V; e0 += WAVE * ROW_CHUNK) {
-        float z[ROW_CHUNK];
-        row_load8<E, ACC, NT>(xr, e0, V, z);
-        float mn = ml;
-#pragma unroll
-        for (int i = 0; i < ROW_CHUNK; ++i) {
-            if (e0 + i == blank) z[i] = ROW_NEG_INF;
-            mn = fmaxf(mn, z[i]);
-        }
-        if (mn > ROW_NEG_INF) {               // (a lane that has seen nothing but -inf keeps s = 0)
-            s = s * row_exp(ml - mn);         // exp(0) = 1 exactly where the maximum stays; 0 * exp(-inf) = 0 at the start
-#pragma unroll
-            for (int i = 0; i < ROW_CHUNK; ++i) s += row_exp(z[i] - mn);
-            ml = mn;
-        }
-    }
-    m = group_max<WAVE>(ml);
-    ls = logf(group_sum<WAVE>(s * row_exp(ml - m)));
+    row_stats<E, WAVE, ACC, NT>(xr, lane, V, V, [blank](int idx) { return idx == blank; }, m, ls);
 }
 
 template <typename E, int ACC>
-__global__ void __launch_bounds__(HAT_THREADS)
+__global__ void __launch_bounds__(ROW_THREADS)
 k_hat_gather_wave(const E* __restrict__ x, const int* __restrict__ labels, float2* __restrict__ ws2, size_t rows, int T,
                   int U, int V, int blank) {
-    const size_t row = (size_t)blockIdx.x * (HAT_THREADS / WAVE) + threadIdx.x / WAVE;
+    const size_t row = (size_t)blockIdx.x * (ROW_THREADS / WAVE) + threadIdx.x / WAVE;
     if (row >= rows) return;
     const int lane = threadIdx.x % WAVE;
     const E* xr = x + row * (size_t)V;
@@ -189,10 +174,10 @@ k_hat_gather_wave(const E* __restrict__ x, const int* __restrict__ labels, float
 }
 
 template <typename E, int ACC>
-__global__ void __launch_bounds__(HAT_THREADS)
+__global__ void __launch_bounds__(ROW_THREADS)
 k_hat_backward_wave(const E* __restrict__ x, const int* __restrict__ labels, const float2* __restrict__ g2,
                     const float* __restrict__ scale, E* __restrict__ out, size_t rows, int T, int U, int V, int blank) {
-    const size_t row = (size_t)blockIdx.x * (HAT_THREADS / WAVE) + threadIdx.x / WAVE;
+    const size_t row = (size_t)blockIdx.x * (ROW_THREADS / WAVE) + threadIdx.x / WAVE;
     if (row >= rows) return;
     const int lane = threadIdx.x % WAVE;
     const E* xr = x + row * (size_t)V;
@@ -212,48 +197,22 @@ k_hat_backward_wave(const E* __restrict__ x, const int* __restrict__ labels, con
     }
 }
 
-// The form of a call, a function of V alone: lanes per row (0: a wave per row, the long form) and workgroups
-struct HatShape {
-    int G;
-    unsigned grid;
-};
-inline HatShape hat_shape(size_t rows, int V) {
-    const int G = V > HAT_SMALL_V ? 0 : V <= 16 * 16 ? 16 : V <= 16 * 32 ? 32 : 64;
-    const size_t per = HAT_THREADS / (G ? G : WAVE);
-    return {G, (unsigned)((rows + per - 1) / per)};        // rows < 2^32 (the C ABI's dims_ok): at most 2^28 workgroups
-}
-
-// launch(kernel) with the instantiation of the call's form and access out of K_SMALL<E, G, ACC> / K_WAVE<E, ACC>
-#define HAT_FORMS(ACC)                                                   \
-    switch (sh.G) {                                                      \
-        case 16: launch(K_SMALL(16, ACC)); break;                        \
-        case 32: launch(K_SMALL(32, ACC)); break;                        \
-        case 64: launch(K_SMALL(64, ACC)); break;                        \
-        default: launch(K_WAVE(ACC)); break;                             \
-    }
-#define HAT_DISPATCH()                                                   \
-    switch (acc) {                                                       \
-        case 16: HAT_FORMS(16) break;                                    \
-        case 8: HAT_FORMS(8) break;                                      \
-        case 4: HAT_FORMS(4) break;                                      \
-        case 2: if constexpr (sizeof(E) == 2) { HAT_FORMS(2) break; }    \
-        default: return hipErrorInvalidValue;                            \
-    }
-
+// The form of a call is a function of V alone: the register form with row_group(V) lanes per row up to HAT_SMALL_V, a
+// wave per row beyond (where row_group(V) is 64: the same rows per workgroup)
 template <typename E>
 hipError_t hat_gather(hipStream_t stream, const E* x, const int* labels, float* ws2, int N, int T, int U, int V, int blank) {
     const size_t rows = (size_t)N * T * U;
     if (rows == 0) return hipSuccess;
-    const int acc = row_access<E>(V, x, nullptr);
-    const HatShape sh = hat_shape(rows, V);
+    const int G = row_group(V);
+    const unsigned grid = row_grid(rows, G);
     float2* out = reinterpret_cast<float2*>(ws2);
-    const auto launch = [&](auto kernel) { kernel<<<sh.grid, HAT_THREADS, 0, stream>>>(x, labels, out, rows, T, U, V, blank); };
-#define K_SMALL(G, ACC) k_hat_gather_small<E, G, ACC>
-#define K_WAVE(ACC) k_hat_gather_wave<E, ACC>
-    HAT_DISPATCH()
-#undef K_SMALL
-#undef K_WAVE
-    return hipGetLastError();
+    return row_dispatch<E>(G, row_access<E>(V, x, nullptr), [&](auto g, auto acc) {
+        constexpr int GG = decltype(g)::value, ACC = decltype(acc)::value;
+        if (V <= HAT_SMALL_V)
+            k_hat_gather_small<E, GG, ACC><<<grid, ROW_THREADS, 0, stream>>>(x, labels, out, rows, T, U, V, blank);
+        else
+            k_hat_gather_wave<E, ACC><<<grid, ROW_THREADS, 0, stream>>>(x, labels, out, rows, T, U, V, blank);
+    });
 }
 
 template <typename E>
@@ -261,51 +220,34 @@ hipError_t hat_backward(hipStream_t stream, const E* x, const int* labels, const
                         E* dx, int N, int T, int U, int V, int blank) {
     const size_t rows = (size_t)N * T * U;
     if (rows == 0) return hipSuccess;
-    const int acc = row_access<E>(V, x, dx);
-    const HatShape sh = hat_shape(rows, V);
+    const int G = row_group(V);
+    const unsigned grid = row_grid(rows, G);
     const float2* g2 = reinterpret_cast<const float2*>(g2_diagonal);
-    const auto launch = [&](auto kernel) {
-        kernel<<<sh.grid, HAT_THREADS, 0, stream>>>(x, labels, g2, scale, dx, rows, T, U, V, blank);
-    };
-#define K_SMALL(G, ACC) k_hat_backward_small<E, G, ACC>
-#define K_WAVE(ACC) k_hat_backward_wave<E, ACC>
-    HAT_DISPATCH()
-#undef K_SMALL
-#undef K_WAVE
-    return hipGetLastError();
+    return row_dispatch<E>(G, row_access<E>(V, x, dx), [&](auto g, auto acc) {
+        constexpr int GG = decltype(g)::value, ACC = decltype(acc)::value;
+        if (V <= HAT_SMALL_V)
+            k_hat_backward_small<E, GG, ACC><<<grid, ROW_THREADS, 0, stream>>>(x, labels, g2, scale, dx, rows, T, U, V, blank);
+        else
+            k_hat_backward_wave<E, ACC><<<grid, ROW_THREADS, 0, stream>>>(x, labels, g2, scale, dx, rows, T, U, V, blank);
+    });
 }
-#undef HAT_DISPATCH
-#undef HAT_FORMS
 
 }  // namespace
 
 hipError_t launch_hat_gather_skewed(hipStream_t stream, int dtype, const void* logits, const int* labels, float* ws2,
                                     int N, int T, int U, int V, int blank) {
     if (V < 2 || blank < 0 || blank >= V) return hipErrorInvalidValue;
-    switch (dtype) {
-        case RNNT_DTYPE_F32: return hat_gather(stream, static_cast<const float*>(logits), labels, ws2, N, T, U, V, blank);
-        case RNNT_DTYPE_BF16: return hat_gather(stream, static_cast<const __bf16*>(logits), labels, ws2, N, T, U, V, blank);
-        case RNNT_DTYPE_F16: return hat_gather(stream, static_cast<const _Float16*>(logits), labels, ws2, N, T, U, V, blank);
-    }
-    return hipErrorInvalidValue;
+    return row_typed(dtype, logits, nullptr,
+                     [&](auto* x, auto*) { return hat_gather(stream, x, labels, ws2, N, T, U, V, blank); });
 }
 
 hipError_t launch_hat_logits_backward(hipStream_t stream, int dtype, const void* logits, const int* labels,
                                       const float* g2_diagonal, const float* scale, void* dlogits, int N, int T, int U,
                                       int V, int blank) {
     if (V < 2 || blank < 0 || blank >= V) return hipErrorInvalidValue;
-    switch (dtype) {
-        case RNNT_DTYPE_F32:
-            return hat_backward(stream, static_cast<const float*>(logits), labels, g2_diagonal, scale,
-                                static_cast<float*>(dlogits), N, T, U, V, blank);
-        case RNNT_DTYPE_BF16:
-            return hat_backward(stream, static_cast<const __bf16*>(logits), labels, g2_diagonal, scale,
-                                static_cast<__bf16*>(dlogits), N, T, U, V, blank);
-        case RNNT_DTYPE_F16:
-            return hat_backward(stream, static_cast<const _Float16*>(logits), labels, g2_diagonal, scale,
-                                static_cast<_Float16*>(dlogits), N, T, U, V, blank);
-    }
-    return hipErrorInvalidValue;
+    return row_typed(dtype, logits, dlogits, [&](auto* x, auto* dx) {
+        return hat_backward(stream, x, labels, g2_diagonal, scale, dx, N, T, U, V, blank);
+    });
 }
 
 }  // namespace rnnt

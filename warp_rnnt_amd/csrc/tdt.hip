@@ -15,11 +15,12 @@
 // rounded once to the logits' type.
 //
 // The streaming kernels hold a row of V+D logits by a group of G lanes (16, 32 or 64, by the row's length alone): the row
-// is cut into chunks of 8 elements (row_chunks.h), chunk c belongs to lane c mod G, a lane runs over its chunks in
-// ascending order keeping a running maximum and sum of the TOKEN logits, the lanes are combined by the xor butterfly of
-// streaming.h.  The D duration logits are read by every lane as single elements and reduced in the order i = 0..D-1.  So
-// a row's bits do not depend on the storage type, the access width or where the row lies.  -inf is a masked entry: +0 in
-// both sums, and an exactly zero gradient.
+// is cut into chunks of 8 elements, chunk c belongs to lane c mod G, a lane runs over its chunks in ascending order
+// keeping a running maximum and sum of the TOKEN logits, the lanes are combined by the xor butterfly of streaming.h --
+// all of it row_chunks.h's, shared with hat.hip, as are the launch side's lanes per row, workgroups and dispatch.  The D
+// duration logits are read by every lane as single elements and reduced in the order i = 0..D-1.  So a row's bits do not
+// depend on the storage type, the access width or where the row lies.  -inf is a masked entry: +0 in both sums, and an
+// exactly zero gradient.
 //
 // The sweeps: one workgroup per utterance and direction, lanes are lattice columns, one wave per 64 columns.  The last
 // max(durations)+2 diagonals of alpha (beta) live in an LDS ring -- the one being written and the max(durations)+1 that
@@ -29,13 +30,12 @@
 #include "row_chunks.h"
 #include "../../include/warp_rnnt_amd.h"
 
-// every product and sum below is rounded on its own (hat.hip has the reasons)
+// every product and sum below is rounded on its own (hat.hip has the reasons; row_chunks.h sets the same for its own
+// functions, which this line, behind the includes, does not reach)
 #pragma clang fp contract(off)
 
 namespace rnnt {
 namespace {
-
-constexpr int TDT_THREADS = 256;
 
 __host__ __device__ __forceinline__ int tdt_mod(int a, int T) {
     const int r = a % T;
@@ -45,28 +45,10 @@ __host__ __device__ __forceinline__ int tdt_mod(int a, int T) {
 // ---------------------------------------------------------------------------------------------------------
 // The two streaming kernels
 // ---------------------------------------------------------------------------------------------------------
-// (max, log sum) of the token logits z[0..V) of the row at xr, whose pitch is W = V + D
+// (max, log sum) of the token logits z[0..V) of the row at xr, whose pitch is W = V + D: a chunk's duration logits masked
 template <typename E, int G, int ACC, bool NT>
 __device__ __forceinline__ void tdt_token_stats(const E* __restrict__ xr, int lane, int V, int W, float& m, float& ls) {
-    float ml = ROW_NEG_INF, s = 0.0f;
-    for (int e0 = lane * ROW_CHUNK; e0 < V; e0 += G * ROW_CHUNK) {
-        float z[ROW_CHUNK];
-        row_load8<E, ACC, NT>(xr, e0, W, z);
-        float mn = ml;
-#pragma unroll
-        for (int i = 0; i < ROW_CHUNK; ++i) {
-            if (e0 + i >= V) z[i] = ROW_NEG_INF;     // a duration logit
-            mn = fmaxf(mn, z[i]);
-        }
-        if (mn > ROW_NEG_INF) {               // (a lane that has seen nothing but -inf keeps s = 0)
-            s = s * row_exp(ml - mn);         // exp(0) = 1 exactly where the maximum stays; 0 * exp(-inf) = 0 at the start
-#pragma unroll
-            for (int i = 0; i < ROW_CHUNK; ++i) s += row_exp(z[i] - mn);
-            ml = mn;
-        }
-    }
-    m = group_max<G>(ml);
-    ls = logf(group_sum<G>(s * row_exp(ml - m)));
+    row_stats<E, G, ACC, NT>(xr, lane, V, W, [V](int idx) { return idx >= V; }, m, ls);
 }
 
 // The D duration logits of the row, and their (max, log sum); every lane does this for itself
@@ -88,10 +70,10 @@ __device__ __forceinline__ void tdt_load_durations(const E* __restrict__ xr, int
 }
 
 template <typename E, int G, int ACC>
-__global__ void __launch_bounds__(TDT_THREADS)
+__global__ void __launch_bounds__(ROW_THREADS)
 k_tdt_plane(const E* __restrict__ x, const int* __restrict__ labels, float* __restrict__ plane, size_t rows, int T, int U,
             int V, int D, int blank, float sigma) {
-    const size_t row = (size_t)blockIdx.x * (TDT_THREADS / G) + threadIdx.x / G;
+    const size_t row = (size_t)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
     if (row >= rows) return;
     const int lane = threadIdx.x % G, W = V + D;
     const E* xr = x + row * (size_t)W;
@@ -112,10 +94,10 @@ k_tdt_plane(const E* __restrict__ x, const int* __restrict__ labels, float* __re
 }
 
 template <typename E, int G, int ACC>
-__global__ void __launch_bounds__(TDT_THREADS)
+__global__ void __launch_bounds__(ROW_THREADS)
 k_tdt_backward(const E* __restrict__ x, const int* __restrict__ labels, const float* __restrict__ gplane,
                const float* __restrict__ scale, E* __restrict__ out, size_t rows, int T, int U, int V, int D, int blank) {
-    const size_t row = (size_t)blockIdx.x * (TDT_THREADS / G) + threadIdx.x / G;
+    const size_t row = (size_t)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
     if (row >= rows) return;
     const int lane = threadIdx.x % G, W = V + D;
     const E* xr = x + row * (size_t)W;
@@ -323,12 +305,12 @@ k_tdt_sweep(const float* __restrict__ plane, const int* __restrict__ xn, const i
 }
 
 // One thread per cell in diagonal-major order (blockIdx.y: the utterance): the 2 + D sums of the cell's edge occupancies
-__global__ void __launch_bounds__(TDT_THREADS)
+__global__ void __launch_bounds__(ROW_THREADS)
 k_tdt_grads(const float* __restrict__ plane, const float* __restrict__ alphas, const float* __restrict__ betas,
             const float* __restrict__ ll, const int* __restrict__ xn, const int* __restrict__ yn,
             float* __restrict__ gplane, TdtDurations dur, size_t cells, int T, int U, float label_scale) {
     const int n = blockIdx.y;
-    const unsigned at = blockIdx.x * TDT_THREADS + threadIdx.x;
+    const unsigned at = blockIdx.x * ROW_THREADS + threadIdx.x;
     if (at >= (unsigned)T * (unsigned)U) return;
     const int r = (int)(at / (unsigned)U), u = (int)(at - (unsigned)r * (unsigned)U);
     const int t = tdt_mod(r - u, T);
@@ -367,47 +349,18 @@ k_tdt_grads(const float* __restrict__ plane, const float* __restrict__ alphas, c
 // ---------------------------------------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------------------------------------
-// The form of a streaming call, a function of the row's length W = V + D alone: lanes per row and workgroups
-struct TdtShape {
-    int G;
-    unsigned grid;
-};
-inline TdtShape tdt_shape(size_t rows, int W) {
-    const int G = W <= 16 * 16 ? 16 : W <= 16 * 32 ? 32 : 64;
-    const size_t per = TDT_THREADS / G;
-    return {G, (unsigned)((rows + per - 1) / per)};        // rows < 2^32 (the C ABI's dims_ok): at most 2^28 workgroups
-}
-
-// launch(kernel) with the instantiation of the call's form and access out of KERNEL<E, G, ACC>
-#define TDT_FORMS(ACC)                                                   \
-    switch (sh.G) {                                                      \
-        case 16: launch(KERNEL(16, ACC)); break;                         \
-        case 32: launch(KERNEL(32, ACC)); break;                         \
-        default: launch(KERNEL(64, ACC)); break;                         \
-    }
-#define TDT_DISPATCH()                                                   \
-    switch (acc) {                                                       \
-        case 16: TDT_FORMS(16) break;                                    \
-        case 8: TDT_FORMS(8) break;                                      \
-        case 4: TDT_FORMS(4) break;                                      \
-        case 2: if constexpr (sizeof(E) == 2) { TDT_FORMS(2) break; }    \
-        default: return hipErrorInvalidValue;                            \
-    }
-
+// The form of a streaming call is a function of the row's length W = V + D alone (row_group, row_grid)
 template <typename E>
 hipError_t tdt_plane(hipStream_t stream, const E* x, const int* labels, float* plane, int N, int T, int U, int V, int D,
                      int blank, float sigma) {
     const size_t rows = (size_t)N * T * U;
     if (rows == 0) return hipSuccess;
-    const int acc = row_access<E>(V + D, x, nullptr);
-    const TdtShape sh = tdt_shape(rows, V + D);
-    const auto launch = [&](auto kernel) {
-        kernel<<<sh.grid, TDT_THREADS, 0, stream>>>(x, labels, plane, rows, T, U, V, D, blank, sigma);
-    };
-#define KERNEL(G, ACC) k_tdt_plane<E, G, ACC>
-    TDT_DISPATCH()
-#undef KERNEL
-    return hipGetLastError();
+    const int G = row_group(V + D);
+    const unsigned grid = row_grid(rows, G);
+    return row_dispatch<E>(G, row_access<E>(V + D, x, nullptr), [&](auto g, auto acc) {
+        k_tdt_plane<E, decltype(g)::value, decltype(acc)::value>
+            <<<grid, ROW_THREADS, 0, stream>>>(x, labels, plane, rows, T, U, V, D, blank, sigma);
+    });
 }
 
 template <typename E>
@@ -415,18 +368,13 @@ hipError_t tdt_backward(hipStream_t stream, const E* x, const int* labels, const
                         int N, int T, int U, int V, int D, int blank) {
     const size_t rows = (size_t)N * T * U;
     if (rows == 0) return hipSuccess;
-    const int acc = row_access<E>(V + D, x, dx);
-    const TdtShape sh = tdt_shape(rows, V + D);
-    const auto launch = [&](auto kernel) {
-        kernel<<<sh.grid, TDT_THREADS, 0, stream>>>(x, labels, gplane, scale, dx, rows, T, U, V, D, blank);
-    };
-#define KERNEL(G, ACC) k_tdt_backward<E, G, ACC>
-    TDT_DISPATCH()
-#undef KERNEL
-    return hipGetLastError();
+    const int G = row_group(V + D);
+    const unsigned grid = row_grid(rows, G);
+    return row_dispatch<E>(G, row_access<E>(V + D, x, dx), [&](auto g, auto acc) {
+        k_tdt_backward<E, decltype(g)::value, decltype(acc)::value>
+            <<<grid, ROW_THREADS, 0, stream>>>(x, labels, gplane, scale, dx, rows, T, U, V, D, blank);
+    });
 }
-#undef TDT_DISPATCH
-#undef TDT_FORMS
 
 inline bool tdt_rows_ok(int V, int D, int blank) { return V >= 2 && D >= 1 && D <= TDT_MAX_D && blank >= 0 && blank < V; }
 
@@ -435,15 +383,8 @@ inline bool tdt_rows_ok(int V, int D, int blank) { return V >= 2 && D >= 1 && D 
 hipError_t launch_tdt_plane(hipStream_t stream, int dtype, const void* logits, const int* labels, float* plane, int N, int T,
                             int U, int V, int D, int blank, float sigma) {
     if (!tdt_rows_ok(V, D, blank)) return hipErrorInvalidValue;
-    switch (dtype) {
-        case RNNT_DTYPE_F32:
-            return tdt_plane(stream, static_cast<const float*>(logits), labels, plane, N, T, U, V, D, blank, sigma);
-        case RNNT_DTYPE_BF16:
-            return tdt_plane(stream, static_cast<const __bf16*>(logits), labels, plane, N, T, U, V, D, blank, sigma);
-        case RNNT_DTYPE_F16:
-            return tdt_plane(stream, static_cast<const _Float16*>(logits), labels, plane, N, T, U, V, D, blank, sigma);
-    }
-    return hipErrorInvalidValue;
+    return row_typed(dtype, logits, nullptr,
+                     [&](auto* x, auto*) { return tdt_plane(stream, x, labels, plane, N, T, U, V, D, blank, sigma); });
 }
 
 hipError_t launch_tdt_sweeps(hipStream_t stream, const float* plane, const int* xn, const int* yn, float* alphas,
@@ -465,8 +406,8 @@ hipError_t launch_tdt_grads(hipStream_t stream, const float* plane, const float*
                             float fastemit_lambda) {
     if (dur.D < 1 || dur.D > TDT_MAX_D) return hipErrorInvalidValue;
     if (N == 0) return hipSuccess;
-    const unsigned per = ((unsigned)T * (unsigned)U + TDT_THREADS - 1) / TDT_THREADS;
-    k_tdt_grads<<<dim3(per, N), TDT_THREADS, 0, stream>>>(plane, alphas, betas, ll, xn, yn, gplane, dur, (size_t)N * T * U, T,
+    const unsigned per = ((unsigned)T * (unsigned)U + ROW_THREADS - 1) / ROW_THREADS;
+    k_tdt_grads<<<dim3(per, N), ROW_THREADS, 0, stream>>>(plane, alphas, betas, ll, xn, yn, gplane, dur, (size_t)N * T * U, T,
                                                           U, 1.0f + fastemit_lambda);
     return hipGetLastError();
 }
@@ -475,18 +416,9 @@ hipError_t launch_tdt_logits_backward(hipStream_t stream, int dtype, const void*
                                       const float* gplane, const float* scale, void* dlogits, int N, int T, int U, int V,
                                       int D, int blank) {
     if (!tdt_rows_ok(V, D, blank)) return hipErrorInvalidValue;
-    switch (dtype) {
-        case RNNT_DTYPE_F32:
-            return tdt_backward(stream, static_cast<const float*>(logits), labels, gplane, scale,
-                                static_cast<float*>(dlogits), N, T, U, V, D, blank);
-        case RNNT_DTYPE_BF16:
-            return tdt_backward(stream, static_cast<const __bf16*>(logits), labels, gplane, scale,
-                                static_cast<__bf16*>(dlogits), N, T, U, V, D, blank);
-        case RNNT_DTYPE_F16:
-            return tdt_backward(stream, static_cast<const _Float16*>(logits), labels, gplane, scale,
-                                static_cast<_Float16*>(dlogits), N, T, U, V, D, blank);
-    }
-    return hipErrorInvalidValue;
+    return row_typed(dtype, logits, dlogits, [&](auto* x, auto* dx) {
+        return tdt_backward(stream, x, labels, gplane, scale, dx, N, T, U, V, D, blank);
+    });
 }
 
 }  // namespace rnnt

@@ -26,6 +26,18 @@ def check_logits_inputs(xs, ys, xn, yn):
     _core.check_inputs(xs, ys, xn, yn, xs_dtypes=tuple(ops.LOGITS_DTYPES))
 
 
+def finish_costs(costs, frames_lengths, average_frames, reduction):
+    """The tail of every ``*_loss_from_*`` function: the per-utterance costs divided by the frame counts where
+    ``average_frames`` asks for it, then ``reduction`` ("none" / None, "sum", "mean")."""
+    if average_frames:
+        costs = costs / frames_lengths.to(costs)      # (fp32 costs: T_n rounded to bf16 would be 1499 -> 1496)
+    if reduction == "none" or reduction is None:
+        return costs
+    if reduction == "sum":
+        return costs.sum()
+    return costs.mean()
+
+
 class RNNTLossFromLogits(torch.autograd.Function):
 
     @staticmethod
@@ -117,10 +129,4 @@ def rnnt_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, frames_len
                                                 wants_grad, max_frames, max_labels, clamp)
     else:
         costs = RNNTLossFromLogits.apply(logits, labels, frames_lengths, labels_lengths, blank, fastemit_lambda, clamp)
-    if average_frames:
-        costs = costs / frames_lengths.to(costs)      # (fp32 costs: T_n rounded to bf16 would be 1499 -> 1496)
-    if reduction == "none" or reduction is None:
-        return costs
-    if reduction == "sum":
-        return costs.sum()
-    return costs.mean()
+    return finish_costs(costs, frames_lengths, average_frames, reduction)

@@ -21,7 +21,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .fused import check_logits_inputs
+from .fused import check_logits_inputs, finish_costs
 
 
 def _softplus(x):
@@ -82,13 +82,7 @@ def hat_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, frames_leng
     assert reduction is None or reduction in ("none", "mean", "sum")
     assert isinstance(blank, int)
     costs = HATLossFromLogits.apply(logits, labels, frames_lengths, labels_lengths, blank, fastemit_lambda)
-    if average_frames:
-        costs = costs / frames_lengths.to(costs)
-    if reduction == "none" or reduction is None:
-        return costs
-    if reduction == "sum":
-        return costs.sum()
-    return costs.mean()
+    return finish_costs(costs, frames_lengths, average_frames, reduction)
 
 
 class HATLoss(torch.nn.Module):

@@ -17,6 +17,7 @@ from typing import Optional
 import torch
 
 from . import _mismatch, ops
+from .fused import finish_costs
 from warp_rnnt import _C as _core
 
 
@@ -176,13 +177,7 @@ def rnnt_loss_from_joint(f: torch.Tensor, g: torch.Tensor, weight: torch.Tensor,
         seed = resolve_dropout_seed(dropout_seed, f.device, torch.cuda.is_current_stream_capturing())
     costs = RNNTLossFromJoint.apply(f, g, weight, bias, labels, frames_lengths, labels_lengths, activation, blank,
                                     fastemit_lambda, with_grads, p, seed)
-    if average_frames:
-        costs = costs / frames_lengths.to(costs)
-    if reduction == "none" or reduction is None:
-        return costs
-    if reduction == "sum":
-        return costs.sum()
-    return costs.mean()
+    return finish_costs(costs, frames_lengths, average_frames, reduction)
 
 
 class JointLoss(torch.nn.Module):

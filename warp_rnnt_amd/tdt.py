@@ -25,7 +25,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .fused import check_logits_inputs
+from .fused import check_logits_inputs, finish_costs
 
 
 def tdt_log_probs(logits: torch.Tensor, num_durations: int, blank: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -75,13 +75,7 @@ def tdt_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, frames_leng
     assert isinstance(blank, int)
     costs = TDTLossFromLogits.apply(logits, labels, frames_lengths, labels_lengths, tuple(durations), float(sigma), blank,
                                     float(fastemit_lambda))
-    if average_frames:
-        costs = costs / frames_lengths.to(costs)
-    if reduction == "none" or reduction is None:
-        return costs
-    if reduction == "sum":
-        return costs.sum()
-    return costs.mean()
+    return finish_costs(costs, frames_lengths, average_frames, reduction)
 
 
 class TDTLoss(torch.nn.Module):
