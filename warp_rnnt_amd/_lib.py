@@ -124,6 +124,17 @@ TDT_SYMBOLS = {
 ADDITIVE = ((CLAMP_SYMBOLS, "warp_rnnt_amd_clamp.h"), (DROPOUT_SYMBOLS, "warp_rnnt_amd_joint_dropout.h"),
             (HAT_SYMBOLS, "warp_rnnt_amd_hat.h"), (ALIGN_SYMBOLS, "warp_rnnt_amd_align.h"),
             (TDT_SYMBOLS, "warp_rnnt_amd_tdt.h"))
+# every symbol include/warp_rnnt_amd_tdt_align.h declares (best-path alignments over the TDT lattice; additive: it did not
+# move the version): the size is a function of (N, T, U, D); the call is (stream, workspace, dtype, logits, labels, xn, yn,
+# durations, D, scores, emit_frames, emit_durations, N, T, U, V, blank, sigma) with durations in host memory
+TDT_ALIGN_SYMBOLS = {
+    "rnnt_amd_tdt_align_workspace_size": (_sz, [_i, _i, _i, _i]),
+    "rnnt_amd_tdt_align": (_i, [_vp, _vp, _i] + [_vp] * 5 + [_i] + [_vp] * 3 + [_i] * 5 + [_f]),
+}
+# the families that came after the five of ADDITIVE, under the same contract; load() walks them behind it
+# (tests/test_host_tdt_align.py holds this one to it).  Folding the two tuples into one is for a change that may touch the
+# tests which pin ADDITIVE to its five.
+ADDITIVE_NEXT = ((TDT_ALIGN_SYMBOLS, "warp_rnnt_amd_tdt_align.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -161,7 +172,7 @@ def load():
         raise RuntimeError(f"{path} reports C-ABI version {L.rnnt_amd_version()}, this package binds version "
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
-    for table, header in ADDITIVE:
+    for table, header in ADDITIVE + ADDITIVE_NEXT:
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

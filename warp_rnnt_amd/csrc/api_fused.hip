@@ -2,17 +2,20 @@
 // own behind one of the loss's producers.  The joint network (include/warp_rnnt_amd.h) and its dropout
 // (include/warp_rnnt_amd_joint_dropout.h), the factorised-blank loss (include/warp_rnnt_amd_hat.h), best-path alignments
 // (include/warp_rnnt_amd_align.h), the token-and-duration loss (include/warp_rnnt_amd_tdt.h: producer, sweeps and
-// gradient kernel all its own).  Host-side orchestration only: argument checks, workspace carving, launches.
+// gradient kernel all its own) and its best-path alignments (include/warp_rnnt_amd_tdt_align.h).  Host-side orchestration
+// only: argument checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd_align.h"
 #include "../../include/warp_rnnt_amd_hat.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
 #include "../../include/warp_rnnt_amd_tdt.h"
+#include "../../include/warp_rnnt_amd_tdt_align.h"
 
 #include "align.h"
 #include "api_common.h"
 #include "hat.h"
 #include "philox.h"
 #include "tdt.h"
+#include "tdt_align.h"
 
 using namespace rnnt;
 
@@ -125,6 +128,19 @@ inline bool tdt_shape_ok(int dtype, int N, int T, int U, int V, int D, int blank
            vocab_ok(V, blank);
 }
 inline size_t dtype_size(int dtype) { return dtype == RNNT_DTYPE_F32 ? 4 : 2; }
+
+// Best-path alignments over the TDT lattice (tdt_align.hip): the plane where and as tdt_layout has it, then the decision
+// bytes.
+struct TdtAlignWorkspace {
+    float* plane;
+    unsigned char* dec;
+};
+TdtAlignWorkspace tdt_align_layout(Carver& c, int N, int T, int U, int D) {
+    TdtAlignWorkspace aw;
+    aw.plane = c.take<float>((size_t)N * T * U * (size_t)(2 + D));
+    aw.dec = c.take<unsigned char>(tdt_align_dec_count(N, T, U));
+    return aw;
+}
 
 }  // namespace
 
@@ -310,6 +326,39 @@ rnntStatus_t rnnt_amd_tdt_logits_backward(rnntStream_t stream, int dtype, const 
     if (launch_tdt_logits_backward(stream, dtype, logits, labels, grads, grad_costs, dlogits, N, T, U, V, D, blank) !=
         hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_tdt_align.h: best-path alignments over the TDT lattice.  The loss's producer fills its plane -- and
+// leaves it filled -- the max-plus sweep and the trace of tdt_align.hip take the place of the alpha / beta sweeps.
+size_t rnnt_amd_tdt_align_workspace_size(int N, int T, int U, int D) {
+    if (rnnt_amd_tdt_workspace_size(N, T, U, D) == 0) return 0;
+    Carver c(nullptr);
+    tdt_align_layout(c, N, T, U, D);
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_tdt_align(rnntStream_t stream, void* workspace, int dtype, const void* logits, const int* labels,
+                                const int* xn, const int* yn, const int* durations, int D, float* scores, int* emit_frames,
+                                int* emit_durations, int N, int T, int U, int V, int blank, float sigma) {
+    if (!tdt_shape_ok(dtype, N, T, U, V, D, blank) || !tdt_durations_ok(durations, D)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!(sigma >= 0.0f && sigma <= 3.402823466e+38f)) return RNNT_STATUS_INVALID_ARGUMENT;      // (false for a NaN)
+    if (!workspace_ok(workspace) || !logits || !xn || !yn || !scores || labels_missing(U, labels) ||
+        (U > 1 && (!emit_frames || !emit_durations)))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!aligned(logits, dtype_size(dtype)) || !aligned(scores, 4) || !aligned(emit_frames, 4) ||
+        !aligned(emit_durations, 4) || !aligned(labels, 4) || !aligned(xn, 4) || !aligned(yn, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const TdtAlignWorkspace aw = tdt_align_layout(c, N, T, U, D);
+    const TdtDurations dur = tdt_durations(durations, D);
+    if (launch_tdt_plane(stream, dtype, logits, labels, aw.plane, N, T, U, V, D, blank, sigma) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    if (launch_tdt_align_sweep(stream, aw.plane, xn, yn, aw.dec, scores, dur, N, T, U) != hipSuccess)
+        return RNNT_STATUS_WARP_FAILED;
+    if (launch_tdt_align_trace(stream, aw.dec, xn, yn, scores, emit_frames, emit_durations, dur, N, T, U) != hipSuccess)
+        return RNNT_STATUS_WARP_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
 

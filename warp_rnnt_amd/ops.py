@@ -639,6 +639,31 @@ def tdt_logits_backward(logits, labels, grads, grad_costs, num_durations, blank=
     return out
 
 
+def tdt_align(logits, labels, xn, yn, durations, blank=0, sigma=0.0):
+    """Best-path alignments over the TDT lattice (include/warp_rnnt_amd_tdt_align.h): logits (N,T,U,V+D) as
+    :func:`tdt_loss` takes them, validated by the caller.  Returns scores (N,) fp32 -- the log-probability of the best path,
+    -inf where there is none -- and emit_frames, emit_durations (N,U-1) int32: the frame at which label u is emitted and
+    the duration emitted with it, -1 behind yn[n] and for an utterance without a path."""
+    L = _lib.load()
+    N, T, U, W = logits.shape
+    D = len(durations)
+    dev = logits.device
+    ds = _tdt_check(W - D, D, blank, durations, sigma)
+    with torch.cuda.device(dev):
+        scores = torch.empty((N,), dtype=torch.float32, device=dev)
+        emit_frames = torch.empty((N, U - 1), dtype=torch.int32, device=dev)
+        emit_durations = torch.empty((N, U - 1), dtype=torch.int32, device=dev)
+        if N == 0:
+            return scores, emit_frames, emit_durations
+        ws = _workspace(dev, L.rnnt_amd_tdt_align_workspace_size, "N T U D", N, T, U, D)
+        host_durations = (ctypes.c_int * D)(*ds)          # read during the call: nothing of it is needed afterwards
+        _check(L.rnnt_amd_tdt_align(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
+                                    _ptr(labels), xn.data_ptr(), yn.data_ptr(), host_durations, D, scores.data_ptr(),
+                                    emit_frames.data_ptr() if U > 1 else 0, emit_durations.data_ptr() if U > 1 else 0,
+                                    N, T, U, W - D, blank, float(sigma)))
+    return scores, emit_frames, emit_durations
+
+
 ALIGN_IN_HAT_LOGITS = _lib.ALIGN_IN_HAT_LOGITS
 
 

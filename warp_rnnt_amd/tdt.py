@@ -78,6 +78,35 @@ def tdt_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, frames_leng
     return finish_costs(costs, frames_lengths, average_frames, reduction)
 
 
+def tdt_align(logits: torch.Tensor, labels: torch.Tensor, frames_lengths: torch.Tensor, labels_lengths: torch.Tensor,
+              durations: Sequence[int] = (0, 1, 2, 3, 4), sigma: float = 0.0,
+              blank: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The best path of every utterance through the TDT lattice: ``(scores, emit_frames, emit_durations)``.
+
+    The loss sums over every path; this asks the same lattice -- same logits, ``durations``, ``sigma`` and ``blank`` as
+    :func:`tdt_loss_from_logits`, same producer -- for its single best one (csrc/tdt_align.hip: a max-plus sweep that
+    records one decision byte per cell, and a trace).  All arithmetic is fp32, one add for an edge's weight
+    ``tok[.] + dur[i]``, one for ``v(source) + weight``, one compare; of equal candidates the earlier one in the order
+    ``i = 0..D-1``, blank before label, is kept.
+
+    ``scores`` (N,) fp32 is the log-probability of the best path, ``-inf`` where the lattice has none (``T_n <= U_n``
+    without a duration 0, masked logits).  ``emit_frames`` (N,U-1) int32 holds the frame ``t`` at which label ``u`` is
+    emitted and ``emit_durations`` (N,U-1) int32 the duration ``d`` emitted with it -- the label edge
+    ``(t,u) -> (t+d,u+1)`` of the path.  ``emit_frames + emit_durations`` is the frame the token ends on: it is ``<=``
+    the next token's emit frame and ``< T_n``.  Both rows hold -1 in the columns from ``labels_lengths[n]`` on, and
+    throughout for an utterance without a path.  An utterance whose lengths are outside ``[1,T]`` x ``[0,U-1]`` gets a
+    NaN score and -1 rows.  Token timestamps, alignment-restricted training masks, emission-delay statistics (what
+    ``fastemit_lambda`` and ``sigma`` are tuned against) and the diagnostic ``score + cost <= 0`` come from here.
+
+    Results are detached and computed under ``no_grad``.  Enqueue-only: the call can be captured into a graph.
+    ``U > 1024`` is refused."""
+    assert isinstance(blank, int)
+    with torch.no_grad():
+        logits = logits.detach()
+        check_logits_inputs(logits, labels, frames_lengths, labels_lengths)
+        return ops.tdt_align(logits, labels, frames_lengths, labels_lengths, tuple(durations), blank, float(sigma))
+
+
 class TDTLoss(torch.nn.Module):
     """:func:`tdt_loss_from_logits` as a module: stores ``durations``, ``sigma``, ``blank``, ``fastemit_lambda`` and
     ``reduction``."""
