@@ -28,8 +28,8 @@
  * is NaN.
  *
  * Not here: the mix with the standard loss (NeMo's omega), a gradient clamp, a forward/backward mismatch guard, the
- * compact layout, the joint network.  A lattice has at most 1024 columns: U <= 1024 (the sweeps hold a column per lane of
- * one workgroup); a wider one is refused.
+ * compact layout.  The joint network in front of the logits, fused into this loss, is warp_rnnt_amd_tdt_joint.h.  A lattice
+ * has at most 1024 columns: U <= 1024 (the sweeps hold a column per lane of one workgroup); a wider one is refused.
  *
  * Everything refused -- an unknown dtype, durations that are not as above, V < 2, a blank outside [0,V), U > 1024 or sizes
  * rnnt_amd_workspace_size refuses, sigma < 0 or not finite, a null or misaligned workspace, a null or misaligned logits /

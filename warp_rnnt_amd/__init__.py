@@ -8,7 +8,8 @@ Layout
   fused.py         rnnt_loss_from_logits: logits -> loss -> d/d logits, log-probabilities never in HBM
   hat.py           hat_loss_from_logits / HATLoss / hat_log_probs: the factorised-blank (HAT) loss on the same path
   tdt.py           tdt_loss_from_logits / TDTLoss / tdt_log_probs: the token-and-duration (TDT) loss, a lattice of its own;
-                   tdt_align: best-path token frames and durations of that lattice
+                   tdt_align: best-path token frames and durations of that lattice;
+                   tdt_loss_from_joint / TDTJointLoss: the joint network fused into the TDT loss
   align.py         rnnt_align / alignment_mask: best-path (Viterbi) alignments from the same lattice, any of its inputs
   joint.py         rnnt_loss_from_joint / JointLoss: the joint network (act, dropout, projection) fused into the loss
   compat.py        the same under torchaudio's / warp-transducer's signatures (rnnt_loss, RNNTLoss; gradient clamp)

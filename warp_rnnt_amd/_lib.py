@@ -135,6 +135,19 @@ TDT_ALIGN_SYMBOLS = {
 # (tests/test_host_tdt_align.py holds this one to it).  Folding the two tuples into one is for a change that may touch the
 # tests which pin ADDITIVE to its five.
 ADDITIVE_NEXT = ((TDT_ALIGN_SYMBOLS, "warp_rnnt_amd_tdt_align.h"),)
+# every symbol include/warp_rnnt_amd_tdt_joint.h declares (the joint network fused into the TDT loss; additive: it did not
+# move the version): the size is a function of (N, T, U, H, V, D); the forward is (stream, workspace, dtype, activation, f,
+# g, weight, bias, labels, xn, yn, durations, D, costs, stats, grads, N, T, U, H, V, blank, sigma, fastemit_lambda, p,
+# seed) with durations in host memory and seed a device pointer; the backward is (stream, workspace, dtype, activation, f,
+# g, weight, bias, labels, xn, yn, stats, grads, grad_costs, df, dg, dweight, dbias, N, T, U, H, V, D, blank, p, seed)
+TDT_JOINT_SYMBOLS = {
+    "rnnt_amd_tdt_joint_workspace_size": (_sz, [_i] * 6),
+    "rnnt_amd_tdt_joint_loss": (_i, [_vp, _vp, _i, _i] + [_vp] * 8 + [_i] + [_vp] * 3 + [_i] * 6 + [_f, _f, _f, _vp]),
+    "rnnt_amd_tdt_joint_backward": (_i, [_vp, _vp, _i, _i] + [_vp] * 14 + [_i] * 7 + [_f, _vp]),
+}
+# the families behind ADDITIVE_NEXT, under the same contract (tests/test_host_tdt_joint.py holds this one to it); a tuple
+# of its own because tests pin the two above to their contents
+ADDITIVE_TDT_JOINT = ((TDT_JOINT_SYMBOLS, "warp_rnnt_amd_tdt_joint.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -172,7 +185,7 @@ def load():
         raise RuntimeError(f"{path} reports C-ABI version {L.rnnt_amd_version()}, this package binds version "
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
-    for table, header in ADDITIVE + ADDITIVE_NEXT:
+    for table, header in ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT:
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

@@ -2,13 +2,14 @@
 // own behind one of the loss's producers.  The joint network (include/warp_rnnt_amd.h) and its dropout
 // (include/warp_rnnt_amd_joint_dropout.h), the factorised-blank loss (include/warp_rnnt_amd_hat.h), best-path alignments
 // (include/warp_rnnt_amd_align.h), the token-and-duration loss (include/warp_rnnt_amd_tdt.h: producer, sweeps and
-// gradient kernel all its own) and its best-path alignments (include/warp_rnnt_amd_tdt_align.h).  Host-side orchestration
-// only: argument checks, workspace carving, launches.
+// gradient kernel all its own), its best-path alignments (include/warp_rnnt_amd_tdt_align.h) and the joint network fused
+// into it (include/warp_rnnt_amd_tdt_joint.h).  Host-side orchestration only: argument checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd_align.h"
 #include "../../include/warp_rnnt_amd_hat.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
 #include "../../include/warp_rnnt_amd_tdt.h"
 #include "../../include/warp_rnnt_amd_tdt_align.h"
+#include "../../include/warp_rnnt_amd_tdt_joint.h"
 
 #include "align.h"
 #include "api_common.h"
@@ -16,6 +17,7 @@
 #include "philox.h"
 #include "tdt.h"
 #include "tdt_align.h"
+#include "tdt_joint.h"
 
 using namespace rnnt;
 
@@ -140,6 +142,23 @@ TdtAlignWorkspace tdt_align_layout(Carver& c, int N, int T, int U, int D) {
     aw.plane = c.take<float>((size_t)N * T * U * (size_t)(2 + D));
     aw.dec = c.take<unsigned char>(tdt_align_dec_count(N, T, U));
     return aw;
+}
+
+// The joint network fused into the TDT loss (tdt_joint.hip).  Behind the TDT layout: W^T (H,Vp) and the weight kernel's fp32
+// partials for a weight of V + D rows, as joint_layout has them, in less room: split 0 of d weight goes straight into
+// dweight, so there are splits - 1 partials, and W^T -- read by the two kernels in front of the weight kernel, dead when it
+// starts -- shares their storage (the larger of the two is reserved).
+JointWorkspace tdt_joint_layout(Carver& c, int N, int T, int U, int H, int W) {
+    const size_t vp = (size_t)joint_vpad(W), splits = (size_t)joint_w_splits(N, T, U, H, W, RNNT_DTYPE_F32);
+    const size_t wt = (size_t)H * vp, parts = (splits - 1) * vp * H;
+    JointWorkspace jw;
+    jw.dw_part = c.take<float>(wt > parts ? wt : parts);
+    jw.wt = jw.dw_part;
+    jw.db_part = c.take<float>(splits * vp);
+    return jw;
+}
+inline bool tdt_joint_args_ok(int dtype, int activation, int N, int T, int U, int H, int V, int D, int blank) {
+    return tdt_shape_ok(dtype, N, T, U, V, D, blank) && joint_args_ok(dtype, activation, N, T, U, H, V + D, blank);
 }
 
 }  // namespace
@@ -359,6 +378,72 @@ rnntStatus_t rnnt_amd_tdt_align(rnntStream_t stream, void* workspace, int dtype,
         return RNNT_STATUS_WARP_FAILED;
     if (launch_tdt_align_trace(stream, aw.dec, xn, yn, scores, emit_frames, emit_durations, dur, N, T, U) != hipSuccess)
         return RNNT_STATUS_WARP_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_tdt_joint.h: the joint network fused into the TDT loss.  rnnt_amd_tdt_loss_logits's shape with
+// tdt_joint.hip's MFMA producer in front: it fills the plane (and the per-cell statistics), the sweeps and the gradient
+// kernel of tdt.hip run as they are; the backward recomputes z.
+size_t rnnt_amd_tdt_joint_workspace_size(int N, int T, int U, int H, int V, int D) {
+    if (!tdt_joint_args_ok(RNNT_DTYPE_F32, RNNT_ACT_TANH, N, T, U, H, V, D, 0)) return 0;
+    Carver c(nullptr);
+    tdt_layout(c, N, T, U, D);
+    tdt_joint_layout(c, N, T, U, H, V + D);
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_tdt_joint_loss(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                     const void* g, const void* weight, const float* bias, const int* labels,
+                                     const int* xn, const int* yn, const int* durations, int D, float* costs, float* stats,
+                                     float* grads, int N, int T, int U, int H, int V, int blank, float sigma,
+                                     float fastemit_lambda, float p, const uint64_t* seed) {
+    if (!tdt_joint_args_ok(dtype, activation, N, T, U, H, V, D, blank) || !tdt_durations_ok(durations, D))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!(sigma >= 0.0f && sigma <= 3.402823466e+38f) || !dropout_ok(p, seed))       // (false for a NaN)
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !f || !g || !weight || !xn || !yn || !costs || labels_missing(U, labels) ||
+        (grads && !stats))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!joint_inputs_aligned(f, g, weight, bias) || !aligned(stats, 16) || !aligned(grads, 4) || !aligned(costs, 4) ||
+        !aligned(labels, 4) || !aligned(xn, 4) || !aligned(yn, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const TdtWorkspace tw = tdt_layout(c, N, T, U, D);
+    const TdtDurations dur = tdt_durations(durations, D);
+    if (launch_tdt_joint_fwd(stream, dtype, activation, f, g, weight, bias, labels, xn, yn, tw.plane,
+                             grads ? stats : nullptr, N, T, U, H, V, D, blank, sigma, p,
+                             p > 0.0f ? seed : nullptr) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    if (launch_tdt_sweeps(stream, tw.plane, xn, yn, tw.alphas, grads ? tw.betas : nullptr, tw.ll, costs, dur, N, T, U) !=
+        hipSuccess)
+        return RNNT_STATUS_WARP_FAILED;
+    if (grads && launch_tdt_grads(stream, tw.plane, tw.alphas, tw.betas, tw.ll, xn, yn, grads, dur, N, T, U,
+                                  fastemit_lambda) != hipSuccess)
+        return RNNT_STATUS_GRADS_BLANK_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_tdt_joint_backward(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                         const void* g, const void* weight, const float* bias, const int* labels,
+                                         const int* xn, const int* yn, const float* stats, const float* grads,
+                                         const float* grad_costs, void* df, void* dg, float* dweight, float* dbias, int N,
+                                         int T, int U, int H, int V, int D, int blank, float p, const uint64_t* seed) {
+    if (!tdt_joint_args_ok(dtype, activation, N, T, U, H, V, D, blank) || !dropout_ok(p, seed))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !f || !g || !weight || !xn || !yn || !stats || !grads || labels_missing(U, labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!joint_inputs_aligned(f, g, weight, bias) || !aligned(stats, 16) || !aligned(grads, 4) ||
+        !aligned(grad_costs, 4) || !aligned(labels, 4) || !aligned(xn, 4) || !aligned(yn, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0 || (!df && !dg && !dweight && !dbias)) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    tdt_layout(c, N, T, U, D);
+    const JointWorkspace jw = tdt_joint_layout(c, N, T, U, H, V + D);
+    if (launch_tdt_joint_bwd(stream, dtype, activation, f, g, weight, bias, labels, xn, yn, stats, grads, grad_costs, jw.wt,
+                             jw.dw_part, jw.db_part, joint_w_splits(N, T, U, H, V + D, dtype), df, dg, dweight, dbias, N,
+                             T, U, H, V, D, blank, p, p > 0.0f ? seed : nullptr) != hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
 

@@ -639,6 +639,68 @@ def tdt_logits_backward(logits, labels, grads, grad_costs, num_durations, blank=
     return out
 
 
+def tdt_joint_loss(f, g, weight, bias, labels, xn, yn, durations, activation="tanh", blank=0, sigma=0.0,
+                   fastemit_lambda=0.0, with_grads=True, dropout=0.0, seed=None):
+    """The joint network fused into the TDT loss (include/warp_rnnt_amd_tdt_joint.h): f (N,T,H), g (N,U,H), weight
+    (V+D,H) of one dtype (fp32 / bf16 / fp16) with D = len(durations), bias (V+D,) fp32 or None; validated by the caller.
+    Returns costs (N,) fp32 and, with_grads, stats (N,T,U,4) fp32 -- (max, log sum) of the token logits and of the
+    duration logits of every cell -- and the per-cell sums (2+D,N,T,U) fp32 of :func:`tdt_loss` -- what
+    :func:`tdt_joint_backward` reads (else None, None: no beta sweep, no G plane, no stats).  dropout, seed: as
+    :func:`joint_loss`."""
+    L = _lib.load()
+    N, T, H = f.shape
+    U = g.shape[1]
+    D = len(durations)
+    V = weight.shape[0] - D
+    dev = f.device
+    ds = _tdt_check(V, D, blank, durations, sigma)
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        stats = torch.empty((N, T, U, 4), dtype=torch.float32, device=dev) if with_grads else None
+        grads = torch.empty((2 + D, N, T, U), dtype=torch.float32, device=dev) if with_grads else None
+        if N == 0:
+            return costs, stats, grads
+        ws = _workspace(dev, L.rnnt_amd_tdt_joint_workspace_size, "N T U H V D", N, T, U, H, V, D)
+        host_durations = (ctypes.c_int * D)(*ds)          # read during the call: nothing of it is needed afterwards
+        p, seed_ptr = _dropout_args(dropout, seed) if dropout > 0 else (0.0, 0)
+        _check(L.rnnt_amd_tdt_joint_loss(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[f.dtype], ACTIVATIONS[activation],
+                                         f.data_ptr(), g.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(labels),
+                                         xn.data_ptr(), yn.data_ptr(), host_durations, D, costs.data_ptr(), _ptr(stats),
+                                         _ptr(grads), N, T, U, H, V, blank, float(sigma), float(fastemit_lambda), p,
+                                         seed_ptr))
+    return costs, stats, grads
+
+
+def tdt_joint_backward(f, g, weight, bias, labels, xn, yn, stats, grads, grad_costs, num_durations, activation="tanh",
+                       blank=0, need_f=True, need_g=True, need_weight=True, need_bias=True, dropout=0.0, seed=None):
+    """d(sum_n grad_costs[n]*cost[n]) / d(f, g, weight, bias) of :func:`tdt_joint_loss`: df / dg in f's dtype, dweight
+    (V+D,H) / dbias (V+D,) fp32; None for what is not asked for.  dropout, seed: those of the forward."""
+    L = _lib.load()
+    N, T, H = f.shape
+    U = g.shape[1]
+    D = num_durations
+    W = weight.shape[0]
+    dev = f.device
+    with torch.cuda.device(dev):
+        df = torch.empty_like(f) if need_f else None
+        dg = torch.empty_like(g) if need_g else None
+        dw = torch.empty((W, H), dtype=torch.float32, device=dev) if need_weight else None
+        db = torch.empty((W,), dtype=torch.float32, device=dev) if (need_bias and bias is not None) else None
+        if N == 0:
+            for t in (df, dg, dw, db):
+                if t is not None:
+                    t.zero_()
+            return df, dg, dw, db
+        ws = _workspace(dev, L.rnnt_amd_tdt_joint_workspace_size, "N T U H V D", N, T, U, H, W - D, D)
+        p, seed_ptr = _dropout_args(dropout, seed) if dropout > 0 else (0.0, 0)
+        _check(L.rnnt_amd_tdt_joint_backward(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[f.dtype], ACTIVATIONS[activation],
+                                             f.data_ptr(), g.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(labels),
+                                             xn.data_ptr(), yn.data_ptr(), stats.data_ptr(), grads.data_ptr(),
+                                             _ptr(grad_costs), _ptr(df), _ptr(dg), _ptr(dw), _ptr(db), N, T, U, H, W - D, D,
+                                             blank, p, seed_ptr))
+    return df, dg, dw, db
+
+
 def tdt_align(logits, labels, xn, yn, durations, blank=0, sigma=0.0):
     """Best-path alignments over the TDT lattice (include/warp_rnnt_amd_tdt_align.h): logits (N,T,U,V+D) as
     :func:`tdt_loss` takes them, validated by the caller.  Returns scores (N,) fp32 -- the log-probability of the best path,
