@@ -7,6 +7,8 @@ Layout
   ops.py           torch-tensor front ends of the native entry points
   fused.py         rnnt_loss_from_logits: logits -> loss -> d/d logits, log-probabilities never in HBM
   hat.py           hat_loss_from_logits / HATLoss / hat_log_probs: the factorised-blank (HAT) loss on the same path
+  pruned.py        pruned_rnnt_loss_from_logits / PrunedRNNTLoss: k2-style pruned loss, logits (N,T,S,V) on a band of S label
+                   positions per frame; simple_pairs / prune_ranges / prune_joint_inputs: the rest of that recipe
   tdt.py           tdt_loss_from_logits / TDTLoss / tdt_log_probs: the token-and-duration (TDT) loss, a lattice of its own;
                    tdt_align: best-path token frames and durations of that lattice;
                    tdt_loss_from_joint / TDTJointLoss: the joint network fused into the TDT loss

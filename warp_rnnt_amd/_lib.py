@@ -148,6 +148,18 @@ TDT_JOINT_SYMBOLS = {
 # the families behind ADDITIVE_NEXT, under the same contract (tests/test_host_tdt_joint.py holds this one to it); a tuple
 # of its own because tests pin the two above to their contents
 ADDITIVE_TDT_JOINT = ((TDT_JOINT_SYMBOLS, "warp_rnnt_amd_tdt_joint.h"),)
+# every symbol include/warp_rnnt_amd_pruned.h declares (the pruned transducer loss over a band of S label positions per
+# frame; additive: it did not move the version): HAT's two argument lists with `starts` (a device pointer, (N,T) int32)
+# behind the labels and S between U and V -- the forward is (stream, workspace, dtype, logits, labels, starts, xn, yn,
+# costs, grads, N, T, U, S, V, blank, fastemit_lambda), the backward (stream, dtype, logits, labels, starts,
+# grads_diagonal, grad_costs, dlogits, N, T, U, S, V, blank)
+PRUNED_SYMBOLS = {
+    "rnnt_amd_pruned_loss_logits": (_i, [_vp, _vp, _i] + [_vp] * 7 + [_i] * 6 + [_f]),
+    "rnnt_amd_pruned_logits_backward": (_i, [_vp, _i] + [_vp] * 6 + [_i] * 6),
+}
+# behind ADDITIVE_TDT_JOINT, under the same contract (tests/test_host_pruned.py holds this one to it); a tuple of its own
+# for the same reason
+ADDITIVE_PRUNED = ((PRUNED_SYMBOLS, "warp_rnnt_amd_pruned.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -185,7 +197,7 @@ def load():
         raise RuntimeError(f"{path} reports C-ABI version {L.rnnt_amd_version()}, this package binds version "
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
-    for table, header in ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT:
+    for table, header in ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED:
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

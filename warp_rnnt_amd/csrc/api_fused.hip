@@ -1,12 +1,14 @@
 // C ABI of libwarp_rnnt_amd.so, the fused family: a producer of its own in front of the loss's sweeps -- or a sweep of its
 // own behind one of the loss's producers.  The joint network (include/warp_rnnt_amd.h) and its dropout
-// (include/warp_rnnt_amd_joint_dropout.h), the factorised-blank loss (include/warp_rnnt_amd_hat.h), best-path alignments
+// (include/warp_rnnt_amd_joint_dropout.h), the factorised-blank loss (include/warp_rnnt_amd_hat.h), the pruned loss over a
+// band of the lattice (include/warp_rnnt_amd_pruned.h), best-path alignments
 // (include/warp_rnnt_amd_align.h), the token-and-duration loss (include/warp_rnnt_amd_tdt.h: producer, sweeps and
 // gradient kernel all its own), its best-path alignments (include/warp_rnnt_amd_tdt_align.h) and the joint network fused
 // into it (include/warp_rnnt_amd_tdt_joint.h).  Host-side orchestration only: argument checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd_align.h"
 #include "../../include/warp_rnnt_amd_hat.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
+#include "../../include/warp_rnnt_amd_pruned.h"
 #include "../../include/warp_rnnt_amd_tdt.h"
 #include "../../include/warp_rnnt_amd_tdt_align.h"
 #include "../../include/warp_rnnt_amd_tdt_joint.h"
@@ -15,6 +17,7 @@
 #include "api_common.h"
 #include "hat.h"
 #include "philox.h"
+#include "pruned.h"
 #include "tdt.h"
 #include "tdt_align.h"
 #include "tdt_joint.h"
@@ -94,6 +97,12 @@ rnntStatus_t joint_backward(rnntStream_t stream, void* workspace, int dtype, int
 // the dropout of the *_dropout entries: p in [0,1) (false for a NaN); p > 0 needs the device word
 inline bool dropout_ok(float p, const uint64_t* seed) {
     return p >= 0.0f && p < 1.0f && (p == 0.0f || (seed && aligned(seed, 8)));
+}
+
+// the band of a pruned call (pruned.hip): S label positions per frame, at most the lattice's U; rows of (N,T,S) numbered
+// in 32 bits
+inline bool pruned_band_ok(int N, int T, int U, int S) {
+    return S >= 1 && S <= U && (int64_t)N * T * S < (int64_t)1 << 32;
 }
 
 // Best-path alignments.  Behind the loss layout: the decision words, then the columns parked between column stripes.
@@ -256,6 +265,40 @@ rnntStatus_t rnnt_amd_hat_logits_backward(rnntStream_t stream, int dtype, const 
     if (N == 0) return RNNT_STATUS_SUCCESS;
     if (launch_hat_logits_backward(stream, dtype, logits, labels, grads_diagonal, grad_costs, dlogits, N, T, U, V, blank) !=
         hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_pruned.h: the pruned transducer loss.  The HAT entry's shape: a producer of its own (pruned.hip)
+// fills the pair plane -- the floor everywhere, the band's pairs over it -- the sweeps and the gradient pairs are the
+// standard ones over the (N,T,U) grid; the backward is one streaming launch over the (N,T,S,V) logits.
+rnntStatus_t rnnt_amd_pruned_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                         const int* labels, const int* starts, const int* xn, const int* yn, float* costs,
+                                         float* grads, int N, int T, int U, int S, int V, int blank,
+                                         float fastemit_lambda) {
+    if (!dtype_ok(dtype) || !dims_ok(N, T, U) || V < 2 || !vocab_ok(V, blank) || !pruned_band_ok(N, T, U, S))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !logits || !starts || !xn || !yn || !costs || labels_missing(U, labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const Workspace w = loss_layout(c, N, T, U);
+    if (launch_pruned_pairs(stream, dtype, logits, labels, starts, w.ws2, N, T, U, S, V, blank) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    return sweeps_and_pair_grads(stream, w, xn, yn, costs, grads ? grads : w.ws2, WRITE_SKEWED2, N, T, U, nullptr,
+                                 fastemit_lambda);
+}
+
+rnntStatus_t rnnt_amd_pruned_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* labels,
+                                             const int* starts, const float* grads_diagonal, const float* grad_costs,
+                                             void* dlogits, int N, int T, int U, int S, int V, int blank) {
+    if (!dtype_ok(dtype) || !dims_ok(N, T, U) || V < 2 || !vocab_ok(V, blank) || !pruned_band_ok(N, T, U, S))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!logits || !starts || !grads_diagonal || !aligned(grads_diagonal, 8) || !dlogits || labels_missing(U, labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    if (launch_pruned_logits_backward(stream, dtype, logits, labels, starts, grads_diagonal, grad_costs, dlogits, N, T, U,
+                                      S, V, blank) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
 }

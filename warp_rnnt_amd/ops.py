@@ -585,6 +585,53 @@ def hat_logits_backward(logits, labels, grads, grad_costs, blank=0):
     return out
 
 
+def _pruned_check(S, U, V, blank):
+    if V < 2 or not 0 <= blank < V or not 1 <= S <= U:
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the pruned loss needs V >= 2, a blank that "
+                           f"is a vocabulary index and a band of 1 <= S <= U positions (V={V}, blank={blank}, S={S}, U={U})")
+
+
+def pruned_loss(logits, labels, starts, xn, yn, blank=0, fastemit_lambda=0.0, with_grads=True):
+    """The pruned transducer loss on the fused path (include/warp_rnnt_amd_pruned.h): logits (N,T,S,V) fp32 / bf16 / fp16,
+    labels (N,U-1), starts (N,T) int32 contiguous, validated by the caller.  Returns costs (N,) fp32 -- >= 1e29 for an
+    utterance whose band holds no path -- and, with_grads, the gradient pairs (N,T,U,2) fp32 of the whole lattice in the
+    diagonal-major layout -- what :func:`pruned_logits_backward` reads (else None)."""
+    L = _lib.load()
+    N, T, S, V = logits.shape
+    U = labels.shape[1] + 1
+    dev = logits.device
+    _pruned_check(S, U, V, blank)
+    _mismatch.poll(dev)
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        grads = torch.empty((N, T, U, 2), dtype=torch.float32, device=dev) if with_grads else None
+        if N == 0:
+            return costs, grads
+        ws = _workspace(dev, L.rnnt_amd_workspace_size, "N T U", N, T, U)
+        _check(L.rnnt_amd_pruned_loss_logits(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
+                                             _ptr(labels), starts.data_ptr(), xn.data_ptr(), yn.data_ptr(),
+                                             costs.data_ptr(), _ptr(grads), N, T, U, S, V, blank, float(fastemit_lambda)))
+    return costs, grads
+
+
+def pruned_logits_backward(logits, labels, starts, grads, grad_costs, blank=0):
+    """d(sum_n grad_costs[n]*cost[n]) / d(logits) of :func:`pruned_loss`, (N,T,S,V) in the logits' dtype (the fp32 result
+    rounded once); grads: the pairs the forward returned.  An utterance with grad_costs[n] == 0 gets exactly zero rows
+    whatever its pairs hold."""
+    L = _lib.load()
+    N, T, S, V = logits.shape
+    U = labels.shape[1] + 1
+    dev = logits.device
+    with torch.cuda.device(dev):
+        out = torch.empty_like(logits)
+        if N == 0:
+            return out
+        _check(L.rnnt_amd_pruned_logits_backward(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(), _ptr(labels),
+                                                 starts.data_ptr(), grads.data_ptr(), _ptr(grad_costs), out.data_ptr(),
+                                                 N, T, U, S, V, blank))
+    return out
+
+
 def _tdt_check(V, D, blank, durations, sigma):
     """The refusals of include/warp_rnnt_amd_tdt.h that depend on values, with their reasons spelt out."""
     ds = [int(d) for d in durations]
