@@ -9,6 +9,8 @@ Layout
   hat.py           hat_loss_from_logits / HATLoss / hat_log_probs: the factorised-blank (HAT) loss on the same path
   pruned.py        pruned_rnnt_loss_from_logits / PrunedRNNTLoss: k2-style pruned loss, logits (N,T,S,V) on a band of S label
                    positions per frame; simple_pairs / prune_ranges / prune_joint_inputs: the rest of that recipe
+  simple.py        simple_rnnt_loss / SimpleRNNTLoss / batch_log_unigram: that recipe's smoothed first pass over the trivial
+                   joiner am + lm (k2's rnnt_loss_smoothed), an MFMA GEMM in front of the lattice, two behind it
   tdt.py           tdt_loss_from_logits / TDTLoss / tdt_log_probs: the token-and-duration (TDT) loss, a lattice of its own;
                    tdt_align: best-path token frames and durations of that lattice;
                    tdt_loss_from_joint / TDTJointLoss: the joint network fused into the TDT loss

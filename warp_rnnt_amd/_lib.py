@@ -160,6 +160,19 @@ PRUNED_SYMBOLS = {
 # behind ADDITIVE_TDT_JOINT, under the same contract (tests/test_host_pruned.py holds this one to it); a tuple of its own
 # for the same reason
 ADDITIVE_PRUNED = ((PRUNED_SYMBOLS, "warp_rnnt_amd_pruned.h"),)
+# every symbol include/warp_rnnt_amd_simple.h declares (the smoothed first pass of the pruned recipe over the trivial joiner
+# am + lm; additive: it did not move the version): the size is a function of (N, T, U); the forward is (stream, workspace,
+# dtype, am, lm, q, labels, xn, yn, costs, pair_grads, znorm, N, T, U, V, blank, lm_only_scale, am_only_scale,
+# fastemit_lambda), the backward (stream, workspace, dtype, am, lm, q, labels, xn, yn, pair_grads, znorm, grad_costs, dam,
+# dlm, dq_partials, N, T, U, V, blank, lm_only_scale, am_only_scale)
+SIMPLE_SYMBOLS = {
+    "rnnt_amd_simple_workspace_size": (_sz, [_i, _i, _i]),
+    "rnnt_amd_simple_loss": (_i, [_vp, _vp, _i] + [_vp] * 9 + [_i] * 5 + [_f] * 3),
+    "rnnt_amd_simple_backward": (_i, [_vp, _vp, _i] + [_vp] * 12 + [_i] * 5 + [_f] * 2),
+}
+# behind ADDITIVE_PRUNED, under the same contract (tests/test_host_simple.py holds this one to it); a tuple of its own for
+# the same reason
+ADDITIVE_SIMPLE = ((SIMPLE_SYMBOLS, "warp_rnnt_amd_simple.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -197,7 +210,7 @@ def load():
         raise RuntimeError(f"{path} reports C-ABI version {L.rnnt_amd_version()}, this package binds version "
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
-    for table, header in ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED:
+    for table, header in ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED + ADDITIVE_SIMPLE:
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

@@ -1,7 +1,8 @@
 // C ABI of libwarp_rnnt_amd.so, the fused family: a producer of its own in front of the loss's sweeps -- or a sweep of its
 // own behind one of the loss's producers.  The joint network (include/warp_rnnt_amd.h) and its dropout
 // (include/warp_rnnt_amd_joint_dropout.h), the factorised-blank loss (include/warp_rnnt_amd_hat.h), the pruned loss over a
-// band of the lattice (include/warp_rnnt_amd_pruned.h), best-path alignments
+// band of the lattice (include/warp_rnnt_amd_pruned.h), the smoothed first pass of its recipe over the trivial joiner
+// (include/warp_rnnt_amd_simple.h), best-path alignments
 // (include/warp_rnnt_amd_align.h), the token-and-duration loss (include/warp_rnnt_amd_tdt.h: producer, sweeps and
 // gradient kernel all its own), its best-path alignments (include/warp_rnnt_amd_tdt_align.h) and the joint network fused
 // into it (include/warp_rnnt_amd_tdt_joint.h).  Host-side orchestration only: argument checks, workspace carving, launches.
@@ -9,6 +10,7 @@
 #include "../../include/warp_rnnt_amd_hat.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
 #include "../../include/warp_rnnt_amd_pruned.h"
+#include "../../include/warp_rnnt_amd_simple.h"
 #include "../../include/warp_rnnt_amd_tdt.h"
 #include "../../include/warp_rnnt_amd_tdt_align.h"
 #include "../../include/warp_rnnt_amd_tdt_joint.h"
@@ -18,6 +20,7 @@
 #include "hat.h"
 #include "philox.h"
 #include "pruned.h"
+#include "simple.h"
 #include "tdt.h"
 #include "tdt_align.h"
 #include "tdt_joint.h"
@@ -103,6 +106,26 @@ inline bool dropout_ok(float p, const uint64_t* seed) {
 // in 32 bits
 inline bool pruned_band_ok(int N, int T, int U, int S) {
     return S >= 1 && S <= U && (int64_t)N * T * S < (int64_t)1 << 32;
+}
+
+// The simple loss (simple.hip).  Behind the loss layout: the row statistics of am and lm, then the backward's row sums
+// (simple.h: SimpleStats).
+SimpleStats simple_layout(Carver& c, int N, int T, int U) {
+    SimpleStats st;
+    st.sa = c.take<float>((size_t)N * T * 4);
+    st.sl = c.take<float>((size_t)N * U * 4);
+    st.ra = c.take<float>((size_t)N * T * 2);
+    st.rl = c.take<float>((size_t)N * U * 4);
+    return st;
+}
+inline bool simple_shape_ok(int dtype, int N, int T, int U, int V, int blank) {
+    return dtype_ok(dtype) && dims_ok(N, T, U) && T <= SIMPLE_MAX_ROWS && U <= SIMPLE_MAX_ROWS && V >= 2 &&
+           V <= (1 << 24) && vocab_ok(V, blank);
+}
+// the two smoothing scales: finite, not negative, their fp32 sum at most 1 (false for a NaN); am_only_scale needs q
+inline bool simple_scales_ok(float lm_only_scale, float am_only_scale, const float* q) {
+    return lm_only_scale >= 0.0f && am_only_scale >= 0.0f && lm_only_scale + am_only_scale <= 1.0f &&
+           (am_only_scale == 0.0f || q);
 }
 
 // Best-path alignments.  Behind the loss layout: the decision words, then the columns parked between column stripes.
@@ -299,6 +322,65 @@ rnntStatus_t rnnt_amd_pruned_logits_backward(rnntStream_t stream, int dtype, con
     if (N == 0) return RNNT_STATUS_SUCCESS;
     if (launch_pruned_logits_backward(stream, dtype, logits, labels, starts, grads_diagonal, grad_costs, dlogits, N, T, U,
                                       S, V, blank) != hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_simple.h: the smoothed first pass of the pruned recipe.  The HAT entry's shape with a GEMM in the
+// producer (simple.hip): it fills the pair plane and the normaliser plane, the sweeps and the gradient pairs are the
+// standard ones, the pairs written row-major for the caller; the backward is the statistics, the row sums and two GEMMs.
+size_t rnnt_amd_simple_workspace_size(int N, int T, int U) {
+    if (!dims_ok(N, T, U) || T > SIMPLE_MAX_ROWS || U > SIMPLE_MAX_ROWS) return 0;
+    Carver c(nullptr);
+    loss_layout(c, N, T, U);
+    simple_layout(c, N, T, U);
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_simple_loss(rnntStream_t stream, void* workspace, int dtype, const void* am, const void* lm,
+                                  const float* q, const int* labels, const int* xn, const int* yn, float* costs,
+                                  float* pair_grads, float* znorm, int N, int T, int U, int V, int blank,
+                                  float lm_only_scale, float am_only_scale, float fastemit_lambda) {
+    if (!simple_shape_ok(dtype, N, T, U, V, blank) || !simple_scales_ok(lm_only_scale, am_only_scale, q))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !am || !lm || !xn || !yn || !costs || labels_missing(U, labels) ||
+        (pair_grads && !znorm))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!aligned(am, dtype_size(dtype)) || !aligned(lm, dtype_size(dtype)) || !aligned(q, 4) || !aligned(labels, 4) ||
+        !aligned(xn, 4) || !aligned(yn, 4) || !aligned(costs, 4) || !aligned(pair_grads, 8) || !aligned(znorm, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const Workspace w = loss_layout(c, N, T, U);
+    const SimpleStats st = simple_layout(c, N, T, U);
+    if (launch_simple_pairs(stream, dtype, am, lm, am_only_scale != 0.0f ? q : nullptr, labels, st, w.ws2, znorm, N, T, U,
+                            V, blank, simple_scales(lm_only_scale, am_only_scale)) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    return sweeps_and_pair_grads(stream, w, xn, yn, costs, pair_grads ? pair_grads : w.ws2,
+                                 pair_grads ? WRITE_ROWMAJOR2 : WRITE_SKEWED2, N, T, U, nullptr, fastemit_lambda);
+}
+
+rnntStatus_t rnnt_amd_simple_backward(rnntStream_t stream, void* workspace, int dtype, const void* am, const void* lm,
+                                      const float* q, const int* labels, const int* xn, const int* yn,
+                                      const float* pair_grads, const float* znorm, const float* grad_costs, void* dam,
+                                      void* dlm, float* dq_partials, int N, int T, int U, int V, int blank,
+                                      float lm_only_scale, float am_only_scale) {
+    if (!simple_shape_ok(dtype, N, T, U, V, blank) || !simple_scales_ok(lm_only_scale, am_only_scale, q))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !am || !lm || !xn || !yn || !pair_grads || !znorm || !dam || !dlm ||
+        labels_missing(U, labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!aligned(am, dtype_size(dtype)) || !aligned(lm, dtype_size(dtype)) || !aligned(dam, dtype_size(dtype)) ||
+        !aligned(dlm, dtype_size(dtype)) || !aligned(q, 4) || !aligned(labels, 4) || !aligned(xn, 4) || !aligned(yn, 4) ||
+        !aligned(pair_grads, 8) || !aligned(znorm, 4) || !aligned(grad_costs, 4) || !aligned(dq_partials, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    loss_layout(c, N, T, U);
+    const SimpleStats st = simple_layout(c, N, T, U);
+    if (launch_simple_backward(stream, dtype, am, lm, am_only_scale != 0.0f ? q : nullptr, labels, xn, yn, pair_grads,
+                               znorm, grad_costs, st, dam, dlm, dq_partials, N, T, U, V, blank,
+                               simple_scales(lm_only_scale, am_only_scale)) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
 }

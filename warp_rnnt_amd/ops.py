@@ -632,6 +632,69 @@ def pruned_logits_backward(logits, labels, starts, grads, grad_costs, blank=0):
     return out
 
 
+def _simple_check(V, blank, lm_only_scale, am_only_scale, q):
+    """The refusals of include/warp_rnnt_amd_simple.h that depend on values, with their reasons spelt out; returns the
+    two scales as the fp32 values the C entries receive."""
+    if V < 2 or not 0 <= blank < V:
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the simple loss needs V >= 2 and a blank "
+                           f"that is a vocabulary index (V={V}, blank={blank})")
+    c1, c2 = ctypes.c_float(lm_only_scale).value, ctypes.c_float(am_only_scale).value
+    if not (c1 >= 0.0 and c2 >= 0.0 and ctypes.c_float(c1 + c2).value <= 1.0):          # (false for a NaN)
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the simple loss needs finite scales "
+                           f"lm_only_scale >= 0, am_only_scale >= 0 with a sum of at most 1 "
+                           f"(lm_only_scale={lm_only_scale}, am_only_scale={am_only_scale})")
+    if c2 != 0.0 and q is None:
+        raise RuntimeError("rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): am_only_scale != 0 needs the log unigram q")
+    return c1, c2
+
+
+def simple_loss(am, lm, q, labels, xn, yn, blank=0, lm_only_scale=0.0, am_only_scale=0.0, fastemit_lambda=0.0,
+                with_grads=True):
+    """The smoothed simple loss (include/warp_rnnt_amd_simple.h): am (N,T,V) and lm (N,U,V) fp32 / bf16 / fp16 of one
+    dtype, q (V,) fp32 or None, labels (N,U-1), validated by the caller.  Returns costs (N,) fp32 and, with_grads, the
+    gradient pairs d cost / d pair (N,T,U,2) fp32 row-major and the normaliser plane (N,T,U) fp32 -- what
+    :func:`simple_backward` reads (else None, None)."""
+    L = _lib.load()
+    N, T, V = am.shape
+    U = lm.shape[1]
+    dev = am.device
+    c1, c2 = _simple_check(V, blank, lm_only_scale, am_only_scale, q)
+    _mismatch.poll(dev)
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        grads = torch.empty((N, T, U, 2), dtype=torch.float32, device=dev) if with_grads else None
+        znorm = torch.empty((N, T, U), dtype=torch.float32, device=dev) if with_grads else None
+        if N == 0:
+            return costs, grads, znorm
+        ws = _workspace(dev, L.rnnt_amd_simple_workspace_size, "N T U", N, T, U)
+        _check(L.rnnt_amd_simple_loss(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[am.dtype], am.data_ptr(), lm.data_ptr(),
+                                      _ptr(q), _ptr(labels), xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(grads),
+                                      _ptr(znorm), N, T, U, V, blank, c1, c2, float(fastemit_lambda)))
+    return costs, grads, znorm
+
+
+def simple_backward(am, lm, q, labels, xn, yn, grads, znorm, grad_costs, blank=0, lm_only_scale=0.0, am_only_scale=0.0):
+    """d(sum_n grad_costs[n]*cost[n]) / d am, / d lm of :func:`simple_loss` in the inputs' dtype (the fp32 result rounded
+    once) and, with am_only_scale != 0, / d q (V,) fp32 with lm held fixed (else None); grads, znorm: what the forward
+    returned."""
+    L = _lib.load()
+    N, T, V = am.shape
+    U = lm.shape[1]
+    dev = am.device
+    c1, c2 = _simple_check(V, blank, lm_only_scale, am_only_scale, q)
+    with torch.cuda.device(dev):
+        dam, dlm = torch.empty_like(am), torch.empty_like(lm)
+        parts = torch.empty((N, V), dtype=torch.float32, device=dev) if c2 != 0.0 else None
+        if N == 0:
+            return dam, dlm, None if parts is None else parts.sum(0)
+        ws = _workspace(dev, L.rnnt_amd_simple_workspace_size, "N T U", N, T, U)
+        _check(L.rnnt_amd_simple_backward(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[am.dtype], am.data_ptr(),
+                                          lm.data_ptr(), _ptr(q), _ptr(labels), xn.data_ptr(), yn.data_ptr(),
+                                          grads.data_ptr(), znorm.data_ptr(), _ptr(grad_costs), dam.data_ptr(),
+                                          dlm.data_ptr(), _ptr(parts), N, T, U, V, blank, c1, c2))
+    return dam, dlm, None if parts is None else parts.sum(0)
+
+
 def _tdt_check(V, D, blank, durations, sigma):
     """The refusals of include/warp_rnnt_amd_tdt.h that depend on values, with their reasons spelt out."""
     ds = [int(d) for d in durations]

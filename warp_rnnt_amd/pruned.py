@@ -13,13 +13,19 @@ and every cell of the ``(N,T,U)`` grid that no row maps to is switched off.  The
 of csrc/pruned.hip -- sweeps, costs, gradient pairs -- is the one of ``rnnt_loss_from_logits`` over the full grid, with a
 finite floor (-1e30) in the cells outside the band.
 
-The recipe, in three steps (tests/test_gpu_pruned.py runs it end to end)::
+The recipe, in three steps (tests/test_gpu_simple.py runs it end to end)::
 
-    pairs  = simple_pairs(am, lm, labels)                                 # (N,T,U,2): no (N,T,U,V) tensor
-    simple = warp_rnnt.rnnt_loss(pairs, labels, xn, yn, blank=-1)          # the first pass; d/d pairs = -occupancies
-    starts = prune_ranges(torch.autograd.grad(simple.sum(), pairs, retain_graph=True)[0], xn, yn, s_range)   # (N,T) int32
+    simple, pair_grads = simple_rnnt_loss(am, lm, labels, xn, yn, lm_only_scale=0.25, return_grad=True)    # the first pass
+    starts = prune_ranges(pair_grads, xn, yn, s_range)                     # (N,T) int32; pair_grads = -occupancies
     fp, gp = prune_joint_inputs(f, g, starts, s_range)                     # (N,T,S,H) twice
     loss   = pruned_rnnt_loss_from_logits(joiner(fp, gp), labels, starts, xn, yn)
+    (simple_loss_scale * simple.sum() + loss.sum()).backward()
+
+``simple_rnnt_loss`` (simple.py, csrc/simple.hip) is k2's ``rnnt_loss_smoothed`` on the fused path: its forward already
+holds the gradient pairs and hands them back with ``return_grad=True`` -- no ``requires_grad_`` on an intermediate tensor,
+no ``autograd.grad(..., retain_graph=True)``.  The plain-torch form of its pairs without the smoothing scales,
+``simple_pairs`` below with ``warp_rnnt.rnnt_loss(pairs, labels, xn, yn, blank=-1)`` behind it, stays
+(tests/test_gpu_pruned.py runs the recipe on it).
 
 Out of scope: k2's ``modified`` topology and ``delay_penalty``; a pruned form of HAT, TDT, the joint entries, the compact
 layout or ``rnnt_align``; the gradient clamp; a sweep that visits the band's cells only (the sweeps cost what the dense
