@@ -14,6 +14,8 @@ Layout
   tdt.py           tdt_loss_from_logits / TDTLoss / tdt_log_probs: the token-and-duration (TDT) loss, a lattice of its own;
                    tdt_align: best-path token frames and durations of that lattice;
                    tdt_loss_from_joint / TDTJointLoss: the joint network fused into the TDT loss
+  multiblank.py    multiblank_loss_from_logits / MultiblankLoss: the multi-blank transducer loss (big blanks that consume
+                   2, 4, 8 ... frames), a lattice of its own
   align.py         rnnt_align / alignment_mask: best-path (Viterbi) alignments from the same lattice, any of its inputs
   joint.py         rnnt_loss_from_joint / JointLoss: the joint network (act, dropout, projection) fused into the loss
   compat.py        the same under torchaudio's / warp-transducer's signatures (rnnt_loss, RNNTLoss; gradient clamp)

@@ -16,10 +16,11 @@ LIB = os.path.join(HERE, "libwarp_rnnt_amd.so")
 SOURCES = ["api_loss.hip", "api_compact.hip", "api_reference.hip", "api_fused.hip", "lattice.hip", "lattice_ws.hip",
            "lattice_wd.hip", "grads.hip", "lsm_f32.hip", "lsm_bf16.hip", "lsm_f16.hip", "lsm_backward.hip", "to_diagonal.hip",
            "compact.hip", "expand.hip", "joint.hip", "hat.hip", "align.hip", "tdt.hip", "tdt_align.hip",
-           "tdt_joint.hip", "pruned.hip", "simple.hip"]
+           "tdt_joint.hip", "pruned.hip", "simple.hip", "multiblank.hip"]
 HEADERS = ["api_common.h", "common.h", "kernels.h", "lattice_plan.h", "lattice_launch.h", "lattice_step.h", "lattice_wd_body.h",
            "lattice_single.h", "grads_cell.h", "streaming.h", "lsm_plan.h", "lsm.h", "philox.h", "hat.h", "align.h", "row_chunks.h", "tdt.h", "tdt_align.h",
-           "joint_tile.h", "tdt_joint.h", "pruned.h", "simple.h",
+           "joint_tile.h", "tdt_joint.h", "pruned.h", "simple.h", "multiblank.h",
+           os.path.join("..", "..", "include", "warp_rnnt_amd_multiblank.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_pruned.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_simple.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd.h"), os.path.join("..", "..", "include", "warp_rnnt_amd_clamp.h"),

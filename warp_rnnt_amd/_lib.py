@@ -173,6 +173,18 @@ SIMPLE_SYMBOLS = {
 # behind ADDITIVE_PRUNED, under the same contract (tests/test_host_simple.py holds this one to it); a tuple of its own for
 # the same reason
 ADDITIVE_SIMPLE = ((SIMPLE_SYMBOLS, "warp_rnnt_amd_simple.h"),)
+# every symbol include/warp_rnnt_amd_multiblank.h declares (the multi-blank transducer loss; additive: it did not move the
+# version): the size is a function of (N, T, U, B); the forward is (stream, workspace, dtype, logits, labels, xn, yn,
+# blank_ids, blank_durations, B, costs, grads, N, T, U, V, sigma, fastemit_lambda) with the ids and durations in host
+# memory; the backward is (stream, dtype, logits, labels, grads, grad_costs, dlogits, N, T, U, V, blank_ids, B)
+MULTIBLANK_SYMBOLS = {
+    "rnnt_amd_multiblank_workspace_size": (_sz, [_i, _i, _i, _i]),
+    "rnnt_amd_multiblank_loss_logits": (_i, [_vp, _vp, _i] + [_vp] * 6 + [_i, _vp, _vp] + [_i] * 4 + [_f, _f]),
+    "rnnt_amd_multiblank_logits_backward": (_i, [_vp, _i] + [_vp] * 5 + [_i] * 4 + [_vp, _i]),
+}
+# behind ADDITIVE_SIMPLE, under the same contract (tests/test_host_multiblank.py holds this one to it); a tuple of its own
+# for the same reason
+ADDITIVE_MULTIBLANK = ((MULTIBLANK_SYMBOLS, "warp_rnnt_amd_multiblank.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -210,7 +222,8 @@ def load():
         raise RuntimeError(f"{path} reports C-ABI version {L.rnnt_amd_version()}, this package binds version "
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
-    for table, header in ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED + ADDITIVE_SIMPLE:
+    for table, header in (ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED + ADDITIVE_SIMPLE +
+                          ADDITIVE_MULTIBLANK):
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

@@ -5,10 +5,12 @@
 // (include/warp_rnnt_amd_simple.h), best-path alignments
 // (include/warp_rnnt_amd_align.h), the token-and-duration loss (include/warp_rnnt_amd_tdt.h: producer, sweeps and
 // gradient kernel all its own), its best-path alignments (include/warp_rnnt_amd_tdt_align.h) and the joint network fused
-// into it (include/warp_rnnt_amd_tdt_joint.h).  Host-side orchestration only: argument checks, workspace carving, launches.
+// into it (include/warp_rnnt_amd_tdt_joint.h), the multi-blank loss (include/warp_rnnt_amd_multiblank.h: producer, sweeps
+// and gradient kernel all its own).  Host-side orchestration only: argument checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd_align.h"
 #include "../../include/warp_rnnt_amd_hat.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
+#include "../../include/warp_rnnt_amd_multiblank.h"
 #include "../../include/warp_rnnt_amd_pruned.h"
 #include "../../include/warp_rnnt_amd_simple.h"
 #include "../../include/warp_rnnt_amd_tdt.h"
@@ -18,6 +20,7 @@
 #include "align.h"
 #include "api_common.h"
 #include "hat.h"
+#include "multiblank.h"
 #include "philox.h"
 #include "pruned.h"
 #include "simple.h"
@@ -191,6 +194,27 @@ JointWorkspace tdt_joint_layout(Carver& c, int N, int T, int U, int H, int W) {
 }
 inline bool tdt_joint_args_ok(int dtype, int activation, int N, int T, int U, int H, int V, int D, int blank) {
     return tdt_shape_ok(dtype, N, T, U, V, D, blank) && joint_args_ok(dtype, activation, N, T, U, H, V + D, blank);
+}
+
+// The multi-blank loss (multiblank.hip): the plane of 1 + B channels, alpha, beta, the log-likelihoods.
+struct MbWorkspace {
+    float* plane;
+    float* alphas;
+    float* betas;
+    float* ll;
+};
+MbWorkspace mb_layout(Carver& c, int N, int T, int U, int B) {
+    const size_t cells = (size_t)N * T * U;
+    MbWorkspace mw;
+    mw.plane = c.take<float>(cells * (size_t)(1 + B));
+    mw.alphas = c.take<float>(cells);
+    mw.betas = c.take<float>(cells);
+    mw.ll = c.take<float>((size_t)N);
+    return mw;
+}
+// the shape of a multi-blank call: the loss's sizes, a lattice that fits one workgroup, B blanks and a label beside them
+inline bool mb_shape_ok(int dtype, int N, int T, int U, int V, int B) {
+    return dtype_ok(dtype) && dims_ok(N, T, U) && U <= MB_MAX_U && B >= 1 && B <= MB_MAX_B && V >= B + 1 && V <= (1 << 24);
 }
 
 }  // namespace
@@ -568,6 +592,58 @@ rnntStatus_t rnnt_amd_tdt_joint_backward(rnntStream_t stream, void* workspace, i
     if (launch_tdt_joint_bwd(stream, dtype, activation, f, g, weight, bias, labels, xn, yn, stats, grads, grad_costs, jw.wt,
                              jw.dw_part, jw.db_part, joint_w_splits(N, T, U, H, V + D, dtype), df, dg, dweight, dbias, N,
                              T, U, H, V, D, blank, p, p > 0.0f ? seed : nullptr) != hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_multiblank.h: the multi-blank loss.  As TDT's, nothing of the standard lattice serves:
+// multiblank.hip's producer fills a plane of 1 + B channels, its sweeps write alpha, beta and the costs, its gradient kernel
+// the 1 + B sums per cell that the backward -- one streaming launch -- turns into d/d logits.
+size_t rnnt_amd_multiblank_workspace_size(int N, int T, int U, int B) {
+    if (!mb_shape_ok(RNNT_DTYPE_F32, N, T, U, B + 1, B)) return 0;
+    Carver c(nullptr);
+    mb_layout(c, N, T, U, B);
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_multiblank_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                             const int* labels, const int* xn, const int* yn, const int* blank_ids,
+                                             const int* blank_durations, int B, float* costs, float* grads, int N, int T,
+                                             int U, int V, float sigma, float fastemit_lambda) {
+    if (!mb_shape_ok(dtype, N, T, U, V, B) || !mb_ids_ok(blank_ids, B, V) || !mb_durations_ok(blank_durations, B))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!(sigma >= 0.0f && sigma <= 3.402823466e+38f)) return RNNT_STATUS_INVALID_ARGUMENT;      // (false for a NaN)
+    if (!workspace_ok(workspace) || !logits || !xn || !yn || !costs || labels_missing(U, labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!aligned(logits, dtype_size(dtype)) || !aligned(costs, 4) || !aligned(grads, 4) || !aligned(labels, 4) ||
+        !aligned(xn, 4) || !aligned(yn, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const MbWorkspace mw = mb_layout(c, N, T, U, B);
+    const MbBlanks blanks = mb_blanks(blank_ids, blank_durations, B);
+    if (launch_mb_plane(stream, dtype, logits, labels, mw.plane, N, T, U, V, blanks, sigma) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    if (launch_mb_sweeps(stream, mw.plane, xn, yn, mw.alphas, grads ? mw.betas : nullptr, mw.ll, costs, blanks, N, T, U) !=
+        hipSuccess)
+        return RNNT_STATUS_WARP_FAILED;
+    if (grads && launch_mb_grads(stream, mw.plane, mw.alphas, mw.betas, mw.ll, xn, yn, grads, blanks, N, T, U,
+                                 fastemit_lambda) != hipSuccess)
+        return RNNT_STATUS_GRADS_BLANK_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_multiblank_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* labels,
+                                                 const float* grads, const float* grad_costs, void* dlogits, int N, int T,
+                                                 int U, int V, const int* blank_ids, int B) {
+    if (!mb_shape_ok(dtype, N, T, U, V, B) || !mb_ids_ok(blank_ids, B, V)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!logits || !grads || !dlogits || labels_missing(U, labels)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!aligned(logits, dtype_size(dtype)) || !aligned(dlogits, dtype_size(dtype)) || !aligned(grads, 4) ||
+        !aligned(grad_costs, 4) || !aligned(labels, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    if (launch_mb_logits_backward(stream, dtype, logits, labels, grads, grad_costs, dlogits, N, T, U, V,
+                                  mb_blanks(blank_ids, nullptr, B)) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
 }

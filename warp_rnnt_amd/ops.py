@@ -749,6 +749,68 @@ def tdt_logits_backward(logits, labels, grads, grad_costs, num_durations, blank=
     return out
 
 
+def _multiblank_check(V, blank_ids, blank_durations, sigma):
+    """The refusals of include/warp_rnnt_amd_multiblank.h that depend on values, with their reasons spelt out."""
+    ids, ds = [int(v) for v in blank_ids], [int(d) for d in blank_durations]
+    if not (1 <= len(ds) <= 8 and len(set(ds)) == len(ds) and all(1 <= d <= 8 for d in ds) and 1 in ds):
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the multi-blank loss needs blank durations "
+                           f"that are distinct integers in [1, 8] with 1 among them, the standard blank's "
+                           f"(durations={tuple(blank_durations)})")
+    if len(ids) != len(ds) or len(set(ids)) != len(ids):
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the multi-blank loss needs one distinct "
+                           f"blank id per duration (ids={tuple(blank_ids)}, durations={tuple(blank_durations)})")
+    if V < len(ids) + 1 or not all(0 <= v < V for v in ids):
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the multi-blank loss needs blank ids that "
+                           f"are vocabulary indices in [0, V) and V >= B + 1 (V={V}, ids={tuple(blank_ids)})")
+    if not 0.0 <= sigma < float("inf"):
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): the multi-blank loss needs a finite "
+                           f"sigma >= 0 (sigma={sigma})")
+    return ids, ds
+
+
+def multiblank_loss(logits, labels, xn, yn, blank_ids, blank_durations, sigma=0.0, fastemit_lambda=0.0, with_grads=True):
+    """The multi-blank transducer loss on the fused path (include/warp_rnnt_amd_multiblank.h): logits (N,T,U,V) fp32 /
+    bf16 / fp16, validated by the caller; blank_ids[i] consumes blank_durations[i] frames.  Returns costs (N,) fp32 and,
+    with_grads, the per-cell sums (1+B,N,T,U) fp32 -- G_l, G_blank as planes in the diagonal-major cell order -- what
+    :func:`multiblank_logits_backward` reads (else None: no beta sweep runs and no such plane is produced)."""
+    N, T, U, V = logits.shape
+    ids, ds = _multiblank_check(V, blank_ids, blank_durations, sigma)
+    L = _lib.load()
+    B = len(ids)
+    dev = logits.device
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        grads = torch.empty((1 + B, N, T, U), dtype=torch.float32, device=dev) if with_grads else None
+        if N == 0:
+            return costs, grads
+        ws = _workspace(dev, L.rnnt_amd_multiblank_workspace_size, "N T U B", N, T, U, B)
+        host_ids, host_durations = (ctypes.c_int * B)(*ids), (ctypes.c_int * B)(*ds)      # read during the call
+        _check(L.rnnt_amd_multiblank_loss_logits(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[logits.dtype],
+                                                 logits.data_ptr(), _ptr(labels), xn.data_ptr(), yn.data_ptr(), host_ids,
+                                                 host_durations, B, costs.data_ptr(), _ptr(grads), N, T, U, V,
+                                                 float(sigma), float(fastemit_lambda)))
+    return costs, grads
+
+
+def multiblank_logits_backward(logits, labels, grads, grad_costs, blank_ids):
+    """d(sum_n grad_costs[n]*cost[n]) / d(logits) of :func:`multiblank_loss`, in the logits' dtype (the fp32 result
+    rounded once); grads: the planes the forward returned; blank_ids: as the forward took them."""
+    L = _lib.load()
+    N, T, U, V = logits.shape
+    ids = [int(v) for v in blank_ids]
+    B = len(ids)
+    dev = logits.device
+    with torch.cuda.device(dev):
+        out = torch.empty_like(logits)
+        if N == 0:
+            return out
+        host_ids = (ctypes.c_int * B)(*ids)
+        _check(L.rnnt_amd_multiblank_logits_backward(_stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
+                                                     _ptr(labels), grads.data_ptr(), _ptr(grad_costs), out.data_ptr(), N,
+                                                     T, U, V, host_ids, B))
+    return out
+
+
 def tdt_joint_loss(f, g, weight, bias, labels, xn, yn, durations, activation="tanh", blank=0, sigma=0.0,
                    fastemit_lambda=0.0, with_grads=True, dropout=0.0, seed=None):
     """The joint network fused into the TDT loss (include/warp_rnnt_amd_tdt_joint.h): f (N,T,H), g (N,U,H), weight
