@@ -21,6 +21,7 @@ HEADERS = ["api_common.h", "common.h", "kernels.h", "lattice_plan.h", "lattice_l
            "lattice_single.h", "grads_cell.h", "streaming.h", "lsm_plan.h", "lsm.h", "philox.h", "hat.h", "align.h", "row_chunks.h", "tdt.h", "tdt_align.h",
            "joint_tile.h", "tdt_joint.h", "pruned.h", "simple.h", "multiblank.h",
            os.path.join("..", "..", "include", "warp_rnnt_amd_multiblank.h"),
+           os.path.join("..", "..", "include", "warp_rnnt_amd_topology.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_pruned.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_simple.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd.h"), os.path.join("..", "..", "include", "warp_rnnt_amd_clamp.h"),

@@ -185,6 +185,22 @@ MULTIBLANK_SYMBOLS = {
 # behind ADDITIVE_SIMPLE, under the same contract (tests/test_host_multiblank.py holds this one to it); a tuple of its own
 # for the same reason
 ADDITIVE_MULTIBLANK = ((MULTIBLANK_SYMBOLS, "warp_rnnt_amd_multiblank.h"),)
+# every symbol include/warp_rnnt_amd_topology.h declares (k2's modified topology and delay penalty for the pruned and the
+# simple loss; additive: it did not move the version): the sizes are functions of (topology, N, T, U); each entry has the
+# argument list of its namesake without the suffix with `topology` behind it, the forwards `delay_penalty` behind that, and
+# the pruned backward takes xn, yn behind `starts`
+TOPOLOGY_REGULAR, TOPOLOGY_MODIFIED = 0, 1
+TOPOLOGY_SYMBOLS = {
+    "rnnt_amd_pruned_topology_workspace_size": (_sz, [_i, _i, _i, _i]),
+    "rnnt_amd_simple_topology_workspace_size": (_sz, [_i, _i, _i, _i]),
+    "rnnt_amd_pruned_loss_logits_topology": (_i, PRUNED_SYMBOLS["rnnt_amd_pruned_loss_logits"][1] + [_i, _f]),
+    "rnnt_amd_pruned_logits_backward_topology": (_i, [_vp, _i] + [_vp] * 8 + [_i] * 6 + [_i]),
+    "rnnt_amd_simple_loss_topology": (_i, SIMPLE_SYMBOLS["rnnt_amd_simple_loss"][1] + [_i, _f]),
+    "rnnt_amd_simple_backward_topology": (_i, SIMPLE_SYMBOLS["rnnt_amd_simple_backward"][1] + [_i]),
+}
+# behind ADDITIVE_MULTIBLANK, under the same contract (tests/test_host_modified.py holds this one to it); a tuple of its own
+# for the same reason
+ADDITIVE_TOPOLOGY = ((TOPOLOGY_SYMBOLS, "warp_rnnt_amd_topology.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -223,7 +239,7 @@ def load():
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
     for table, header in (ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED + ADDITIVE_SIMPLE +
-                          ADDITIVE_MULTIBLANK):
+                          ADDITIVE_MULTIBLANK + ADDITIVE_TOPOLOGY):
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

@@ -2,7 +2,8 @@
 // own behind one of the loss's producers.  The joint network (include/warp_rnnt_amd.h) and its dropout
 // (include/warp_rnnt_amd_joint_dropout.h), the factorised-blank loss (include/warp_rnnt_amd_hat.h), the pruned loss over a
 // band of the lattice (include/warp_rnnt_amd_pruned.h), the smoothed first pass of its recipe over the trivial joiner
-// (include/warp_rnnt_amd_simple.h), best-path alignments
+// (include/warp_rnnt_amd_simple.h), the modified topology and the delay penalty of the two
+// (include/warp_rnnt_amd_topology.h), best-path alignments
 // (include/warp_rnnt_amd_align.h), the token-and-duration loss (include/warp_rnnt_amd_tdt.h: producer, sweeps and
 // gradient kernel all its own), its best-path alignments (include/warp_rnnt_amd_tdt_align.h) and the joint network fused
 // into it (include/warp_rnnt_amd_tdt_joint.h), the multi-blank loss (include/warp_rnnt_amd_multiblank.h: producer, sweeps
@@ -16,6 +17,7 @@
 #include "../../include/warp_rnnt_amd_tdt.h"
 #include "../../include/warp_rnnt_amd_tdt_align.h"
 #include "../../include/warp_rnnt_amd_tdt_joint.h"
+#include "../../include/warp_rnnt_amd_topology.h"
 
 #include "align.h"
 #include "api_common.h"
@@ -129,6 +131,44 @@ inline bool simple_shape_ok(int dtype, int N, int T, int U, int V, int blank) {
 inline bool simple_scales_ok(float lm_only_scale, float am_only_scale, const float* q) {
     return lm_only_scale >= 0.0f && am_only_scale >= 0.0f && lm_only_scale + am_only_scale <= 1.0f &&
            (am_only_scale == 0.0f || q);
+}
+
+// The topology and the delay penalty of the pruned and the simple entries (include/warp_rnnt_amd_topology.h).  The modified
+// lattice is the regular one over the sheared cells (t - u, u): its plane has T + 1 rows and is frame-major, and the sweeps
+// take T_n - U_n + 1 for the frames of utterance n -- N ints behind the loss layout (pruned.h: launch_modified_terminal).
+inline bool topology_ok(int topology, float delay_penalty) {
+    return (topology == RNNT_TOPOLOGY_REGULAR || topology == RNNT_TOPOLOGY_MODIFIED) && delay_penalty >= 0.0f &&
+           delay_penalty <= 3.402823466e+38f;                                                     // (false for a NaN)
+}
+// the rows of the lattice's planes
+inline int plane_frames(int topology, int T) { return topology == RNNT_TOPOLOGY_MODIFIED ? T + 1 : T; }
+inline bool topology_dims_ok(int topology, int N, int T, int U) {
+    return dims_ok(N, T, U) && (topology != RNNT_TOPOLOGY_MODIFIED || dims_ok(N, T + 1, U));
+}
+struct TopologyWorkspace {
+    Workspace w;
+    int* xs;         // modified: the sheared lattice's frame counts; regular: nullptr
+};
+TopologyWorkspace topology_layout(Carver& c, int topology, int N, int T, int U) {
+    TopologyWorkspace tw;
+    tw.w = loss_layout(c, N, plane_frames(topology, T), U);
+    tw.xs = topology == RNNT_TOPOLOGY_MODIFIED ? c.take<int>((size_t)N) : nullptr;
+    return tw;
+}
+// Steps 2 and 3 of a loss call on a plane a producer of either topology filled.  clear_terminal: the pairs go to a reader
+// that walks them by frames and masks nothing (pruned.h: launch_modified_clear_terminal).
+rnntStatus_t topology_sweeps(rnntStream_t stream, const TopologyWorkspace& tw, int topology, const int* xn, const int* yn,
+                             float* costs, float* gout, int writer, bool clear_terminal, int N, int T, int U,
+                             float fastemit_lambda) {
+    if (topology != RNNT_TOPOLOGY_MODIFIED)
+        return sweeps_and_pair_grads(stream, tw.w, xn, yn, costs, gout, writer, N, T, U, nullptr, fastemit_lambda);
+    if (launch_modified_terminal(stream, xn, yn, tw.xs, tw.w.ws2, N, T, U) != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
+    const rnntStatus_t st = sweeps_and_pair_grads(stream, tw.w, tw.xs, yn, costs, gout, WRITE_SKEWED2, N, T + 1, U, nullptr,
+                                                  fastemit_lambda);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (clear_terminal && launch_modified_clear_terminal(stream, xn, yn, gout, N, T, U) != hipSuccess)
+        return RNNT_STATUS_GRADS_BLANK_FAILED;
+    return RNNT_STATUS_SUCCESS;
 }
 
 // Best-path alignments.  Behind the loss layout: the decision words, then the columns parked between column stripes.
@@ -319,53 +359,92 @@ rnntStatus_t rnnt_amd_hat_logits_backward(rnntStream_t stream, int dtype, const 
 // include/warp_rnnt_amd_pruned.h: the pruned transducer loss.  The HAT entry's shape: a producer of its own (pruned.hip)
 // fills the pair plane -- the floor everywhere, the band's pairs over it -- the sweeps and the gradient pairs are the
 // standard ones over the (N,T,U) grid; the backward is one streaming launch over the (N,T,S,V) logits.
-rnntStatus_t rnnt_amd_pruned_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits,
-                                         const int* labels, const int* starts, const int* xn, const int* yn, float* costs,
-                                         float* grads, int N, int T, int U, int S, int V, int blank,
-                                         float fastemit_lambda) {
-    if (!dtype_ok(dtype) || !dims_ok(N, T, U) || V < 2 || !vocab_ok(V, blank) || !pruned_band_ok(N, T, U, S))
+// include/warp_rnnt_amd_topology.h: the same with a topology and a delay penalty.  RNNT_TOPOLOGY_REGULAR with
+// delay_penalty == 0 IS the entry without them.
+rnntStatus_t rnnt_amd_pruned_loss_logits_topology(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                                  const int* labels, const int* starts, const int* xn, const int* yn,
+                                                  float* costs, float* grads, int N, int T, int U, int S, int V, int blank,
+                                                  float fastemit_lambda, int topology, float delay_penalty) {
+    if (!topology_ok(topology, delay_penalty) || !dtype_ok(dtype) || !topology_dims_ok(topology, N, T, U) || V < 2 ||
+        !vocab_ok(V, blank) || !pruned_band_ok(N, T, U, S))
         return RNNT_STATUS_INVALID_ARGUMENT;
     if (!workspace_ok(workspace) || !logits || !starts || !xn || !yn || !costs || labels_missing(U, labels))
         return RNNT_STATUS_INVALID_ARGUMENT;
     if (N == 0) return RNNT_STATUS_SUCCESS;
     Carver c(workspace);
-    const Workspace w = loss_layout(c, N, T, U);
-    if (launch_pruned_pairs(stream, dtype, logits, labels, starts, w.ws2, N, T, U, S, V, blank) != hipSuccess)
+    const TopologyWorkspace tw = topology_layout(c, topology, N, T, U);
+    if (launch_pruned_pairs(stream, dtype, logits, labels, starts, xn, yn, tw.w.ws2, N, T, U, S, V, blank, topology,
+                            delay_penalty) != hipSuccess)
         return RNNT_STATUS_PROLOGUE_FAILED;
-    return sweeps_and_pair_grads(stream, w, xn, yn, costs, grads ? grads : w.ws2, WRITE_SKEWED2, N, T, U, nullptr,
-                                 fastemit_lambda);
+    return topology_sweeps(stream, tw, topology, xn, yn, costs, grads ? grads : tw.w.ws2, WRITE_SKEWED2, false, N, T, U,
+                           fastemit_lambda);
+}
+
+rnntStatus_t rnnt_amd_pruned_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                         const int* labels, const int* starts, const int* xn, const int* yn, float* costs,
+                                         float* grads, int N, int T, int U, int S, int V, int blank,
+                                         float fastemit_lambda) {
+    return rnnt_amd_pruned_loss_logits_topology(stream, workspace, dtype, logits, labels, starts, xn, yn, costs, grads, N, T,
+                                                U, S, V, blank, fastemit_lambda, RNNT_TOPOLOGY_REGULAR, 0.0f);
+}
+
+rnntStatus_t rnnt_amd_pruned_logits_backward_topology(rnntStream_t stream, int dtype, const void* logits,
+                                                      const int* labels, const int* starts, const int* xn, const int* yn,
+                                                      const float* grads_diagonal, const float* grad_costs, void* dlogits,
+                                                      int N, int T, int U, int S, int V, int blank, int topology) {
+    if (!topology_ok(topology, 0.0f) || !dtype_ok(dtype) || !topology_dims_ok(topology, N, T, U) || V < 2 ||
+        !vocab_ok(V, blank) || !pruned_band_ok(N, T, U, S))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!logits || !starts || !grads_diagonal || !aligned(grads_diagonal, 8) || !dlogits || labels_missing(U, labels) ||
+        (topology == RNNT_TOPOLOGY_MODIFIED && (!xn || !yn)))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    if (launch_pruned_logits_backward(stream, dtype, logits, labels, starts, xn, yn, grads_diagonal, grad_costs, dlogits, N,
+                                      T, U, S, V, blank, topology) != hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
 }
 
 rnntStatus_t rnnt_amd_pruned_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* labels,
                                              const int* starts, const float* grads_diagonal, const float* grad_costs,
                                              void* dlogits, int N, int T, int U, int S, int V, int blank) {
-    if (!dtype_ok(dtype) || !dims_ok(N, T, U) || V < 2 || !vocab_ok(V, blank) || !pruned_band_ok(N, T, U, S))
-        return RNNT_STATUS_INVALID_ARGUMENT;
-    if (!logits || !starts || !grads_diagonal || !aligned(grads_diagonal, 8) || !dlogits || labels_missing(U, labels))
-        return RNNT_STATUS_INVALID_ARGUMENT;
-    if (N == 0) return RNNT_STATUS_SUCCESS;
-    if (launch_pruned_logits_backward(stream, dtype, logits, labels, starts, grads_diagonal, grad_costs, dlogits, N, T, U,
-                                      S, V, blank) != hipSuccess)
-        return RNNT_STATUS_EXPAND_FAILED;
-    return RNNT_STATUS_SUCCESS;
+    return rnnt_amd_pruned_logits_backward_topology(stream, dtype, logits, labels, starts, nullptr, nullptr, grads_diagonal,
+                                                    grad_costs, dlogits, N, T, U, S, V, blank, RNNT_TOPOLOGY_REGULAR);
+}
+
+size_t rnnt_amd_pruned_topology_workspace_size(int topology, int N, int T, int U) {
+    if (!topology_ok(topology, 0.0f) || !topology_dims_ok(topology, N, T, U)) return 0;
+    Carver c(nullptr);
+    topology_layout(c, topology, N, T, U);
+    return c.off;
 }
 
 // include/warp_rnnt_amd_simple.h: the smoothed first pass of the pruned recipe.  The HAT entry's shape with a GEMM in the
 // producer (simple.hip): it fills the pair plane and the normaliser plane, the sweeps and the gradient pairs are the
 // standard ones, the pairs written row-major for the caller; the backward is the statistics, the row sums and two GEMMs.
-size_t rnnt_amd_simple_workspace_size(int N, int T, int U) {
-    if (!dims_ok(N, T, U) || T > SIMPLE_MAX_ROWS || U > SIMPLE_MAX_ROWS) return 0;
+// include/warp_rnnt_amd_topology.h: the same with a topology and a delay penalty; RNNT_TOPOLOGY_REGULAR with
+// delay_penalty == 0 IS the entry without them.  The modified pairs stay frame-major, (N,T+1,U,2), as the gradient kernel
+// writes them in place of the row-major turn, and the backward reads them with a row pitch of T + 1: no copy.
+size_t rnnt_amd_simple_topology_workspace_size(int topology, int N, int T, int U) {
+    if (!topology_ok(topology, 0.0f) || !topology_dims_ok(topology, N, T, U) || T > SIMPLE_MAX_ROWS || U > SIMPLE_MAX_ROWS)
+        return 0;
     Carver c(nullptr);
-    loss_layout(c, N, T, U);
+    topology_layout(c, topology, N, T, U);
     simple_layout(c, N, T, U);
     return c.off;
 }
 
-rnntStatus_t rnnt_amd_simple_loss(rnntStream_t stream, void* workspace, int dtype, const void* am, const void* lm,
-                                  const float* q, const int* labels, const int* xn, const int* yn, float* costs,
-                                  float* pair_grads, float* znorm, int N, int T, int U, int V, int blank,
-                                  float lm_only_scale, float am_only_scale, float fastemit_lambda) {
-    if (!simple_shape_ok(dtype, N, T, U, V, blank) || !simple_scales_ok(lm_only_scale, am_only_scale, q))
+size_t rnnt_amd_simple_workspace_size(int N, int T, int U) {
+    return rnnt_amd_simple_topology_workspace_size(RNNT_TOPOLOGY_REGULAR, N, T, U);
+}
+
+rnntStatus_t rnnt_amd_simple_loss_topology(rnntStream_t stream, void* workspace, int dtype, const void* am, const void* lm,
+                                           const float* q, const int* labels, const int* xn, const int* yn, float* costs,
+                                           float* pair_grads, float* znorm, int N, int T, int U, int V, int blank,
+                                           float lm_only_scale, float am_only_scale, float fastemit_lambda, int topology,
+                                           float delay_penalty) {
+    if (!topology_ok(topology, delay_penalty) || !topology_dims_ok(topology, N, T, U) ||
+        !simple_shape_ok(dtype, N, T, U, V, blank) || !simple_scales_ok(lm_only_scale, am_only_scale, q))
         return RNNT_STATUS_INVALID_ARGUMENT;
     if (!workspace_ok(workspace) || !am || !lm || !xn || !yn || !costs || labels_missing(U, labels) ||
         (pair_grads && !znorm))
@@ -375,21 +454,33 @@ rnntStatus_t rnnt_amd_simple_loss(rnntStream_t stream, void* workspace, int dtyp
         return RNNT_STATUS_INVALID_ARGUMENT;
     if (N == 0) return RNNT_STATUS_SUCCESS;
     Carver c(workspace);
-    const Workspace w = loss_layout(c, N, T, U);
+    const TopologyWorkspace tw = topology_layout(c, topology, N, T, U);
     const SimpleStats st = simple_layout(c, N, T, U);
-    if (launch_simple_pairs(stream, dtype, am, lm, am_only_scale != 0.0f ? q : nullptr, labels, st, w.ws2, znorm, N, T, U,
-                            V, blank, simple_scales(lm_only_scale, am_only_scale)) != hipSuccess)
+    if (launch_simple_pairs(stream, dtype, am, lm, am_only_scale != 0.0f ? q : nullptr, labels, xn, yn, st, tw.w.ws2, znorm,
+                            N, T, U, V, blank, simple_scales(lm_only_scale, am_only_scale), topology,
+                            delay_penalty) != hipSuccess)
         return RNNT_STATUS_PROLOGUE_FAILED;
-    return sweeps_and_pair_grads(stream, w, xn, yn, costs, pair_grads ? pair_grads : w.ws2,
-                                 pair_grads ? WRITE_ROWMAJOR2 : WRITE_SKEWED2, N, T, U, nullptr, fastemit_lambda);
+    return topology_sweeps(stream, tw, topology, xn, yn, costs, pair_grads ? pair_grads : tw.w.ws2,
+                           pair_grads ? WRITE_ROWMAJOR2 : WRITE_SKEWED2, pair_grads != nullptr, N, T, U, fastemit_lambda);
 }
 
-rnntStatus_t rnnt_amd_simple_backward(rnntStream_t stream, void* workspace, int dtype, const void* am, const void* lm,
-                                      const float* q, const int* labels, const int* xn, const int* yn,
-                                      const float* pair_grads, const float* znorm, const float* grad_costs, void* dam,
-                                      void* dlm, float* dq_partials, int N, int T, int U, int V, int blank,
-                                      float lm_only_scale, float am_only_scale) {
-    if (!simple_shape_ok(dtype, N, T, U, V, blank) || !simple_scales_ok(lm_only_scale, am_only_scale, q))
+rnntStatus_t rnnt_amd_simple_loss(rnntStream_t stream, void* workspace, int dtype, const void* am, const void* lm,
+                                  const float* q, const int* labels, const int* xn, const int* yn, float* costs,
+                                  float* pair_grads, float* znorm, int N, int T, int U, int V, int blank,
+                                  float lm_only_scale, float am_only_scale, float fastemit_lambda) {
+    return rnnt_amd_simple_loss_topology(stream, workspace, dtype, am, lm, q, labels, xn, yn, costs, pair_grads, znorm, N, T,
+                                         U, V, blank, lm_only_scale, am_only_scale, fastemit_lambda, RNNT_TOPOLOGY_REGULAR,
+                                         0.0f);
+}
+
+rnntStatus_t rnnt_amd_simple_backward_topology(rnntStream_t stream, void* workspace, int dtype, const void* am,
+                                               const void* lm, const float* q, const int* labels, const int* xn,
+                                               const int* yn, const float* pair_grads, const float* znorm,
+                                               const float* grad_costs, void* dam, void* dlm, float* dq_partials, int N,
+                                               int T, int U, int V, int blank, float lm_only_scale, float am_only_scale,
+                                               int topology) {
+    if (!topology_ok(topology, 0.0f) || !topology_dims_ok(topology, N, T, U) ||
+        !simple_shape_ok(dtype, N, T, U, V, blank) || !simple_scales_ok(lm_only_scale, am_only_scale, q))
         return RNNT_STATUS_INVALID_ARGUMENT;
     if (!workspace_ok(workspace) || !am || !lm || !xn || !yn || !pair_grads || !znorm || !dam || !dlm ||
         labels_missing(U, labels))
@@ -400,13 +491,23 @@ rnntStatus_t rnnt_amd_simple_backward(rnntStream_t stream, void* workspace, int 
         return RNNT_STATUS_INVALID_ARGUMENT;
     if (N == 0) return RNNT_STATUS_SUCCESS;
     Carver c(workspace);
-    loss_layout(c, N, T, U);
+    topology_layout(c, topology, N, T, U);
     const SimpleStats st = simple_layout(c, N, T, U);
     if (launch_simple_backward(stream, dtype, am, lm, am_only_scale != 0.0f ? q : nullptr, labels, xn, yn, pair_grads,
                                znorm, grad_costs, st, dam, dlm, dq_partials, N, T, U, V, blank,
-                               simple_scales(lm_only_scale, am_only_scale)) != hipSuccess)
+                               simple_scales(lm_only_scale, am_only_scale), plane_frames(topology, T)) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_simple_backward(rnntStream_t stream, void* workspace, int dtype, const void* am, const void* lm,
+                                      const float* q, const int* labels, const int* xn, const int* yn,
+                                      const float* pair_grads, const float* znorm, const float* grad_costs, void* dam,
+                                      void* dlm, float* dq_partials, int N, int T, int U, int V, int blank,
+                                      float lm_only_scale, float am_only_scale) {
+    return rnnt_amd_simple_backward_topology(stream, workspace, dtype, am, lm, q, labels, xn, yn, pair_grads, znorm,
+                                             grad_costs, dam, dlm, dq_partials, N, T, U, V, blank, lm_only_scale,
+                                             am_only_scale, RNNT_TOPOLOGY_REGULAR);
 }
 
 // include/warp_rnnt_amd_align.h: best-path alignments.  A producer of the loss fills the pair plane -- and leaves it

@@ -25,14 +25,21 @@ namespace {
 
 // Where row `row` of (N,T,S) lies in the lattice.  live: u in [0,U) -- starts is device data nobody validated, and the sum
 // is formed in 64 bits so that no start wraps into the grid
+//
+// TOPO_MODIFIED (pruned.h): the plane has T + 1 rows per utterance and is frame-major, cell (t,u) at ((n (T+1) + t) U + u) --
+// the diagonal-major address of cell (t' = t - u, u) of the sheared lattice.  live: also t < xn[n], t >= u, u <= yn[n], the
+// cells a path can reach -- row (t = T_n, u = U_n) of a padding frame has the address of the virtual terminal cell.
 struct BandCell {
     size_t sk;      // float2 index into the diagonal-major plane
     int label;      // vocabulary index of the label channel (the blank in the last column and for a label outside [0,V))
     int n;
+    int t;
     bool live;
 };
+template <int TOPO>
 __device__ __forceinline__ BandCell band_cell(size_t row, const int* __restrict__ labels, const int* __restrict__ starts,
-                                              int T, int U, int S, int V, int blank) {
+                                              const int* __restrict__ xn, const int* __restrict__ yn, int T, int U, int S,
+                                              int V, int blank) {
     // N*T*S < 2^32 is checked by the C ABI, so 32-bit divisions are enough
     const unsigned r32 = (unsigned)row;
     const unsigned frame = r32 / (unsigned)S;          // n*T + t
@@ -42,44 +49,54 @@ __device__ __forceinline__ BandCell band_cell(size_t row, const int* __restrict_
     const long long u64 = (long long)starts[frame] + s;
     BandCell c;
     c.n = (int)n;
+    c.t = t;
     c.live = u64 >= 0 && u64 < (long long)U;
     c.sk = 0;
     c.label = blank;
+    if constexpr (TOPO == TOPO_MODIFIED) c.live = c.live && t < xn[n] && (long long)t >= u64 && u64 <= (long long)yn[n];
     if (c.live) {
         const int u = (int)u64;
-        int r = t + u;
-        r = r >= T ? r % T : r;
-        c.sk = ((size_t)n * T + r) * (size_t)U + u;
+        if constexpr (TOPO == TOPO_MODIFIED) {
+            c.sk = ((size_t)n * (T + 1) + t) * (size_t)U + u;
+        } else {
+            int r = t + u;
+            r = r >= T ? r % T : r;
+            c.sk = ((size_t)n * T + r) * (size_t)U + u;
+        }
         if (u < U - 1) c.label = safe_label(labels[(size_t)n * (U - 1) + u], V, blank);
     }
     return c;
 }
 
-template <typename E, int G, int ACC>
+// PEN: the label channel of frame t gets dp (0.5 (T_n - 1) - t) added, fp32: the bracket, one multiply, one add
+template <typename E, int G, int ACC, int TOPO, bool PEN>
 __global__ void __launch_bounds__(ROW_THREADS)
 k_pruned_pairs(const E* __restrict__ x, const int* __restrict__ labels, const int* __restrict__ starts,
-               float2* __restrict__ ws2, size_t rows, int T, int U, int S, int V, int blank) {
+               const int* __restrict__ xn, const int* __restrict__ yn, float2* __restrict__ ws2, size_t rows, int T, int U,
+               int S, int V, int blank, float dp) {
     const size_t row = (size_t)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
     if (row >= rows) return;
     const int lane = threadIdx.x % G;
-    const BandCell c = band_cell(row, labels, starts, T, U, S, V, blank);
+    const BandCell c = band_cell<TOPO>(row, labels, starts, xn, yn, T, U, S, V, blank);
     if (!c.live) return;                               // (the whole group: no lane of it is asked for a shuffle below)
     const E* xr = x + row * (size_t)V;
     const float zb = (float)xr[blank], zl = (float)xr[c.label];
     float m, ls;
     row_stats<E, G, ACC, true>(xr, lane, V, V, [](int) { return false; }, m, ls);
-    if (lane == 0) ws2[c.sk] = make_float2((zb - m) - ls, (zl - m) - ls);
+    float lpl = (zl - m) - ls;
+    if constexpr (PEN) lpl = lpl + dp * (0.5f * (float)(xn[c.n] - 1) - (float)c.t);
+    if (lane == 0) ws2[c.sk] = make_float2((zb - m) - ls, lpl);
 }
 
-template <typename E, int G, int ACC>
+template <typename E, int G, int ACC, int TOPO>
 __global__ void __launch_bounds__(ROW_THREADS)
 k_pruned_backward(const E* __restrict__ x, const int* __restrict__ labels, const int* __restrict__ starts,
-                  const float2* __restrict__ g2, const float* __restrict__ scale, E* __restrict__ out, size_t rows, int T,
-                  int U, int S, int V, int blank) {
+                  const int* __restrict__ xn, const int* __restrict__ yn, const float2* __restrict__ g2,
+                  const float* __restrict__ scale, E* __restrict__ out, size_t rows, int T, int U, int S, int V, int blank) {
     const size_t row = (size_t)blockIdx.x * (ROW_THREADS / G) + threadIdx.x / G;
     if (row >= rows) return;
     const int lane = threadIdx.x % G;
-    const BandCell c = band_cell(row, labels, starts, T, U, S, V, blank);
+    const BandCell c = band_cell<TOPO>(row, labels, starts, xn, yn, T, U, S, V, blank);
     const float sc = scale ? scale[c.n] : 1.0f;
     E* o = out + row * (size_t)V;
     // an utterance that is switched off is not looked at: its pairs may hold anything (a band without a path)
@@ -119,27 +136,69 @@ __global__ void __launch_bounds__(ROW_THREADS) k_pruned_floor(float2* __restrict
         ws2[cells - 1] = make_float2(PRUNED_FLOOR, PRUNED_FLOOR);
 }
 
-template <typename E>
-hipError_t pruned_pairs(hipStream_t stream, const E* x, const int* labels, const int* starts, float* ws2, int N, int T,
-                        int U, int S, int V, int blank) {
-    const size_t rows = (size_t)N * T * S, cells = (size_t)N * T * U;
-    if (rows == 0) return hipSuccess;
-    float2* out = reinterpret_cast<float2*>(ws2);
+// The modified plane's per-utterance words, a thread per utterance, behind the floor and the producer and in front of the
+// sweeps (a kernel, not copies and memsets, for k_pruned_floor's reason): the sheared lattice's frame count
+// xs[n] = T_n - U_n + 1 and its virtual terminal cell (t' = T_n - U_n, u = U_n), row T_n of the plane, whose blank is 0 -- the
+// modified lattice has no terminal blank.  T_n < U_n holds no path: one frame, the terminal cell left at the floor, and
+// the cost comes back >= 1e29.  Lengths the regular entries refuse (utt_lens) stay refused: xs[n] = 0.
+__global__ void __launch_bounds__(ROW_THREADS)
+k_modified_terminal(const int* __restrict__ xn, const int* __restrict__ yn, int* __restrict__ xs, float2* __restrict__ ws2,
+                    int N, int T, int U) {
+    const int n = blockIdx.x * ROW_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const int x = xn[n], y = yn[n];
+    const bool ok = x >= 1 && x <= T && y >= 0 && y < U;
+    xs[n] = !ok ? 0 : x < y ? 1 : x - y + 1;
+    if (ok && x >= y) ws2[((size_t)n * (T + 1) + x) * (size_t)U + y] = make_float2(0.0f, PRUNED_FLOOR);
+}
+
+// ... and behind the gradient kernel, for a reader that walks the plane by frames without the lengths: the terminal
+// cell's gradient pair, (-1, 0) in row T_n, is no frame's
+__global__ void __launch_bounds__(ROW_THREADS)
+k_modified_clear_terminal(const int* __restrict__ xn, const int* __restrict__ yn, float2* __restrict__ g2, int N, int T,
+                          int U) {
+    const int n = blockIdx.x * ROW_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const int x = xn[n], y = yn[n];
+    if (x >= 1 && x <= T && y >= 0 && y < U && x >= y) g2[((size_t)n * (T + 1) + x) * (size_t)U + y] = make_float2(0.0f, 0.0f);
+}
+
+hipError_t pruned_floor(hipStream_t stream, float2* out, size_t cells) {
     // cells < 2^32 (the C ABI's dims_ok): at most 2^23 workgroups, one lane more than pairs for the odd cell
     k_pruned_floor<<<(unsigned)((cells / 2 + 1 + ROW_THREADS - 1) / ROW_THREADS), ROW_THREADS, 0, stream>>>(out, cells);
-    const hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+template <typename E>
+hipError_t pruned_pairs(hipStream_t stream, const E* x, const int* labels, const int* starts, const int* xn, const int* yn,
+                        float* ws2, int N, int T, int U, int S, int V, int blank, int topology, float dp) {
+    const bool modified = topology == TOPO_MODIFIED;
+    const size_t rows = (size_t)N * T * S, cells = (size_t)N * (modified ? T + 1 : T) * U;
+    if (rows == 0) return hipSuccess;
+    float2* out = reinterpret_cast<float2*>(ws2);
+    const hipError_t e = pruned_floor(stream, out, cells);
     if (e != hipSuccess) return e;
     const int G = row_group(V);
     const unsigned grid = row_grid(rows, G);
     return row_dispatch<E>(G, row_access<E>(V, x, nullptr), [&](auto g, auto acc) {
         constexpr int GG = decltype(g)::value, ACC = decltype(acc)::value;
-        k_pruned_pairs<E, GG, ACC><<<grid, ROW_THREADS, 0, stream>>>(x, labels, starts, out, rows, T, U, S, V, blank);
+        // (regular with dp == 0: the kernel as it was, no length is read)
+        if (modified)
+            k_pruned_pairs<E, GG, ACC, TOPO_MODIFIED, true><<<grid, ROW_THREADS, 0, stream>>>(x, labels, starts, xn, yn, out,
+                                                                                             rows, T, U, S, V, blank, dp);
+        else if (dp != 0.0f)
+            k_pruned_pairs<E, GG, ACC, TOPO_REGULAR, true><<<grid, ROW_THREADS, 0, stream>>>(x, labels, starts, xn, yn, out,
+                                                                                            rows, T, U, S, V, blank, dp);
+        else
+            k_pruned_pairs<E, GG, ACC, TOPO_REGULAR, false><<<grid, ROW_THREADS, 0, stream>>>(x, labels, starts, xn, yn, out,
+                                                                                             rows, T, U, S, V, blank, dp);
     });
 }
 
 template <typename E>
-hipError_t pruned_backward(hipStream_t stream, const E* x, const int* labels, const int* starts, const float* g2_diagonal,
-                           const float* scale, E* dx, int N, int T, int U, int S, int V, int blank) {
+hipError_t pruned_backward(hipStream_t stream, const E* x, const int* labels, const int* starts, const int* xn,
+                           const int* yn, const float* g2_diagonal, const float* scale, E* dx, int N, int T, int U, int S,
+                           int V, int blank, int topology) {
     const size_t rows = (size_t)N * T * S;
     if (rows == 0) return hipSuccess;
     const int G = row_group(V);
@@ -147,8 +206,12 @@ hipError_t pruned_backward(hipStream_t stream, const E* x, const int* labels, co
     const float2* g2 = reinterpret_cast<const float2*>(g2_diagonal);
     return row_dispatch<E>(G, row_access<E>(V, x, dx), [&](auto g, auto acc) {
         constexpr int GG = decltype(g)::value, ACC = decltype(acc)::value;
-        k_pruned_backward<E, GG, ACC><<<grid, ROW_THREADS, 0, stream>>>(x, labels, starts, g2, scale, dx, rows, T, U, S, V,
-                                                                       blank);
+        if (topology == TOPO_MODIFIED)
+            k_pruned_backward<E, GG, ACC, TOPO_MODIFIED><<<grid, ROW_THREADS, 0, stream>>>(x, labels, starts, xn, yn, g2, scale,
+                                                                                          dx, rows, T, U, S, V, blank);
+        else
+            k_pruned_backward<E, GG, ACC, TOPO_REGULAR><<<grid, ROW_THREADS, 0, stream>>>(x, labels, starts, xn, yn, g2, scale,
+                                                                                         dx, rows, T, U, S, V, blank);
     });
 }
 
@@ -159,19 +222,46 @@ inline bool pruned_shape_ok(int N, int T, int U, int S, int V, int blank) {
 
 }  // namespace
 
+inline bool topology_ok(int topology, const int* xn, const int* yn) {
+    return topology == TOPO_REGULAR || (topology == TOPO_MODIFIED && xn && yn);
+}
+
 hipError_t launch_pruned_pairs(hipStream_t stream, int dtype, const void* logits, const int* labels, const int* starts,
-                               float* ws2, int N, int T, int U, int S, int V, int blank) {
-    if (!pruned_shape_ok(N, T, U, S, V, blank)) return hipErrorInvalidValue;
-    return row_typed(dtype, logits, nullptr,
-                     [&](auto* x, auto*) { return pruned_pairs(stream, x, labels, starts, ws2, N, T, U, S, V, blank); });
+                               const int* xn, const int* yn, float* ws2, int N, int T, int U, int S, int V, int blank,
+                               int topology, float delay_penalty) {
+    if (!pruned_shape_ok(N, T, U, S, V, blank) || !topology_ok(topology, xn, yn) || (delay_penalty != 0.0f && !xn))
+        return hipErrorInvalidValue;
+    return row_typed(dtype, logits, nullptr, [&](auto* x, auto*) {
+        return pruned_pairs(stream, x, labels, starts, xn, yn, ws2, N, T, U, S, V, blank, topology, delay_penalty);
+    });
+}
+
+hipError_t launch_pruned_floor(hipStream_t stream, float* ws2, size_t cells) {
+    return cells ? pruned_floor(stream, reinterpret_cast<float2*>(ws2), cells) : hipSuccess;
+}
+
+hipError_t launch_modified_terminal(hipStream_t stream, const int* xn, const int* yn, int* xs, float* ws2, int N, int T,
+                                    int U) {
+    if (N <= 0) return hipSuccess;
+    k_modified_terminal<<<(unsigned)((N + ROW_THREADS - 1) / ROW_THREADS), ROW_THREADS, 0, stream>>>(
+        xn, yn, xs, reinterpret_cast<float2*>(ws2), N, T, U);
+    return hipGetLastError();
+}
+
+hipError_t launch_modified_clear_terminal(hipStream_t stream, const int* xn, const int* yn, float* g2, int N, int T, int U) {
+    if (N <= 0) return hipSuccess;
+    k_modified_clear_terminal<<<(unsigned)((N + ROW_THREADS - 1) / ROW_THREADS), ROW_THREADS, 0, stream>>>(
+        xn, yn, reinterpret_cast<float2*>(g2), N, T, U);
+    return hipGetLastError();
 }
 
 hipError_t launch_pruned_logits_backward(hipStream_t stream, int dtype, const void* logits, const int* labels,
-                                         const int* starts, const float* g2_diagonal, const float* scale, void* dlogits,
-                                         int N, int T, int U, int S, int V, int blank) {
-    if (!pruned_shape_ok(N, T, U, S, V, blank)) return hipErrorInvalidValue;
+                                         const int* starts, const int* xn, const int* yn, const float* g2_diagonal,
+                                         const float* scale, void* dlogits, int N, int T, int U, int S, int V, int blank,
+                                         int topology) {
+    if (!pruned_shape_ok(N, T, U, S, V, blank) || !topology_ok(topology, xn, yn)) return hipErrorInvalidValue;
     return row_typed(dtype, logits, dlogits, [&](auto* x, auto* dx) {
-        return pruned_backward(stream, x, labels, starts, g2_diagonal, scale, dx, N, T, U, S, V, blank);
+        return pruned_backward(stream, x, labels, starts, xn, yn, g2_diagonal, scale, dx, N, T, U, S, V, blank, topology);
     });
 }
 

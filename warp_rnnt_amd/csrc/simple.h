@@ -37,18 +37,25 @@ inline SimpleScales simple_scales(float lm_only_scale, float am_only_scale) {
 //   (T_n, U_n + 1) window too: they are computed from the padding rows of am and lm, which are finite like the others --
 //   at map_cell's address of the diagonal-major pair plane ws2, and, where znorm is given, znorm[n,t,u] =
 //   log(max(sum_v exp(am[t,v] - ma) exp(lm[u,v] - ml), FLT_MIN)) = Z(t,u) - ma(t) - ml(u) of every cell, row-major.
+//   topology, delay_penalty (pruned.h: TOPO_*; include/warp_rnnt_amd_topology.h): TOPO_MODIFIED fills the frame-major plane
+//   ws2 (N,T+1,U,2) with the floor and writes the pairs of the cells with t < xn[n], t >= u, u <= yn[n] at
+//   ((n (T+1) + t) U + u); znorm as above.  delay_penalty dp adds dp * (0.5f * (float)(T_n - 1) - (float)t) to the label
+//   channel.  xn, yn: needed by TOPO_MODIFIED and by dp != 0, else unread; TOPO_REGULAR with dp == 0 is the kernel above.
 hipError_t launch_simple_pairs(hipStream_t stream, int dtype, const void* am, const void* lm, const float* q,
-                               const int* labels, const SimpleStats& st, float* ws2, float* znorm, int N, int T, int U,
-                               int V, int blank, SimpleScales c);
+                               const int* labels, const int* xn, const int* yn, const SimpleStats& st, float* ws2,
+                               float* znorm, int N, int T, int U, int V, int blank, SimpleScales c, int topology,
+                               float delay_penalty);
 
 //   backward: from the row-major gradient pairs g2 (N,T,U,2) (zero outside the window, as k_grads writes them), znorm and
 //   scale[n] (nullptr: 1): the statistics again, the row sums ra and rl, then the two MFMA tile kernels -- d am over
 //   (64 t, 64 v) tiles with K = U, d lm over (64 u, 64 v) tiles with K = T -- and, with c2 != 0 and dq given, the (N,V)
 //   partial vectors of d q.  Every element of d am and d lm is written, in the inputs' type, rounded once; rows t >= T_n,
 //   rows u > U_n and the rows of an utterance with scale[n] == 0 are exactly zero.  No atomics: the same bits every run.
+//   g2_frames: the frames per utterance of g2, its row pitch: T, or T + 1 for the frame-major pairs of the modified
+//   topology (frames t < T are read; the kernels are blind to the topology given pairs by frame, zero outside the window).
 hipError_t launch_simple_backward(hipStream_t stream, int dtype, const void* am, const void* lm, const float* q,
                                   const int* labels, const int* xn, const int* yn, const float* g2, const float* znorm,
                                   const float* scale, const SimpleStats& st, void* dam, void* dlm, float* dq, int N, int T,
-                                  int U, int V, int blank, SimpleScales c);
+                                  int U, int V, int blank, SimpleScales c, int g2_frames);
 
 }  // namespace rnnt

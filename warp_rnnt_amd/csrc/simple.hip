@@ -21,6 +21,7 @@
 // owns column v adds G(t,u,1) of its 16 rows for every u of the step whose label is v, in ascending u.  No atomics
 // anywhere: a result's bits are a function of the utterance (with c2 != 0: and of q).
 #include "simple.h"
+#include "pruned.h"
 #include "row_chunks.h"
 
 #include <cfloat>
@@ -102,11 +103,15 @@ k_simple_stats(const E* __restrict__ x, const float* __restrict__ q, const int* 
 }
 
 // ---- the producer: Z and the two pair channels of every cell ----
-template <typename E, int ACC>
+// TOPO_MODIFIED (pruned.h): the pair goes to the frame-major plane of T + 1 rows, and only from the cells a path can reach
+// (t < xn[n], t >= u, u <= yn[n]; the rest of that plane is the floor, filled in front of this kernel); znorm as ever.
+// PEN: the label channel of frame t gets dp (0.5 (T_n - 1) - t) added, fp32: the bracket, one multiply, one add.
+template <typename E, int ACC, int TOPO, bool PEN>
 __global__ void __launch_bounds__(STHREADS)
 k_simple_pairs(const E* __restrict__ am, const E* __restrict__ lm, const float* __restrict__ q,
-               const int* __restrict__ labels, const float4* __restrict__ sa, const float4* __restrict__ sl,
-               float2* __restrict__ ws2, float* __restrict__ znorm, int T, int U, int V, int blank, SimpleScales c) {
+               const int* __restrict__ labels, const int* __restrict__ xn, const int* __restrict__ yn,
+               const float4* __restrict__ sa, const float4* __restrict__ sl, float2* __restrict__ ws2,
+               float* __restrict__ znorm, int T, int U, int V, int blank, SimpleScales c, float dp) {
     __shared__ float As[SK][SP], Bs[SK][SP];
     const int n = blockIdx.z, t0 = blockIdx.y * ST, u0 = blockIdx.x * ST;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -151,22 +156,28 @@ k_simple_pairs(const E* __restrict__ am, const E* __restrict__ lm, const float* 
         const float z = (lz + s.x) + su.x;
         const float al = (float)am[row * (size_t)V + lab];
         const float pb = (c.c0 * ((s.z + su.z) - z) + onlyB) + c.c2 * ((s.z + qb) - s.y);
-        const float pl = (c.c0 * ((al + su.w) - z) + onlyL) + c.c2 * ((al + ql) - s.y);
-        int d = t + u;
-        d = d >= T ? d % T : d;
-        ws2[((size_t)n * T + d) * (size_t)U + u] = make_float2(pb, pl);
+        float pl = (c.c0 * ((al + su.w) - z) + onlyL) + c.c2 * ((al + ql) - s.y);
+        if constexpr (PEN) pl = pl + dp * (0.5f * (float)(xn[n] - 1) - (float)t);
+        if constexpr (TOPO == TOPO_MODIFIED) {
+            if (t < xn[n] && t >= u && u <= yn[n]) ws2[((size_t)n * (T + 1) + t) * (size_t)U + u] = make_float2(pb, pl);
+        } else {
+            int d = t + u;
+            d = d >= T ? d % T : d;
+            ws2[((size_t)n * T + d) * (size_t)U + u] = make_float2(pb, pl);
+        }
         if (znorm) znorm[row * (size_t)U + u] = lz;
     }
 }
 
 // ---- the backward's row sums (simple.h: ra, rl) ----
-// a wave per frame: lanes over u, then the wave's sum
+// a wave per frame: lanes over u, then the wave's sum.  TP: frames per utterance of g2 (T; the modified plane: T + 1)
 __global__ void __launch_bounds__(STHREADS)
-k_simple_frame_sums(const float2* __restrict__ g2, const float* __restrict__ scale, float2* __restrict__ ra, int T, int U) {
+k_simple_frame_sums(const float2* __restrict__ g2, const float* __restrict__ scale, float2* __restrict__ ra, int T, int U,
+                    int TP) {
     const int n = blockIdx.y, t = blockIdx.x * (STHREADS / WAVE) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (t >= T) return;
     const float sc = scale ? scale[n] : 1.0f;
-    const float2* g = g2 + ((size_t)n * T + t) * (size_t)U;
+    const float2* g = g2 + ((size_t)n * TP + t) * (size_t)U;
     float s = 0.0f, b = 0.0f;
     if (sc != 0.0f)
         for (int u = lane; u < U; u += WAVE) {
@@ -183,14 +194,14 @@ k_simple_frame_sums(const float2* __restrict__ g2, const float* __restrict__ sca
 // 64 columns per workgroup: wave w sums the frames t = w mod 4, the four partial sums are added in the order of the waves
 __global__ void __launch_bounds__(STHREADS)
 k_simple_column_sums(const float2* __restrict__ g2, const float* __restrict__ scale, float4* __restrict__ rl, int T,
-                     int U) {
+                     int U, int TP) {
     __shared__ float part[STHREADS / WAVE][3][WAVE];
     const int n = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = blockIdx.x * WAVE + lane;
     const float sc = scale ? scale[n] : 1.0f;
     float s = 0.0f, b = 0.0f, l = 0.0f;
     if (u < U && sc != 0.0f)
         for (int t = wave; t < T; t += STHREADS / WAVE) {
-            const float2 v = g2[((size_t)n * T + t) * (size_t)U + u];
+            const float2 v = g2[((size_t)n * TP + t) * (size_t)U + u];
             const float g0 = sc * v.x, g1 = sc * v.y;
             s += g0 + g1;
             b += g0;
@@ -219,7 +230,7 @@ k_simple_backward(const E* __restrict__ am, const E* __restrict__ lm, const floa
                   const int* __restrict__ labels, const int* __restrict__ xn, const int* __restrict__ yn,
                   const float2* __restrict__ g2, const float* __restrict__ znorm, const float* __restrict__ scale,
                   const float4* __restrict__ sa, const float4* __restrict__ sl, const float2* __restrict__ ra,
-                  E* __restrict__ out, int T, int U, int V, int blank, SimpleScales c) {
+                  E* __restrict__ out, int T, int U, int V, int blank, SimpleScales c, int TP) {
     __shared__ float As[SK][SP], Bs[SK][SP];
     __shared__ float Gs[LM ? 1 : SK][SP];
     __shared__ float sums[LM ? 4 : 1][3][ST];
@@ -264,7 +275,7 @@ k_simple_backward(const E* __restrict__ am, const E* __restrict__ lm, const floa
             float w = 0.0f, g1 = 0.0f;
             if (t < T && u < U) {
                 const size_t cell = ((size_t)n * T + t) * (size_t)U + u;
-                const float2 g = g2[cell];
+                const float2 g = g2[((size_t)n * TP + t) * (size_t)U + u];
                 const float a = sc * g.x, b = sc * g.y;
                 w = (a + b) * row_exp(-znorm[cell]);
                 g1 = b;
@@ -420,23 +431,37 @@ hipError_t simple_stats(hipStream_t stream, const E* am, const E* lm, const floa
 
 template <typename E>
 hipError_t simple_pairs(hipStream_t stream, const E* am, const E* lm, const float* q, const int* labels,
-                        const SimpleStats& st, float* ws2, float* znorm, int N, int T, int U, int V, int blank,
-                        SimpleScales c) {
+                        const int* xn, const int* yn, const SimpleStats& st, float* ws2, float* znorm, int N, int T, int U,
+                        int V, int blank, SimpleScales c, int topology, float dp) {
     if (N == 0) return hipSuccess;
-    const hipError_t e = simple_stats(stream, am, lm, q, labels, st, N, T, U, V, blank);
+    hipError_t e = simple_stats(stream, am, lm, q, labels, st, N, T, U, V, blank);
     if (e != hipSuccess) return e;
+    const bool modified = topology == TOPO_MODIFIED;
+    // (the regular form writes every cell of its plane; the modified one the cells on a path over the floor)
+    if (modified && (e = launch_pruned_floor(stream, ws2, (size_t)N * (T + 1) * U)) != hipSuccess) return e;
     const dim3 grid(tiles(U), tiles(T), (unsigned)N);
+    const float4* sa = reinterpret_cast<const float4*>(st.sa);
+    const float4* sl = reinterpret_cast<const float4*>(st.sl);
+    float2* out = reinterpret_cast<float2*>(ws2);
     return access_dispatch<E>(row_access<E>(V, am, lm), [&](auto acc) {
-        k_simple_pairs<E, decltype(acc)::value><<<grid, STHREADS, 0, stream>>>(
-            am, lm, q, labels, reinterpret_cast<const float4*>(st.sa), reinterpret_cast<const float4*>(st.sl),
-            reinterpret_cast<float2*>(ws2), znorm, T, U, V, blank, c);
+        constexpr int ACC = decltype(acc)::value;
+        // (regular with dp == 0: the kernel as it was, no length is read)
+        if (modified)
+            k_simple_pairs<E, ACC, TOPO_MODIFIED, true><<<grid, STHREADS, 0, stream>>>(am, lm, q, labels, xn, yn, sa, sl, out,
+                                                                                      znorm, T, U, V, blank, c, dp);
+        else if (dp != 0.0f)
+            k_simple_pairs<E, ACC, TOPO_REGULAR, true><<<grid, STHREADS, 0, stream>>>(am, lm, q, labels, xn, yn, sa, sl, out,
+                                                                                     znorm, T, U, V, blank, c, dp);
+        else
+            k_simple_pairs<E, ACC, TOPO_REGULAR, false><<<grid, STHREADS, 0, stream>>>(am, lm, q, labels, xn, yn, sa, sl, out,
+                                                                                      znorm, T, U, V, blank, c, dp);
     });
 }
 
 template <typename E>
 hipError_t simple_backward(hipStream_t stream, const E* am, const E* lm, const float* q, const int* labels, const int* xn,
                            const int* yn, const float* g2, const float* znorm, const float* scale, const SimpleStats& st,
-                           E* dam, E* dlm, float* dq, int N, int T, int U, int V, int blank, SimpleScales c) {
+                           E* dam, E* dlm, float* dq, int N, int T, int U, int V, int blank, SimpleScales c, int TP) {
     if (N == 0) return hipSuccess;
     hipError_t e = simple_stats(stream, am, lm, q, labels, st, N, T, U, V, blank);
     if (e != hipSuccess) return e;
@@ -446,16 +471,16 @@ hipError_t simple_backward(hipStream_t stream, const E* am, const E* lm, const f
     float2* ra = reinterpret_cast<float2*>(st.ra);
     float4* rl = reinterpret_cast<float4*>(st.rl);
     const bool wants_dq = dq && q && c.c2 != 0.0f;
-    k_simple_frame_sums<<<dim3((unsigned)((T + 3) / 4), (unsigned)N), STHREADS, 0, stream>>>(g, scale, ra, T, U);
+    k_simple_frame_sums<<<dim3((unsigned)((T + 3) / 4), (unsigned)N), STHREADS, 0, stream>>>(g, scale, ra, T, U, TP);
     if (wants_dq)      // (d lm forms its column sums on the way: only d q reads these)
         k_simple_column_sums<<<dim3((unsigned)((U + WAVE - 1) / WAVE), (unsigned)N), STHREADS, 0, stream>>>(g, scale, rl, T,
-                                                                                                          U);
+                                                                                                          U, TP);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (dam) {
         const dim3 grid(tiles(V), tiles(T), (unsigned)N);
         e = access_dispatch<E>(row_access<E>(V, lm, nullptr), [&](auto acc) {
             k_simple_backward<E, decltype(acc)::value, false><<<grid, STHREADS, 0, stream>>>(
-                am, lm, q, labels, xn, yn, g, znorm, scale, sa, sl, ra, dam, T, U, V, blank, c);
+                am, lm, q, labels, xn, yn, g, znorm, scale, sa, sl, ra, dam, T, U, V, blank, c, TP);
         });
         if (e != hipSuccess) return e;
     }
@@ -463,7 +488,7 @@ hipError_t simple_backward(hipStream_t stream, const E* am, const E* lm, const f
         const dim3 grid(tiles(V), tiles(U), (unsigned)N);
         e = access_dispatch<E>(row_access<E>(V, am, nullptr), [&](auto acc) {
             k_simple_backward<E, decltype(acc)::value, true><<<grid, STHREADS, 0, stream>>>(
-                am, lm, q, labels, xn, yn, g, znorm, scale, sa, sl, ra, dlm, T, U, V, blank, c);
+                am, lm, q, labels, xn, yn, g, znorm, scale, sa, sl, ra, dlm, T, U, V, blank, c, TP);
         });
         if (e != hipSuccess) return e;
     }
@@ -478,24 +503,28 @@ hipError_t simple_backward(hipStream_t stream, const E* am, const E* lm, const f
 }  // namespace
 
 hipError_t launch_simple_pairs(hipStream_t stream, int dtype, const void* am, const void* lm, const float* q,
-                               const int* labels, const SimpleStats& st, float* ws2, float* znorm, int N, int T, int U,
-                               int V, int blank, SimpleScales c) {
+                               const int* labels, const int* xn, const int* yn, const SimpleStats& st, float* ws2,
+                               float* znorm, int N, int T, int U, int V, int blank, SimpleScales c, int topology,
+                               float delay_penalty) {
     if (!simple_shape_ok(N, T, U, V, blank) || (c.c2 != 0.0f && !q)) return hipErrorInvalidValue;
+    if ((topology != TOPO_REGULAR && topology != TOPO_MODIFIED) || ((topology == TOPO_MODIFIED || delay_penalty != 0.0f) && (!xn || !yn)))
+        return hipErrorInvalidValue;
     return row_typed(dtype, am, nullptr, [&](auto* a, auto*) {
         using E = std::remove_const_t<std::remove_pointer_t<decltype(a)>>;
-        return simple_pairs<E>(stream, a, static_cast<const E*>(lm), q, labels, st, ws2, znorm, N, T, U, V, blank, c);
+        return simple_pairs<E>(stream, a, static_cast<const E*>(lm), q, labels, xn, yn, st, ws2, znorm, N, T, U, V, blank, c,
+                               topology, delay_penalty);
     });
 }
 
 hipError_t launch_simple_backward(hipStream_t stream, int dtype, const void* am, const void* lm, const float* q,
                                   const int* labels, const int* xn, const int* yn, const float* g2, const float* znorm,
                                   const float* scale, const SimpleStats& st, void* dam, void* dlm, float* dq, int N, int T,
-                                  int U, int V, int blank, SimpleScales c) {
-    if (!simple_shape_ok(N, T, U, V, blank) || (c.c2 != 0.0f && !q)) return hipErrorInvalidValue;
+                                  int U, int V, int blank, SimpleScales c, int g2_frames) {
+    if (!simple_shape_ok(N, T, U, V, blank) || (c.c2 != 0.0f && !q) || g2_frames < T) return hipErrorInvalidValue;
     return row_typed(dtype, am, dam, [&](auto* a, auto* da) {
         using E = std::remove_const_t<std::remove_pointer_t<decltype(a)>>;
         return simple_backward<E>(stream, a, static_cast<const E*>(lm), q, labels, xn, yn, g2, znorm, scale, st, da,
-                                  static_cast<E*>(dlm), dq, N, T, U, V, blank, c);
+                                  static_cast<E*>(dlm), dq, N, T, U, V, blank, c, g2_frames);
     });
 }
 

@@ -1,5 +1,7 @@
 """Torch-tensor front ends of the native entry points (device memory + streams only)."""
 import ctypes
+import functools
+import inspect
 import os
 import warnings
 
@@ -692,6 +694,125 @@ def simple_backward(am, lm, q, labels, xn, yn, grads, znorm, grad_costs, blank=0
                                           lm.data_ptr(), _ptr(q), _ptr(labels), xn.data_ptr(), yn.data_ptr(),
                                           grads.data_ptr(), znorm.data_ptr(), _ptr(grad_costs), dam.data_ptr(),
                                           dlm.data_ptr(), _ptr(parts), N, T, U, V, blank, c1, c2))
+    return dam, dlm, None if parts is None else parts.sum(0)
+
+
+RNNT_TYPES = {"regular": _lib.TOPOLOGY_REGULAR, "modified": _lib.TOPOLOGY_MODIFIED}
+
+
+def topology_of(rnnt_type, delay_penalty):
+    """(topology, delay_penalty as the fp32 value the C entries receive) of k2's ``rnnt_type`` and ``delay_penalty``, with
+    the refusals of include/warp_rnnt_amd_topology.h spelt out."""
+    if rnnt_type not in RNNT_TYPES:
+        raise ValueError(f'rnnt_type must be "regular" or "modified", not {rnnt_type!r} (k2\'s "constrained" topology is '
+                         f"not covered)")
+    dp = ctypes.c_float(delay_penalty).value
+    if not 0.0 <= dp < float("inf"):                                                             # (false for a NaN)
+        raise ValueError(f"delay_penalty must be finite and >= 0, not {delay_penalty}")
+    return RNNT_TYPES[rnnt_type], dp
+
+
+def with_topology_keywords(positional, full):
+    """``positional`` -- a front end as it is documented and introspected, its positional signature unchanged -- taking
+    the keyword-only ``rnnt_type`` and ``delay_penalty`` as well: ``full`` is called with ``positional``'s arguments, bound
+    and with their defaults, and the two keywords behind them."""
+    signature = inspect.signature(positional)
+
+    @functools.wraps(positional)
+    def front(*args, rnnt_type="regular", delay_penalty=0.0, **kwargs):
+        bound = signature.bind(*args, **kwargs)
+        bound.apply_defaults()
+        return full(*bound.args, rnnt_type=rnnt_type, delay_penalty=delay_penalty)
+    return front
+
+
+def pruned_loss_topology(logits, labels, starts, xn, yn, blank=0, fastemit_lambda=0.0, with_grads=True,
+                         topology=_lib.TOPOLOGY_REGULAR, delay_penalty=0.0):
+    """:func:`pruned_loss` with a topology and a delay penalty (include/warp_rnnt_amd_topology.h).  The gradient pairs of
+    TOPOLOGY_MODIFIED are (N,T+1,U,2), frame-major -- what :func:`pruned_logits_backward_topology` reads."""
+    L = _lib.load()
+    N, T, S, V = logits.shape
+    U = labels.shape[1] + 1
+    dev = logits.device
+    _pruned_check(S, U, V, blank)
+    _mismatch.poll(dev)
+    frames = T + 1 if topology == _lib.TOPOLOGY_MODIFIED else T
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        grads = torch.empty((N, frames, U, 2), dtype=torch.float32, device=dev) if with_grads else None
+        if N == 0:
+            return costs, grads
+        ws = _workspace(dev, lambda n, t, u: L.rnnt_amd_pruned_topology_workspace_size(topology, n, t, u), "N T U", N, T, U)
+        _check(L.rnnt_amd_pruned_loss_logits_topology(
+            _stream(dev), ws.data_ptr(), LOGITS_DTYPES[logits.dtype], logits.data_ptr(), _ptr(labels), starts.data_ptr(),
+            xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(grads), N, T, U, S, V, blank, float(fastemit_lambda),
+            topology, float(delay_penalty)))
+    return costs, grads
+
+
+def pruned_logits_backward_topology(logits, labels, starts, xn, yn, grads, grad_costs, blank=0,
+                                    topology=_lib.TOPOLOGY_REGULAR):
+    """:func:`pruned_logits_backward` of :func:`pruned_loss_topology`; TOPOLOGY_MODIFIED reads the lengths: rows with
+    t >= xn[n], t < u or u > yn[n] are exactly zero."""
+    L = _lib.load()
+    N, T, S, V = logits.shape
+    U = labels.shape[1] + 1
+    dev = logits.device
+    with torch.cuda.device(dev):
+        out = torch.empty_like(logits)
+        if N == 0:
+            return out
+        _check(L.rnnt_amd_pruned_logits_backward_topology(
+            _stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(), _ptr(labels), starts.data_ptr(), xn.data_ptr(),
+            yn.data_ptr(), grads.data_ptr(), _ptr(grad_costs), out.data_ptr(), N, T, U, S, V, blank, topology))
+    return out
+
+
+def simple_loss_topology(am, lm, q, labels, xn, yn, blank=0, lm_only_scale=0.0, am_only_scale=0.0, fastemit_lambda=0.0,
+                         with_grads=True, topology=_lib.TOPOLOGY_REGULAR, delay_penalty=0.0):
+    """:func:`simple_loss` with a topology and a delay penalty (include/warp_rnnt_amd_topology.h).  The gradient pairs of
+    TOPOLOGY_MODIFIED are (N,T+1,U,2), frame-major: rows 0 .. T-1 are d cost / d pair of cell (t,u), zero outside an
+    utterance's window (the terminal cell's pair is cleared); row T is no frame's -- what
+    :func:`simple_backward_topology` reads."""
+    L = _lib.load()
+    N, T, V = am.shape
+    U = lm.shape[1]
+    dev = am.device
+    c1, c2 = _simple_check(V, blank, lm_only_scale, am_only_scale, q)
+    _mismatch.poll(dev)
+    frames = T + 1 if topology == _lib.TOPOLOGY_MODIFIED else T
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        grads = torch.empty((N, frames, U, 2), dtype=torch.float32, device=dev) if with_grads else None
+        znorm = torch.empty((N, T, U), dtype=torch.float32, device=dev) if with_grads else None
+        if N == 0:
+            return costs, grads, znorm
+        ws = _workspace(dev, lambda n, t, u: L.rnnt_amd_simple_topology_workspace_size(topology, n, t, u), "N T U", N, T, U)
+        _check(L.rnnt_amd_simple_loss_topology(
+            _stream(dev), ws.data_ptr(), LOGITS_DTYPES[am.dtype], am.data_ptr(), lm.data_ptr(), _ptr(q), _ptr(labels),
+            xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(grads), _ptr(znorm), N, T, U, V, blank, c1, c2,
+            float(fastemit_lambda), topology, float(delay_penalty)))
+    return costs, grads, znorm
+
+
+def simple_backward_topology(am, lm, q, labels, xn, yn, grads, znorm, grad_costs, blank=0, lm_only_scale=0.0,
+                             am_only_scale=0.0, topology=_lib.TOPOLOGY_REGULAR):
+    """:func:`simple_backward` of :func:`simple_loss_topology`."""
+    L = _lib.load()
+    N, T, V = am.shape
+    U = lm.shape[1]
+    dev = am.device
+    c1, c2 = _simple_check(V, blank, lm_only_scale, am_only_scale, q)
+    with torch.cuda.device(dev):
+        dam, dlm = torch.empty_like(am), torch.empty_like(lm)
+        parts = torch.empty((N, V), dtype=torch.float32, device=dev) if c2 != 0.0 else None
+        if N == 0:
+            return dam, dlm, None if parts is None else parts.sum(0)
+        ws = _workspace(dev, lambda n, t, u: L.rnnt_amd_simple_topology_workspace_size(topology, n, t, u), "N T U", N, T, U)
+        _check(L.rnnt_amd_simple_backward_topology(
+            _stream(dev), ws.data_ptr(), LOGITS_DTYPES[am.dtype], am.data_ptr(), lm.data_ptr(), _ptr(q), _ptr(labels),
+            xn.data_ptr(), yn.data_ptr(), grads.data_ptr(), znorm.data_ptr(), _ptr(grad_costs), dam.data_ptr(),
+            dlm.data_ptr(), _ptr(parts), N, T, U, V, blank, c1, c2, topology))
     return dam, dlm, None if parts is None else parts.sum(0)
 
 

@@ -27,7 +27,13 @@ no ``autograd.grad(..., retain_graph=True)``.  The plain-torch form of its pairs
 ``simple_pairs`` below with ``warp_rnnt.rnnt_loss(pairs, labels, xn, yn, blank=-1)`` behind it, stays
 (tests/test_gpu_pruned.py runs the recipe on it).
 
-Out of scope: k2's ``modified`` topology and ``delay_penalty``; a pruned form of HAT, TDT, the joint entries, the compact
+``rnnt_type="modified"`` (k2's second topology: a label consumes a frame, at most one symbol per frame, no terminal blank)
+and ``delay_penalty`` (Kang et al. 2022: ``delay_penalty * ((T_n - 1) / 2 - t)`` added to the label log-probs of frame
+``t``) are the two knobs of the streaming recipes; both passes take them and must be given the same values.  The modified
+lattice is the regular one over the sheared cells ``(t - u, u)``, whose diagonals are the frames: the sweeps, the gradient
+kernel, FastEmit and the guard run unchanged on a frame-major plane of ``T + 1`` rows.
+
+Out of scope: k2's ``constrained`` topology; a pruned form of HAT, TDT, the joint entries, the compact
 layout or ``rnnt_align``; the gradient clamp; a sweep that visits the band's cells only (the sweeps cost what the dense
 loss's do -- DESIGN.md 3.17 prices the alternative).
 """
@@ -86,23 +92,33 @@ def band_starts(ranges, S=None):
 class PrunedRNNTLossFromLogits(torch.autograd.Function):
 
     @staticmethod
-    def forward(ctx, logits, labels, starts, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0):
+    def forward(ctx, logits, labels, starts, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0,
+                topology=ops.RNNT_TYPES["regular"], delay_penalty=0.0):
         check_pruned_inputs(logits, labels, starts, frames_lengths, labels_lengths)
         wants_grad = ctx.needs_input_grad[0]          # (nothing requires grad: no pairs are produced or kept)
-        costs, grads = ops.pruned_loss(logits, labels, starts, frames_lengths, labels_lengths, blank, fastemit_lambda,
-                                       wants_grad)
+        # the defaults are the entries without a topology: the calls, and so the bits, of every earlier version
+        ctx.plain = topology == ops.RNNT_TYPES["regular"] and delay_penalty == 0.0
+        if ctx.plain:
+            costs, grads = ops.pruned_loss(logits, labels, starts, frames_lengths, labels_lengths, blank, fastemit_lambda,
+                                           wants_grad)
+        else:
+            costs, grads = ops.pruned_loss_topology(logits, labels, starts, frames_lengths, labels_lengths, blank,
+                                                    fastemit_lambda, wants_grad, topology, delay_penalty)
         no_path = costs >= NO_PATH_COST               # (on the device: nothing is read back)
         if wants_grad:
-            ctx.save_for_backward(logits, labels, starts, grads, no_path)
-        ctx.blank = blank
+            ctx.save_for_backward(logits, labels, starts, frames_lengths, labels_lengths, grads, no_path)
+        ctx.blank, ctx.topology = blank, topology
         return torch.where(no_path, torch.full_like(costs, float("inf")), costs)
 
     @staticmethod
     def backward(ctx, grads_output):
-        logits, labels, starts, grads, no_path = ctx.saved_tensors
+        logits, labels, starts, xn, yn, grads, no_path = ctx.saved_tensors
         go = grads_output.reshape(-1).to(torch.float32)
         go = torch.where(no_path, torch.zeros_like(go), go).contiguous()       # scale 0: exactly zero rows, pairs unread
-        return (ops.pruned_logits_backward(logits, labels, starts, grads, go, ctx.blank),) + (None,) * 6
+        if ctx.plain:
+            return (ops.pruned_logits_backward(logits, labels, starts, grads, go, ctx.blank),) + (None,) * 8
+        return (ops.pruned_logits_backward_topology(logits, labels, starts, xn, yn, grads, go, ctx.blank,
+                                                    ctx.topology),) + (None,) * 8
 
 
 def pruned_rnnt_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, ranges: torch.Tensor,
@@ -121,27 +137,51 @@ def pruned_rnnt_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, ran
     An utterance whose band holds no path from ``(0,0)`` to ``(T_n - 1, U_n)`` -- ``prune_ranges`` explains when that
     happens -- has the cost ``+inf`` and exactly zero gradient rows; the other utterances of the batch are not affected.
     The forward/backward guard of the lattice (a ``RuntimeWarning`` at a later call, ``warp_rnnt_amd.last_mismatch()``) may
-    name such an utterance: its two sweeps are sums of the floor and need not agree."""
+    name such an utterance: its two sweeps are sums of the floor and need not agree.
+
+    Two more arguments, by keyword only: ``rnnt_type="regular"`` and ``delay_penalty=0.0``.
+    ``rnnt_type``: ``"regular"`` or ``"modified"`` (k2's: a label consumes a frame; the cost is ``-alpha(T_n, U_n)`` of
+    ``alpha(t,u) = lse(alpha(t-1,u) + lpB(t-1,u), alpha(t-1,u-1) + lpL(t-1,u-1))``; an utterance with ``T_n < U_n`` has
+    no path); another string is a ``ValueError`` (``"constrained"`` is not covered).  ``delay_penalty >= 0`` adds
+    ``delay_penalty * ((T_n - 1) / 2 - t)`` to the label log-prob of every cell of frame ``t`` (fp32), as k2 does.  With
+    ``"modified"`` rows of frames ``t >= frames_lengths[n]`` are never read, whatever their starts are."""
+    return _pruned_loss(logits, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank,
+                        fastemit_lambda)
+
+
+def _pruned_loss(logits, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank, fastemit_lambda,
+                 rnnt_type="regular", delay_penalty=0.0):
+    topology, delay_penalty = ops.topology_of(rnnt_type, delay_penalty)
     assert reduction is None or reduction in ("none", "mean", "sum")
     assert isinstance(blank, int)
     starts = band_starts(ranges, logits.shape[2] if logits.dim() == 4 else None)
-    costs = PrunedRNNTLossFromLogits.apply(logits, labels, starts, frames_lengths, labels_lengths, blank, fastemit_lambda)
+    costs = PrunedRNNTLossFromLogits.apply(logits, labels, starts, frames_lengths, labels_lengths, blank, fastemit_lambda,
+                                           topology, delay_penalty)
     return finish_costs(costs, frames_lengths, average_frames, reduction)
 
 
-class PrunedRNNTLoss(torch.nn.Module):
-    """:func:`pruned_rnnt_loss_from_logits` as a module: stores ``blank``, ``fastemit_lambda`` and ``reduction``."""
+pruned_rnnt_loss_from_logits = ops.with_topology_keywords(pruned_rnnt_loss_from_logits, _pruned_loss)
 
-    def __init__(self, blank: int = 0, fastemit_lambda: float = 0.0, reduction: Optional[str] = "mean"):
+
+class PrunedRNNTLoss(torch.nn.Module):
+    """:func:`pruned_rnnt_loss_from_logits` as a module: stores ``blank``, ``fastemit_lambda``, ``reduction``,
+    ``rnnt_type`` and ``delay_penalty``."""
+
+    def __init__(self, blank: int = 0, fastemit_lambda: float = 0.0, reduction: Optional[str] = "mean",
+                 rnnt_type: str = "regular", delay_penalty: float = 0.0):
         super().__init__()
+        ops.topology_of(rnnt_type, delay_penalty)
         self.blank = blank
         self.fastemit_lambda = fastemit_lambda
         self.reduction = reduction
+        self.rnnt_type = rnnt_type
+        self.delay_penalty = delay_penalty
 
     def forward(self, logits, labels, ranges, frames_lengths, labels_lengths):
         return pruned_rnnt_loss_from_logits(logits, labels, ranges, frames_lengths, labels_lengths,
                                             reduction=self.reduction, blank=self.blank,
-                                            fastemit_lambda=self.fastemit_lambda)
+                                            fastemit_lambda=self.fastemit_lambda, rnnt_type=self.rnnt_type,
+                                            delay_penalty=self.delay_penalty)
 
 
 # ---- the rest of the recipe: plain torch on any device, not a hot path, no Python loop over N or T, no read-back ----

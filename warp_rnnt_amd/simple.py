@@ -18,8 +18,9 @@ epilogue writes the pairs where the lattice sweeps read them, and the backward i
 DESIGN.md 3.18).  The forward already holds the gradient pairs -- minus the edge occupancies that
 :func:`warp_rnnt_amd.pruned.prune_ranges` reads -- and hands them back with ``return_grad=True``.
 
-``am`` and ``lm`` are finite: a ``-inf`` entry is not a masked entry here.  Out of scope: k2's ``modified`` topology and
-``delay_penalty``, the compact layout, the gradient clamp.
+``am`` and ``lm`` are finite: a ``-inf`` entry is not a masked entry here.  ``rnnt_type="modified"`` and
+``delay_penalty`` are those of :func:`warp_rnnt_amd.pruned.pruned_rnnt_loss_from_logits`; the two passes
+of the recipe take the same values.  Out of scope: k2's ``constrained`` topology, the compact layout, the gradient clamp.
 """
 from typing import Optional
 
@@ -27,6 +28,7 @@ import torch
 
 from . import ops
 from .fused import finish_costs
+from .pruned import NO_PATH_COST
 from warp_rnnt import _C as _core
 
 TINY = torch.finfo(torch.float32).tiny
@@ -73,25 +75,48 @@ class SimpleRNNTLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, am, lm, q, labels, frames_lengths, labels_lengths, blank, lm_only_scale, am_only_scale,
-                fastemit_lambda, return_grad):
+                fastemit_lambda, return_grad, topology=ops.RNNT_TYPES["regular"], delay_penalty=0.0):
         check_simple_inputs(am, lm, labels, frames_lengths, labels_lengths)
         wants_grad = any(ctx.needs_input_grad[:3])
-        costs, grads, znorm = ops.simple_loss(am, lm, q, labels, frames_lengths, labels_lengths, blank, lm_only_scale,
-                                              am_only_scale, fastemit_lambda, wants_grad or return_grad)
-        if wants_grad:
-            ctx.save_for_backward(am, lm, q, labels, frames_lengths, labels_lengths, grads, znorm)
         ctx.args = (blank, lm_only_scale, am_only_scale)
+        # the defaults are the entries without a topology: the calls, and so the bits, of every earlier version
+        ctx.plain = topology == ops.RNNT_TYPES["regular"] and delay_penalty == 0.0
+        ctx.topology = topology
+        if ctx.plain:
+            costs, grads, znorm = ops.simple_loss(am, lm, q, labels, frames_lengths, labels_lengths, blank, lm_only_scale,
+                                                  am_only_scale, fastemit_lambda, wants_grad or return_grad)
+            if wants_grad:
+                ctx.save_for_backward(am, lm, q, labels, frames_lengths, labels_lengths, grads, znorm)
+            if not return_grad:
+                return costs
+            ctx.mark_non_differentiable(grads)
+            return costs, grads
+        costs, grads, znorm = ops.simple_loss_topology(am, lm, q, labels, frames_lengths, labels_lengths, blank,
+                                                       lm_only_scale, am_only_scale, fastemit_lambda,
+                                                       wants_grad or return_grad, topology, delay_penalty)
+        # the modified lattice of an utterance with T_n < U_n holds no path: +inf, zero pairs, zero rows (on the device)
+        no_path = costs >= NO_PATH_COST
+        costs = torch.where(no_path, torch.full_like(costs, float("inf")), costs)
+        if wants_grad:
+            ctx.save_for_backward(am, lm, q, labels, frames_lengths, labels_lengths, grads, znorm, no_path)
         if not return_grad:
             return costs
-        ctx.mark_non_differentiable(grads)
-        return costs, grads
+        # by frame: the modified pairs are (N,T+1,U,2) and row T is no frame's
+        pairs = torch.where(no_path[:, None, None, None], torch.zeros_like(grads), grads)[:, :am.shape[1]]
+        ctx.mark_non_differentiable(pairs)
+        return costs, pairs
 
     @staticmethod
     def backward(ctx, grads_output, *_):
-        am, lm, q, labels, xn, yn, grads, znorm = ctx.saved_tensors
-        go = grads_output.reshape(-1).to(torch.float32).contiguous()
-        dam, dlm, dq = ops.simple_backward(am, lm, q, labels, xn, yn, grads, znorm, go, *ctx.args)
-        return (dam, dlm, dq) + (None,) * 8
+        go = grads_output.reshape(-1).to(torch.float32)
+        if ctx.plain:
+            am, lm, q, labels, xn, yn, grads, znorm = ctx.saved_tensors
+            dam, dlm, dq = ops.simple_backward(am, lm, q, labels, xn, yn, grads, znorm, go.contiguous(), *ctx.args)
+            return (dam, dlm, dq) + (None,) * 10
+        am, lm, q, labels, xn, yn, grads, znorm, no_path = ctx.saved_tensors
+        go = torch.where(no_path, torch.zeros_like(go), go).contiguous()       # scale 0: exactly zero rows, pairs unread
+        dam, dlm, dq = ops.simple_backward_topology(am, lm, q, labels, xn, yn, grads, znorm, go, *ctx.args, ctx.topology)
+        return (dam, dlm, dq) + (None,) * 10
 
 
 def simple_rnnt_loss(am: torch.Tensor, lm: torch.Tensor, labels: torch.Tensor, frames_lengths: torch.Tensor,
@@ -107,23 +132,45 @@ def simple_rnnt_loss(am: torch.Tensor, lm: torch.Tensor, labels: torch.Tensor, f
     ``return_grad=True`` returns ``(loss, pair_grads)``: ``pair_grads`` is the detached ``(N,T,U,2)`` fp32
     ``d cost[n] / d pair`` -- not scaled by the reduction or any upstream gradient, zero outside an utterance's window --
     which is what :func:`warp_rnnt_amd.pruned.prune_ranges` takes.  With ``am_only_scale == 0`` an utterance's cost and
-    gradients do not depend on its batch."""
+    gradients do not depend on its batch.
+
+    Two more arguments, by keyword only: ``rnnt_type="regular"`` and ``delay_penalty=0.0``.
+    ``rnnt_type`` (``"regular"`` or ``"modified"``; another string is a ``ValueError``, ``"constrained"`` is not
+    covered) and ``delay_penalty >= 0`` are those of :func:`warp_rnnt_amd.pruned.pruned_rnnt_loss_from_logits`.  With
+    ``"modified"`` an utterance with ``T_n < U_n`` has the cost ``+inf``, zero ``pair_grads`` and zero gradient rows, and
+    ``pair_grads`` is a ``(N,T,U,2)`` view of the frames of a ``(N,T+1,U,2)`` tensor: index it by ``(t,u)`` as ever."""
+    return _simple_loss(am, lm, labels, frames_lengths, labels_lengths, blank, lm_only_scale, am_only_scale,
+                        fastemit_lambda, average_frames, reduction, return_grad)
+
+
+def _simple_loss(am, lm, labels, frames_lengths, labels_lengths, blank, lm_only_scale, am_only_scale, fastemit_lambda,
+                 average_frames, reduction, return_grad, rnnt_type="regular", delay_penalty=0.0):
+    topology, delay_penalty = ops.topology_of(rnnt_type, delay_penalty)
     assert reduction is None or reduction in ("none", "mean", "sum")
     assert isinstance(blank, int)
     q = batch_log_unigram(lm) if am_only_scale != 0 and lm.dim() == 3 and lm.is_floating_point() else None
     out = SimpleRNNTLossFunction.apply(am, lm, q, labels, frames_lengths, labels_lengths, blank, float(lm_only_scale),
-                                       float(am_only_scale), float(fastemit_lambda), bool(return_grad))
+                                       float(am_only_scale), float(fastemit_lambda), bool(return_grad), topology,
+                                       delay_penalty)
     if not return_grad:
         return finish_costs(out, frames_lengths, average_frames, reduction)
     return finish_costs(out[0], frames_lengths, average_frames, reduction), out[1]
 
 
+simple_rnnt_loss = ops.with_topology_keywords(simple_rnnt_loss, _simple_loss)
+
+
 class SimpleRNNTLoss(torch.nn.Module):
-    """:func:`simple_rnnt_loss` as a module: stores ``blank``, the two scales, ``fastemit_lambda`` and ``reduction``."""
+    """:func:`simple_rnnt_loss` as a module: stores ``blank``, the two scales, ``fastemit_lambda``, ``reduction``,
+    ``rnnt_type`` and ``delay_penalty``."""
 
     def __init__(self, blank: int = 0, lm_only_scale: float = 0.0, am_only_scale: float = 0.0,
-                 fastemit_lambda: float = 0.0, reduction: Optional[str] = "mean"):
+                 fastemit_lambda: float = 0.0, reduction: Optional[str] = "mean", rnnt_type: str = "regular",
+                 delay_penalty: float = 0.0):
         super().__init__()
+        ops.topology_of(rnnt_type, delay_penalty)
+        self.rnnt_type = rnnt_type
+        self.delay_penalty = delay_penalty
         self.blank = blank
         self.lm_only_scale = lm_only_scale
         self.am_only_scale = am_only_scale
@@ -133,4 +180,5 @@ class SimpleRNNTLoss(torch.nn.Module):
     def forward(self, am, lm, labels, frames_lengths, labels_lengths, return_grad: bool = False):
         return simple_rnnt_loss(am, lm, labels, frames_lengths, labels_lengths, blank=self.blank,
                                 lm_only_scale=self.lm_only_scale, am_only_scale=self.am_only_scale,
-                                fastemit_lambda=self.fastemit_lambda, reduction=self.reduction, return_grad=return_grad)
+                                fastemit_lambda=self.fastemit_lambda, reduction=self.reduction, return_grad=return_grad,
+                                rnnt_type=self.rnnt_type, delay_penalty=self.delay_penalty)
