@@ -201,6 +201,18 @@ TOPOLOGY_SYMBOLS = {
 # behind ADDITIVE_MULTIBLANK, under the same contract (tests/test_host_modified.py holds this one to it); a tuple of its own
 # for the same reason
 ADDITIVE_TOPOLOGY = ((TOPOLOGY_SYMBOLS, "warp_rnnt_amd_topology.h"),)
+# every symbol include/warp_rnnt_amd_pruned_joint.h declares (the joint network fused into the pruned loss; additive: it did
+# not move the version): the size is a function of (dtype, N, T, U, S, H, V); the forward is (stream, workspace, dtype,
+# activation, f, g, weight, bias, labels, starts, xn, yn, costs, stats, grads, N, T, U, S, H, V, blank, fastemit_lambda), the
+# backward (stream, workspace, dtype, activation, f, g, weight, bias, labels, starts, xn, yn, stats, grads, grad_costs, df,
+# dg, dweight, dbias, N, T, U, S, H, V, blank): the joint entries' lists with `starts` behind the labels and S behind U
+PRUNED_JOINT_SYMBOLS = {
+    "rnnt_amd_pruned_joint_workspace_size": (_sz, [_i] * 7),
+    "rnnt_amd_pruned_joint_loss": (_i, [_vp, _vp, _i, _i] + [_vp] * 11 + [_i] * 7 + [_f]),
+    "rnnt_amd_pruned_joint_backward": (_i, [_vp, _vp, _i, _i] + [_vp] * 15 + [_i] * 7),
+}
+# behind ADDITIVE_TOPOLOGY, under the same contract; a tuple of its own for the same reason
+ADDITIVE_PRUNED_JOINT = ((PRUNED_JOINT_SYMBOLS, "warp_rnnt_amd_pruned_joint.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -239,7 +251,7 @@ def load():
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
     for table, header in (ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED + ADDITIVE_SIMPLE +
-                          ADDITIVE_MULTIBLANK + ADDITIVE_TOPOLOGY):
+                          ADDITIVE_MULTIBLANK + ADDITIVE_TOPOLOGY + ADDITIVE_PRUNED_JOINT):
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

@@ -7,12 +7,14 @@
 // (include/warp_rnnt_amd_align.h), the token-and-duration loss (include/warp_rnnt_amd_tdt.h: producer, sweeps and
 // gradient kernel all its own), its best-path alignments (include/warp_rnnt_amd_tdt_align.h) and the joint network fused
 // into it (include/warp_rnnt_amd_tdt_joint.h), the multi-blank loss (include/warp_rnnt_amd_multiblank.h: producer, sweeps
-// and gradient kernel all its own).  Host-side orchestration only: argument checks, workspace carving, launches.
+// and gradient kernel all its own), the joint network fused into the pruned loss
+// (include/warp_rnnt_amd_pruned_joint.h).  Host-side orchestration only: argument checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd_align.h"
 #include "../../include/warp_rnnt_amd_hat.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
 #include "../../include/warp_rnnt_amd_multiblank.h"
 #include "../../include/warp_rnnt_amd_pruned.h"
+#include "../../include/warp_rnnt_amd_pruned_joint.h"
 #include "../../include/warp_rnnt_amd_simple.h"
 #include "../../include/warp_rnnt_amd_tdt.h"
 #include "../../include/warp_rnnt_amd_tdt_align.h"
@@ -25,6 +27,7 @@
 #include "multiblank.h"
 #include "philox.h"
 #include "pruned.h"
+#include "pruned_joint.h"
 #include "simple.h"
 #include "tdt.h"
 #include "tdt_align.h"
@@ -255,6 +258,28 @@ MbWorkspace mb_layout(Carver& c, int N, int T, int U, int B) {
 // the shape of a multi-blank call: the loss's sizes, a lattice that fits one workgroup, B blanks and a label beside them
 inline bool mb_shape_ok(int dtype, int N, int T, int U, int V, int B) {
     return dtype_ok(dtype) && dims_ok(N, T, U) && U <= MB_MAX_U && B >= 1 && B <= MB_MAX_B && V >= B + 1 && V <= (1 << 24);
+}
+
+// The joint network fused into the pruned loss (pruned_joint.hip).  Behind the loss layout: d cost / d (f + g) of every
+// band row (N,T,S,H) in the call's dtype, W^T (H,Vp) in it, the weight kernel's fp32 partials (splits x Vp x H, splits x Vp).
+struct PrunedJointWorkspace {
+    void* dpre;
+    void* wt;
+    float* dw_part;
+    float* db_part;
+};
+PrunedJointWorkspace pruned_joint_layout(Carver& c, int dtype, int N, int T, int S, int H, int V) {
+    const size_t vp = (size_t)pruned_joint_vpad(V), splits = (size_t)pruned_joint_w_splits(dtype, N, T, S, H, V);
+    PrunedJointWorkspace pw;
+    pw.dpre = c.take<char>((size_t)N * T * S * H * dtype_size(dtype));
+    pw.wt = c.take<char>((size_t)H * vp * dtype_size(dtype));
+    pw.dw_part = c.take<float>(splits * vp * H);
+    pw.db_part = c.take<float>(splits * vp);
+    return pw;
+}
+inline bool pruned_joint_args_ok(int dtype, int activation, int N, int T, int U, int S, int H, int V, int blank) {
+    return joint_args_ok(dtype, activation, N, T, U, H, V, blank) && pruned_band_ok(N, T, U, S) &&
+           (int64_t)N * T < (int64_t)1 << 31;
 }
 
 }  // namespace
@@ -745,6 +770,65 @@ rnntStatus_t rnnt_amd_multiblank_logits_backward(rnntStream_t stream, int dtype,
     if (N == 0) return RNNT_STATUS_SUCCESS;
     if (launch_mb_logits_backward(stream, dtype, logits, labels, grads, grad_costs, dlogits, N, T, U, V,
                                   mb_blanks(blank_ids, nullptr, B)) != hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_pruned_joint.h: the joint network fused into the pruned loss.  rnnt_amd_pruned_loss_logits's shape
+// with pruned_joint.hip's MFMA producer in place of the streaming one: the floor over the plane, the band's pairs (and the
+// per-row statistics) over it, the standard sweeps and gradient pairs; the backward recomputes z.
+size_t rnnt_amd_pruned_joint_workspace_size(int dtype, int N, int T, int U, int S, int H, int V) {
+    if (!pruned_joint_args_ok(dtype, RNNT_ACT_TANH, N, T, U, S, H, V, 0)) return 0;
+    Carver c(nullptr);
+    loss_layout(c, N, T, U);
+    pruned_joint_layout(c, dtype, N, T, S, H, V);
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_pruned_joint_loss(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                        const void* g, const void* weight, const float* bias, const int* labels,
+                                        const int* starts, const int* xn, const int* yn, float* costs, float* stats,
+                                        float* grads, int N, int T, int U, int S, int H, int V, int blank,
+                                        float fastemit_lambda) {
+    if (!pruned_joint_args_ok(dtype, activation, N, T, U, S, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !f || !g || !weight || !starts || !xn || !yn || !costs || labels_missing(U, labels) ||
+        (grads && !stats))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!joint_inputs_aligned(f, g, weight, bias) || !aligned(stats, 8) || !aligned(grads, 8) || !aligned(costs, 4) ||
+        !aligned(labels, 4) || !aligned(starts, 4) || !aligned(xn, 4) || !aligned(yn, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const Workspace w = loss_layout(c, N, T, U);
+    if (launch_pruned_floor(stream, w.ws2, (size_t)N * T * U) != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
+    if (launch_pruned_joint_fwd(stream, dtype, activation, f, g, weight, bias, labels, starts, xn, yn, w.ws2,
+                                grads ? stats : nullptr, N, T, U, S, H, V, blank) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    return sweeps_and_pair_grads(stream, w, xn, yn, costs, grads ? grads : w.ws2, WRITE_SKEWED2, N, T, U, nullptr,
+                                 fastemit_lambda);
+}
+
+rnntStatus_t rnnt_amd_pruned_joint_backward(rnntStream_t stream, void* workspace, int dtype, int activation, const void* f,
+                                            const void* g, const void* weight, const float* bias, const int* labels,
+                                            const int* starts, const int* xn, const int* yn, const float* stats,
+                                            const float* grads, const float* grad_costs, void* df, void* dg,
+                                            float* dweight, float* dbias, int N, int T, int U, int S, int H, int V,
+                                            int blank) {
+    if (!pruned_joint_args_ok(dtype, activation, N, T, U, S, H, V, blank)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !f || !g || !weight || !starts || !xn || !yn || !stats || !grads ||
+        labels_missing(U, labels))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!joint_inputs_aligned(f, g, weight, bias) || !aligned(stats, 8) || !aligned(grads, 8) || !aligned(grad_costs, 4) ||
+        !aligned(df, 16) || !aligned(dg, 16) || !aligned(dweight, 4) || !aligned(dbias, 4) || !aligned(labels, 4) ||
+        !aligned(starts, 4) || !aligned(xn, 4) || !aligned(yn, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0 || (!df && !dg && !dweight && !dbias)) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    loss_layout(c, N, T, U);
+    const PrunedJointWorkspace pw = pruned_joint_layout(c, dtype, N, T, S, H, V);
+    if (launch_pruned_joint_bwd(stream, dtype, activation, f, g, weight, bias, labels, starts, xn, yn, stats, grads,
+                                grad_costs, pw.dpre, pw.wt, pw.dw_part, pw.db_part, df, dg, dweight, dbias, N, T, U, S, H,
+                                V, blank) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
 }

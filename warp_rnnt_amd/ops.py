@@ -994,6 +994,64 @@ def tdt_joint_backward(f, g, weight, bias, labels, xn, yn, stats, grads, grad_co
     return df, dg, dw, db
 
 
+def pruned_joint_loss(f, g, weight, bias, labels, starts, S, xn, yn, activation="tanh", blank=0, fastemit_lambda=0.0,
+                      with_grads=True):
+    """The joint network fused into the pruned loss (include/warp_rnnt_amd_pruned_joint.h): f (N,T,H), g (N,U,H), weight
+    (V,H) of one dtype (fp32 / bf16 / fp16), bias (V,) fp32 or None, starts (N,T) int32 contiguous and the band's width S;
+    validated by the caller.  Returns costs (N,) fp32 -- >= 1e29 for an utterance whose band holds no path -- and,
+    with_grads, stats (N,T,S,2) fp32 -- (max, log sum) of every band row's logits -- and the gradient pairs (N,T,U,2) of the
+    whole lattice in the diagonal-major layout -- what :func:`pruned_joint_backward` reads (else None, None)."""
+    L = _lib.load()
+    N, T, H = f.shape
+    U = g.shape[1]
+    V = weight.shape[0]
+    dev = f.device
+    _pruned_check(S, U, V, blank)
+    _mismatch.poll(dev)
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        stats = torch.empty((N, T, S, 2), dtype=torch.float32, device=dev) if with_grads else None
+        grads = torch.empty((N, T, U, 2), dtype=torch.float32, device=dev) if with_grads else None
+        if N == 0:
+            return costs, stats, grads
+        dt = LOGITS_DTYPES[f.dtype]
+        ws = _workspace(dev, L.rnnt_amd_pruned_joint_workspace_size, "dtype N T U S H V", dt, N, T, U, S, H, V)
+        _check(L.rnnt_amd_pruned_joint_loss(_stream(dev), ws.data_ptr(), dt, ACTIVATIONS[activation], f.data_ptr(),
+                                            g.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(labels), starts.data_ptr(),
+                                            xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(stats), _ptr(grads), N, T,
+                                            U, S, H, V, blank, float(fastemit_lambda)))
+    return costs, stats, grads
+
+
+def pruned_joint_backward(f, g, weight, bias, labels, starts, S, xn, yn, stats, grads, grad_costs, activation="tanh",
+                          blank=0, need_f=True, need_g=True, need_weight=True, need_bias=True):
+    """d(sum_n grad_costs[n]*cost[n]) / d(f, g, weight, bias) of :func:`pruned_joint_loss`: df / dg in f's dtype, dweight /
+    dbias fp32; None for what is not asked for.  An utterance with grad_costs[n] == 0 contributes exactly nothing."""
+    L = _lib.load()
+    N, T, H = f.shape
+    U = g.shape[1]
+    V = weight.shape[0]
+    dev = f.device
+    with torch.cuda.device(dev):
+        df = torch.empty_like(f) if need_f else None
+        dg = torch.empty_like(g) if need_g else None
+        dw = torch.empty((V, H), dtype=torch.float32, device=dev) if need_weight else None
+        db = torch.empty((V,), dtype=torch.float32, device=dev) if (need_bias and bias is not None) else None
+        if N == 0:
+            for t in (df, dg, dw, db):
+                if t is not None:
+                    t.zero_()
+            return df, dg, dw, db
+        dt = LOGITS_DTYPES[f.dtype]
+        ws = _workspace(dev, L.rnnt_amd_pruned_joint_workspace_size, "dtype N T U S H V", dt, N, T, U, S, H, V)
+        _check(L.rnnt_amd_pruned_joint_backward(_stream(dev), ws.data_ptr(), dt, ACTIVATIONS[activation], f.data_ptr(),
+                                                g.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(labels),
+                                                starts.data_ptr(), xn.data_ptr(), yn.data_ptr(), stats.data_ptr(),
+                                                grads.data_ptr(), _ptr(grad_costs), _ptr(df), _ptr(dg), _ptr(dw), _ptr(db),
+                                                N, T, U, S, H, V, blank))
+    return df, dg, dw, db
+
+
 def tdt_align(logits, labels, xn, yn, durations, blank=0, sigma=0.0):
     """Best-path alignments over the TDT lattice (include/warp_rnnt_amd_tdt_align.h): logits (N,T,U,V+D) as
     :func:`tdt_loss` takes them, validated by the caller.  Returns scores (N,) fp32 -- the log-probability of the best path,

@@ -33,16 +33,26 @@ and ``delay_penalty`` (Kang et al. 2022: ``delay_penalty * ((T_n - 1) / 2 - t)``
 lattice is the regular one over the sheared cells ``(t - u, u)``, whose diagonals are the frames: the sweeps, the gradient
 kernel, FastEmit and the guard run unchanged on a frame-major plane of ``T + 1`` rows.
 
-Out of scope: k2's ``constrained`` topology; a pruned form of HAT, TDT, the joint entries, the compact
-layout or ``rnnt_align``; the gradient clamp; a sweep that visits the band's cells only (the sweeps cost what the dense
-loss's do -- DESIGN.md 3.17 prices the alternative).
+The joiner itself can be part of the loss: :func:`pruned_rnnt_loss_from_joint` takes ``f``, ``g``, the starts and the
+joiner's output projection in place of the last two steps and forms the band's logits tile by tile in HIP (MFMA;
+csrc/pruned_joint.hip) -- no ``(N,T,S,V)`` logits, no ``(N,T,S,H)`` gather or activation and no autograd
+graph over them; the backward's workspace holds one ``(N,T,S,H)`` buffer::
+
+    loss = pruned_rnnt_loss_from_joint(f, g, joiner.output_linear.weight, joiner.output_linear.bias, labels, starts,
+                                       xn, yn, s_range=s_range, activation="tanh")
+
+Out of scope: k2's ``constrained`` topology; a pruned form of HAT, TDT, the compact layout or ``rnnt_align``; the gradient
+clamp; a sweep that visits the band's cells only (the sweeps cost what the dense loss's do -- DESIGN.md 3.17 prices the
+alternative).  Of the joint form: the two knobs of the streaming recipes above, dropout, a HIP ``prune_ranges``.
 """
+import math
 from typing import Optional
 
 import torch
 
 from . import ops
 from .fused import finish_costs
+from .joint import _aligned, check_joint_inputs
 from warp_rnnt import _C as _core
 
 NO_PATH_COST = 1e29      # the C entry's cost of an utterance whose band holds no path is at least this (sums of the floor)
@@ -269,3 +279,115 @@ def prune_joint_inputs(f: torch.Tensor, g: torch.Tensor, ranges: torch.Tensor, s
     idx = (starts.long()[..., None] + torch.arange(S, device=starts.device)).clamp(0, U - 1)          # (N,T,S)
     gp = g.gather(1, idx.reshape(N, T * S, 1).expand(N, T * S, H)).reshape(N, T, S, H)
     return f[:, :, None, :].expand(N, T, S, H), gp
+
+
+# ---- the joiner fused into the loss (csrc/pruned_joint.hip) ----
+
+class PrunedRNNTLossFromJoint(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, f, g, weight, bias, labels, starts, S, frames_lengths, labels_lengths, activation, blank,
+                fastemit_lambda, with_grads):
+        fc, gc = _aligned(f), _aligned(g)
+        w = _aligned(weight.to(fc.dtype))                        # W staged in the activations' dtype
+        b = bias.to(torch.float32).contiguous() if bias is not None else None
+        labels, xn, yn = labels.contiguous(), frames_lengths.contiguous(), labels_lengths.contiguous()
+        costs, stats, grads = ops.pruned_joint_loss(fc, gc, w, b, labels, starts, S, xn, yn, activation, blank,
+                                                    fastemit_lambda, with_grads)
+        no_path = costs >= NO_PATH_COST               # (on the device: nothing is read back)
+        if with_grads:
+            ctx.save_for_backward(fc, gc, w, b, labels, starts, xn, yn, stats, grads, no_path)
+        ctx.S, ctx.activation, ctx.blank = S, activation, blank
+        ctx.weight_dtype = weight.dtype
+        ctx.bias_dtype = bias.dtype if bias is not None else None
+        return torch.where(no_path, torch.full_like(costs, float("inf")), costs)
+
+    @staticmethod
+    def backward(ctx, grads_output):
+        f, g, w, b, labels, starts, xn, yn, stats, grads, no_path = ctx.saved_tensors
+        go = grads_output.reshape(-1).to(torch.float32)
+        go = torch.where(no_path, torch.zeros_like(go), go).contiguous()       # scale 0: the utterance adds exactly nothing
+        need = ctx.needs_input_grad
+        df, dg, dw, db = ops.pruned_joint_backward(f, g, w, b, labels, starts, ctx.S, xn, yn, stats, grads, go,
+                                                   ctx.activation, ctx.blank, need[0], need[1], need[2],
+                                                   need[3] and b is not None)
+        if dw is not None:
+            dw = dw.to(ctx.weight_dtype)
+        if db is not None:
+            db = db.to(ctx.bias_dtype)
+        return (df, dg, dw, db) + (None,) * 9
+
+
+def pruned_rnnt_loss_from_joint(f: torch.Tensor, g: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                                labels: torch.Tensor, ranges: torch.Tensor, frames_lengths: torch.Tensor,
+                                labels_lengths: torch.Tensor, activation: str = "tanh", blank: int = 0,
+                                fastemit_lambda: float = 0.0, average_frames: bool = False,
+                                reduction: Optional[str] = "none", *, s_range: Optional[int] = None,
+                                rnnt_type: str = "regular") -> torch.Tensor:
+    """The value of ``pruned_rnnt_loss_from_logits(F.linear(act(fp + gp), weight, bias), labels, ranges, ...)`` on
+    ``fp, gp = prune_joint_inputs(f, g, ranges, s_range)`` -- f ``(N,T,H)``, g ``(N,U,H)`` the projected encoder and
+    decoder outputs, weight ``(V,H)`` and bias ``(V,)`` or None as ``nn.Linear`` holds them, labels ``(N,U-1)``, act
+    ``"tanh"`` or ``"relu"`` -- and gradients to f, g, weight and bias, without an ``(N,T,S,V)`` tensor and without an
+    ``(N,T,S,H)`` activation or autograd tensor; the backward's workspace holds one ``(N,T,S,H)`` buffer.  Beyond the inputs
+    and the returned gradients a step holds at most the byte count of include/warp_rnnt_amd_pruned_joint.h -- the workspace,
+    8 bytes per band row, 8 per lattice cell -- plus the staged copy of a master weight (``V H`` elements of the activations'
+    dtype) and 64 KiB for the ``(N,)`` vectors.
+    ``ranges``: k2's ``(N,T,S)`` integer tensor (only ``[..., 0]`` is used) or the ``(N,T)`` starts with ``s_range=S``.
+
+    f and g share one dtype (fp32, bf16 or fp16); weight and bias may be fp32 or that dtype (an fp32 master weight is
+    staged in the activations' dtype).  act(f+g) is computed in fp32 and rounded once to that dtype as the matrix-core
+    operand; the logits stay fp32.  Costs are fp32; every gradient comes back in its parameter's dtype.  Supported:
+    H % 32 == 0, 32 <= H <= 1024, V >= 2, 1 <= S <= U.  Enqueue-only: the call can be captured into a graph.
+
+    Rows, masked columns (a bias of ``-inf``), an utterance whose band holds no path (``+inf``, exactly zero gradients,
+    the rest of the batch untouched) and the guard are those of :func:`pruned_rnnt_loss_from_logits`; frames
+    ``t >= frames_lengths[n]`` and positions behind ``labels_lengths[n]`` are not read.  Two runs give the same bits: no
+    atomics anywhere.
+
+    Not covered: ``rnnt_type`` other than ``"regular"`` (a ``ValueError``) and ``delay_penalty``, dropout, the gradient
+    clamp, HAT / TDT band forms, the compact layout."""
+    if rnnt_type != "regular":
+        raise ValueError(f"pruned_rnnt_loss_from_joint takes rnnt_type='regular' only, not {rnnt_type!r}: the modified "
+                         "topology and the delay penalty are served by pruned_rnnt_loss_from_logits")
+    assert reduction is None or reduction in ("none", "mean", "sum")
+    assert isinstance(blank, int)
+    if not isinstance(labels, torch.Tensor) or not isinstance(g, torch.Tensor) or labels.dim() != 2 or g.dim() != 3:
+        raise RuntimeError("labels must be (N,U-1) and g (N,U,H)")
+    if ranges.dim() == 3:
+        S = ranges.shape[2] if s_range is None else int(s_range)
+    elif s_range is None:
+        raise ValueError("pruned_rnnt_loss_from_joint needs s_range with ranges of shape (N,T)")
+    else:
+        S = int(s_range)
+    check_joint_inputs(f, g, weight, bias, labels, frames_lengths, labels_lengths, activation, blank)
+    starts = band_starts(ranges, S)
+    if tuple(starts.shape) != tuple(f.shape[:2]) or starts.device != f.device:
+        raise RuntimeError(f"ranges must be (N,T,S) or (N,T) for f (N,T,H) = {tuple(f.shape)}, on its device")
+    with_grads = torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (f, g, weight, bias))
+    costs = PrunedRNNTLossFromJoint.apply(f, g, weight, bias, labels, starts, S, frames_lengths, labels_lengths, activation,
+                                          blank, fastemit_lambda, with_grads)
+    return finish_costs(costs, frames_lengths, average_frames, reduction)
+
+
+class PrunedJointLoss(torch.nn.Module):
+    """The joiner's output projection and the pruned loss as one module -- ``activation -> Linear(hidden, vocab) -> pruned
+    loss`` on :func:`pruned_rnnt_loss_from_joint`: it owns ``weight`` (vocab, hidden) and ``bias``, initialised as
+    ``nn.Linear`` initialises them."""
+
+    def __init__(self, hidden: int, vocab: int, activation: str = "tanh", bias: bool = True, blank: int = 0,
+                 fastemit_lambda: float = 0.0, reduction: Optional[str] = "mean"):
+        super().__init__()
+        if activation not in ops.ACTIVATIONS:
+            raise ValueError(f"activation must be one of {tuple(ops.ACTIVATIONS)}, not {activation!r}")
+        self.hidden, self.vocab, self.activation = hidden, vocab, activation
+        self.blank, self.fastemit_lambda, self.reduction = blank, fastemit_lambda, reduction
+        self.weight = torch.nn.Parameter(torch.empty(vocab, hidden))
+        self.bias = torch.nn.Parameter(torch.empty(vocab)) if bias else None
+        torch.nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))      # (nn.Linear.reset_parameters)
+        if self.bias is not None:
+            torch.nn.init.uniform_(self.bias, -1 / math.sqrt(hidden), 1 / math.sqrt(hidden))
+
+    def forward(self, f, g, labels, ranges, frames_lengths, labels_lengths, s_range=None):
+        return pruned_rnnt_loss_from_joint(f, g, self.weight, self.bias, labels, ranges, frames_lengths, labels_lengths,
+                                           activation=self.activation, blank=self.blank,
+                                           fastemit_lambda=self.fastemit_lambda, reduction=self.reduction, s_range=s_range)
