@@ -8,7 +8,8 @@ Layout
   fused.py         rnnt_loss_from_logits: logits -> loss -> d/d logits, log-probabilities never in HBM
   hat.py           hat_loss_from_logits / HATLoss / hat_log_probs: the factorised-blank (HAT) loss on the same path
   pruned.py        pruned_rnnt_loss_from_logits / PrunedRNNTLoss: k2-style pruned loss, logits (N,T,S,V) on a band of S label
-                   positions per frame; simple_pairs / prune_ranges / prune_joint_inputs: the rest of that recipe
+                   positions per frame; simple_pairs / prune_ranges / prune_joint_inputs: the rest of that recipe;
+                   prune_ranges_hip: its band selection in HIP
   simple.py        simple_rnnt_loss / SimpleRNNTLoss / batch_log_unigram: that recipe's smoothed first pass over the trivial
                    joiner am + lm (k2's rnnt_loss_smoothed), an MFMA GEMM in front of the lattice, two behind it
   tdt.py           tdt_loss_from_logits / TDTLoss / tdt_log_probs: the token-and-duration (TDT) loss, a lattice of its own;

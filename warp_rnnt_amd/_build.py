@@ -16,10 +16,11 @@ LIB = os.path.join(HERE, "libwarp_rnnt_amd.so")
 SOURCES = ["api_loss.hip", "api_compact.hip", "api_reference.hip", "api_fused.hip", "lattice.hip", "lattice_ws.hip",
            "lattice_wd.hip", "grads.hip", "lsm_f32.hip", "lsm_bf16.hip", "lsm_f16.hip", "lsm_backward.hip", "to_diagonal.hip",
            "compact.hip", "expand.hip", "joint.hip", "hat.hip", "align.hip", "tdt.hip", "tdt_align.hip",
-           "tdt_joint.hip", "pruned.hip", "simple.hip", "multiblank.hip", "pruned_joint.hip"]
+           "tdt_joint.hip", "pruned.hip", "simple.hip", "multiblank.hip", "pruned_joint.hip", "prune_ranges.hip"]
 HEADERS = ["api_common.h", "common.h", "kernels.h", "lattice_plan.h", "lattice_launch.h", "lattice_step.h", "lattice_wd_body.h",
            "lattice_single.h", "grads_cell.h", "streaming.h", "lsm_plan.h", "lsm.h", "philox.h", "hat.h", "align.h", "row_chunks.h", "tdt.h", "tdt_align.h",
-           "joint_tile.h", "tdt_joint.h", "pruned.h", "simple.h", "multiblank.h", "pruned_joint.h",
+           "joint_tile.h", "tdt_joint.h", "pruned.h", "simple.h", "multiblank.h", "pruned_joint.h", "prune_ranges.h",
+           os.path.join("..", "..", "include", "warp_rnnt_amd_prune_ranges.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_pruned_joint.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_multiblank.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_topology.h"),
@@ -44,6 +45,10 @@ RELOAD_CHECKED = {"lattice_wd.hip": (8, 600)}
 # log-softmax units and to_diagonal.hip that is what they held before the blank-plane variants: four and two more now).
 HAZARD_CHECKED = {"lattice_wd.hip": 8, "lattice.hip": 4, "lattice_ws.hip": 2, "lsm_f32.hip": 132, "lsm_bf16.hip": 132,
                   "lsm_f16.hip": 132, "to_diagonal.hip": 8}
+
+# Flags of single sources, behind the common ones.  prune_ranges.hip: no packed fp32 arithmetic in the device code (the
+# host pass does not know the feature and says so) -- its occupancies are sums of float2 halves, each rounded on its own.
+UNIT_FLAGS = {"prune_ranges.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc():
@@ -112,7 +117,8 @@ def build(force=False, verbose=False, extra_flags=(), variant=None):
 
     srcs = [os.path.join(CSRC, x) for x in SOURCES]
     _isa_check.require_no_wide_asm_stores(srcs + hdrs)       # (cheap, every call: a rule on the source text)
-    fp = _fingerprint(srcs + hdrs + [_isa_check.__file__], flags)     # (a changed gate re-examines what it guards)
+    unit_flags = [f for src in sorted(UNIT_FLAGS) for f in [src] + UNIT_FLAGS[src]]
+    fp = _fingerprint(srcs + hdrs + [_isa_check.__file__], flags + unit_flags)   # (a changed gate re-examines what it guards)
     if not force and os.path.exists(lib) and _read(lib + ".fingerprint") == fp:
         # built from exactly these sources with exactly these flags: nothing to do, even when the object
         # files are absent and whatever the file times say (only the .so and this sidecar travel to the
@@ -128,7 +134,8 @@ def build(force=False, verbose=False, extra_flags=(), variant=None):
         if force or _stale(o, [s] + hdrs) or ((checked or hazard_checked) and _read(ok_mark) != fp):
             # (the files with hand-placed LDS reloads are compiled through their assembly text, -save-temps=obj, so that
             #  what is checked below is what is assembled into the object -- not a second compilation's output)
-            cmd = [hipcc] + flags + (["-save-temps=obj"] if (checked or hazard_checked) else []) + ["-c", s, "-o", o]
+            cmd = ([hipcc] + flags + UNIT_FLAGS.get(src, []) + (["-save-temps=obj"] if (checked or hazard_checked) else []) +
+                   ["-c", s, "-o", o])
             if verbose:
                 print(" ".join(cmd), flush=True)
             if os.path.exists(ok_mark):

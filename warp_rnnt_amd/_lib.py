@@ -213,6 +213,15 @@ PRUNED_JOINT_SYMBOLS = {
 }
 # behind ADDITIVE_TOPOLOGY, under the same contract; a tuple of its own for the same reason
 ADDITIVE_PRUNED_JOINT = ((PRUNED_JOINT_SYMBOLS, "warp_rnnt_amd_pruned_joint.h"),)
+# every symbol include/warp_rnnt_amd_prune_ranges.h declares (the band selection between the pruned recipe's two passes;
+# additive: it did not move the version): (stream, pair_grads, pitch, xn, yn, starts, N, T, U, S) with the pitch of an
+# utterance's pairs in cells, 64 bits, and no workspace
+PRUNE_RANGES_SYMBOLS = {
+    "rnnt_amd_prune_ranges": (_i, [_vp, _vp, _i64, _vp, _vp, _vp] + [_i] * 4),
+}
+# behind ADDITIVE_PRUNED_JOINT, under the same contract (tests/test_host_prune_ranges.py holds this one to it); a tuple of
+# its own for the same reason
+ADDITIVE_PRUNE_RANGES = ((PRUNE_RANGES_SYMBOLS, "warp_rnnt_amd_prune_ranges.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -251,7 +260,7 @@ def load():
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
     for table, header in (ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED + ADDITIVE_SIMPLE +
-                          ADDITIVE_MULTIBLANK + ADDITIVE_TOPOLOGY + ADDITIVE_PRUNED_JOINT):
+                          ADDITIVE_MULTIBLANK + ADDITIVE_TOPOLOGY + ADDITIVE_PRUNED_JOINT + ADDITIVE_PRUNE_RANGES):
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

@@ -8,11 +8,13 @@
 // gradient kernel all its own), its best-path alignments (include/warp_rnnt_amd_tdt_align.h) and the joint network fused
 // into it (include/warp_rnnt_amd_tdt_joint.h), the multi-blank loss (include/warp_rnnt_amd_multiblank.h: producer, sweeps
 // and gradient kernel all its own), the joint network fused into the pruned loss
-// (include/warp_rnnt_amd_pruned_joint.h).  Host-side orchestration only: argument checks, workspace carving, launches.
+// (include/warp_rnnt_amd_pruned_joint.h), the band selection between the recipe's two passes
+// (include/warp_rnnt_amd_prune_ranges.h).  Host-side orchestration only: argument checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd_align.h"
 #include "../../include/warp_rnnt_amd_hat.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
 #include "../../include/warp_rnnt_amd_multiblank.h"
+#include "../../include/warp_rnnt_amd_prune_ranges.h"
 #include "../../include/warp_rnnt_amd_pruned.h"
 #include "../../include/warp_rnnt_amd_pruned_joint.h"
 #include "../../include/warp_rnnt_amd_simple.h"
@@ -26,6 +28,7 @@
 #include "hat.h"
 #include "multiblank.h"
 #include "philox.h"
+#include "prune_ranges.h"
 #include "pruned.h"
 #include "pruned_joint.h"
 #include "simple.h"
@@ -830,6 +833,21 @@ rnntStatus_t rnnt_amd_pruned_joint_backward(rnntStream_t stream, void* workspace
                                 grad_costs, pw.dpre, pw.wt, pw.dw_part, pw.db_part, df, dg, dweight, dbias, N, T, U, S, H,
                                 V, blank) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_prune_ranges.h: the band selection of the pruned recipe, from rnnt_amd_simple_loss's pair_grads to
+// the starts the pruned entries above take.  Two launches of prune_ranges.hip, no workspace.
+rnntStatus_t rnnt_amd_prune_ranges(rnntStream_t stream, const float* pair_grads, int64_t pitch, const int* xn,
+                                   const int* yn, int* starts, int N, int T, int U, int S) {
+    if (!dims_ok(N, T, U) || S < 2 || S > U || U > PRUNE_RANGES_MAX_U || pitch < (int64_t)T * U)
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!pair_grads || !xn || !yn || !starts || !aligned(pair_grads, 8) || !aligned(xn, 4) || !aligned(yn, 4) ||
+        !aligned(starts, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    if (launch_prune_ranges(stream, pair_grads, pitch, xn, yn, starts, N, T, U, S) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
 

@@ -1052,6 +1052,26 @@ def pruned_joint_backward(f, g, weight, bias, labels, starts, S, xn, yn, stats, 
     return df, dg, dw, db
 
 
+def prune_ranges(pair_grads, xn, yn, S):
+    """The band selection of the pruned recipe (include/warp_rnnt_amd_prune_ranges.h): pair_grads (N,T,U,2) fp32 whose
+    last three dimensions are contiguous -- the batch stride is handed over as the per-utterance pitch, nothing is copied --
+    xn, yn (N,) int32 contiguous, 2 <= S <= U; validated by the caller.  Returns the starts (N,T) int32."""
+    L = _lib.load()
+    N, T, U, _ = pair_grads.shape
+    dev = pair_grads.device
+    if not 2 <= S <= U or T < 1:
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): prune_ranges needs T >= 1 and a band of "
+                           f"2 <= S <= U positions (T={T}, S={S}, U={U})")
+    pitch = pair_grads.stride(0) // 2 if N > 1 else T * U
+    with torch.cuda.device(dev):
+        starts = torch.empty((N, T), dtype=torch.int32, device=dev)
+        if N == 0:
+            return starts
+        _check(L.rnnt_amd_prune_ranges(_stream(dev), pair_grads.data_ptr(), pitch, xn.data_ptr(), yn.data_ptr(),
+                                       starts.data_ptr(), N, T, U, S))
+    return starts
+
+
 def tdt_align(logits, labels, xn, yn, durations, blank=0, sigma=0.0):
     """Best-path alignments over the TDT lattice (include/warp_rnnt_amd_tdt_align.h): logits (N,T,U,V+D) as
     :func:`tdt_loss` takes them, validated by the caller.  Returns scores (N,) fp32 -- the log-probability of the best path,

@@ -16,7 +16,7 @@ finite floor (-1e30) in the cells outside the band.
 The recipe, in three steps (tests/test_gpu_simple.py runs it end to end)::
 
     simple, pair_grads = simple_rnnt_loss(am, lm, labels, xn, yn, lm_only_scale=0.25, return_grad=True)    # the first pass
-    starts = prune_ranges(pair_grads, xn, yn, s_range)                     # (N,T) int32; pair_grads = -occupancies
+    starts = prune_ranges_hip(pair_grads, xn, yn, s_range)                 # (N,T) int32; pair_grads = -occupancies
     fp, gp = prune_joint_inputs(f, g, starts, s_range)                     # (N,T,S,H) twice
     loss   = pruned_rnnt_loss_from_logits(joiner(fp, gp), labels, starts, xn, yn)
     (simple_loss_scale * simple.sum() + loss.sum()).backward()
@@ -25,7 +25,8 @@ The recipe, in three steps (tests/test_gpu_simple.py runs it end to end)::
 holds the gradient pairs and hands them back with ``return_grad=True`` -- no ``requires_grad_`` on an intermediate tensor,
 no ``autograd.grad(..., retain_graph=True)``.  The plain-torch form of its pairs without the smoothing scales,
 ``simple_pairs`` below with ``warp_rnnt.rnnt_loss(pairs, labels, xn, yn, blank=-1)`` behind it, stays
-(tests/test_gpu_pruned.py runs the recipe on it).
+(tests/test_gpu_pruned.py runs the recipe on it).  :func:`prune_ranges_hip` (csrc/prune_ranges.hip) is
+:func:`prune_ranges`, the plain-torch definition for any device, in two HIP launches: one pass over the pairs.
 
 ``rnnt_type="modified"`` (k2's second topology: a label consumes a frame, at most one symbol per frame, no terminal blank)
 and ``delay_penalty`` (Kang et al. 2022: ``delay_penalty * ((T_n - 1) / 2 - t)`` added to the label log-probs of frame
@@ -43,7 +44,7 @@ graph over them; the backward's workspace holds one ``(N,T,S,H)`` buffer::
 
 Out of scope: k2's ``constrained`` topology; a pruned form of HAT, TDT, the compact layout or ``rnnt_align``; the gradient
 clamp; a sweep that visits the band's cells only (the sweeps cost what the dense loss's do -- DESIGN.md 3.17 prices the
-alternative).  Of the joint form: the two knobs of the streaming recipes above, dropout, a HIP ``prune_ranges``.
+alternative).  Of the joint form: the two knobs of the streaming recipes above, dropout.
 """
 import math
 from typing import Optional
@@ -194,7 +195,8 @@ class PrunedRNNTLoss(torch.nn.Module):
                                             delay_penalty=self.delay_penalty)
 
 
-# ---- the rest of the recipe: plain torch on any device, not a hot path, no Python loop over N or T, no read-back ----
+# ---- the rest of the recipe: plain torch on any device, no Python loop over N or T, no read-back; prune_ranges_hip is the
+# ---- band selection on the GPU, prune_ranges its definition ----
 
 def simple_pairs(am: torch.Tensor, lm: torch.Tensor, labels: torch.Tensor, blank: int = 0) -> torch.Tensor:
     """The ``(N,T,U,2)`` (blank, label) log-probability pairs of the trivial joiner ``log_softmax(am[n,t,:] + lm[n,u,:])``
@@ -257,6 +259,56 @@ def prune_ranges(pair_grads: torch.Tensor, frames_lengths: torch.Tensor, labels_
     ramp = t * (S - 1)
     start = (start - ramp).flip(1).cummax(dim=1).values.flip(1) + ramp
     return start.to(torch.int32)
+
+
+def prune_ranges_hip(pair_grads: torch.Tensor, frames_lengths: torch.Tensor, labels_lengths: torch.Tensor,
+                     s_range: int) -> torch.Tensor:
+    """:func:`prune_ranges` in HIP (csrc/prune_ranges.hip): the same arguments, the ``(N,T)`` int32 starts
+    from one pass over the pairs and one over the ``(N,T)`` ints instead of about fifteen torch operations over
+    ``(N,T,U)`` temporaries.  ``pair_grads`` is fp32 on the GPU, the lengths int32 on its device.  Its last three dimensions
+    must be contiguous, its batch stride is free -- the ``(N,T,U,2)`` view of the modified topology's ``(N,T+1,U,2)`` pairs
+    is read as it is; any other striding costs one ``.contiguous()``.  ``U <= 4096``.  Enqueue-only: no read-back, no host
+    synchronisation, the call can be captured into a graph; no atomics, two runs give the same starts.
+
+    Per utterance, with ``occ = -(pair_grads[..., 0] + pair_grads[..., 1])`` and ``hi = clamp(U_n + 1 - S, 0, U - S)``:
+    for ``t < T_n - 1`` the lowest ``u0`` in ``[0, hi]`` at which ``w(t,u0) = occ[t,u0] + ... + occ[t,u0+S-1]`` is largest
+    -- ``hi`` if an ``occ[t,u]`` with ``u < hi + S`` is a NaN -- and ``hi`` for ``t >= T_n - 1``, whatever ``T_n`` is; then
+    the two backward scans of :func:`prune_ranges`.  ``s_range >= U``: all zeros.  Cells ``u >= hi + S`` and frames
+    ``t >= T_n - 1`` are not read.
+
+    ``w`` is added left to right from ``u0``, each sum rounded to fp32 on its own: a function of ``S``, ``u0`` and the
+    window's values alone, so an utterance's starts do not depend on ``U``'s padding, on ``T`` or on its place in the batch.
+    :func:`prune_ranges` forms ``w`` as a difference of two ``cumsum`` values instead, so on real-valued data the two may
+    choose differently between windows whose sums agree to within rounding; where every partial sum is exact in fp32
+    (occupancies on a dyadic grid) they return the same starts, ties included."""
+    S = int(s_range)
+    if S < 2:
+        raise ValueError(f"s_range must be >= 2, not {s_range}")
+    xn, yn = frames_lengths, labels_lengths
+    if pair_grads.dtype != torch.float32:
+        raise RuntimeError(f"pair_grads must be a float32 tensor, not {pair_grads.dtype}")
+    for x, name in ((xn, "xn"), (yn, "yn")):
+        _core._check_int(x, name)
+    for x, name in ((pair_grads, "pair_grads"), (xn, "xn"), (yn, "yn")):
+        _core._check_cuda(x, name)
+    if pair_grads.dim() != 4 or pair_grads.size(3) != 2:
+        raise RuntimeError("pair_grads must be (N,T,U,2)")
+    N, T, U, _ = pair_grads.shape
+    if xn.numel() != N:
+        raise RuntimeError("xn shape must be equal (N,)")
+    if yn.numel() != N:
+        raise RuntimeError("yn shape must be equal (N,)")
+    for x, name in ((xn, "xn"), (yn, "yn")):
+        if x.device != pair_grads.device:
+            raise RuntimeError(f"{name} must be on the same device as pair_grads")
+    if S >= U or T == 0:
+        return torch.zeros((N, T), dtype=torch.int32, device=pair_grads.device)
+    g = pair_grads.detach()
+    # the entry reads 8-byte cells at n * pitch + t * U + u: rows and cells contiguous, planes apart and on whole cells
+    if (g.stride()[1:] != (2 * U, 2, 1) or g.data_ptr() % 8 or
+            (N > 1 and (g.stride(0) < 2 * T * U or g.stride(0) % 2))):
+        g = g.contiguous()
+    return ops.prune_ranges(g, xn.contiguous(), yn.contiguous(), S)
 
 
 def prune_joint_inputs(f: torch.Tensor, g: torch.Tensor, ranges: torch.Tensor, s_range: Optional[int] = None):
