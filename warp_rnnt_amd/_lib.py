@@ -222,6 +222,16 @@ PRUNE_RANGES_SYMBOLS = {
 # behind ADDITIVE_PRUNED_JOINT, under the same contract (tests/test_host_prune_ranges.py holds this one to it); a tuple of
 # its own for the same reason
 ADDITIVE_PRUNE_RANGES = ((PRUNE_RANGES_SYMBOLS, "warp_rnnt_amd_prune_ranges.h"),)
+# every symbol include/warp_rnnt_amd_pruned_hat.h declares (the factorised-blank loss on the pruned band; additive: it did
+# not move the version): the argument lists of the two ..._topology pruned entries, the workspace of
+# rnnt_amd_pruned_topology_workspace_size
+PRUNED_HAT_SYMBOLS = {
+    "rnnt_amd_pruned_hat_loss_logits": (_i, TOPOLOGY_SYMBOLS["rnnt_amd_pruned_loss_logits_topology"][1]),
+    "rnnt_amd_pruned_hat_logits_backward": (_i, TOPOLOGY_SYMBOLS["rnnt_amd_pruned_logits_backward_topology"][1]),
+}
+# behind ADDITIVE_PRUNE_RANGES, under the same contract (tests/test_host_pruned_hat.py holds this one to it); a tuple of
+# its own for the same reason
+ADDITIVE_PRUNED_HAT = ((PRUNED_HAT_SYMBOLS, "warp_rnnt_amd_pruned_hat.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -260,7 +270,8 @@ def load():
                            f"{ABI_VERSION}: rebuild it (`python warp_rnnt_amd/_build.py`)")
     # additive entries do not move the version: a library built before them has to be told apart by its exports
     for table, header in (ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED + ADDITIVE_SIMPLE +
-                          ADDITIVE_MULTIBLANK + ADDITIVE_TOPOLOGY + ADDITIVE_PRUNED_JOINT + ADDITIVE_PRUNE_RANGES):
+                          ADDITIVE_MULTIBLANK + ADDITIVE_TOPOLOGY + ADDITIVE_PRUNED_JOINT + ADDITIVE_PRUNE_RANGES +
+                          ADDITIVE_PRUNED_HAT):
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

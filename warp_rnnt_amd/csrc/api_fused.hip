@@ -16,6 +16,7 @@
 #include "../../include/warp_rnnt_amd_multiblank.h"
 #include "../../include/warp_rnnt_amd_prune_ranges.h"
 #include "../../include/warp_rnnt_amd_pruned.h"
+#include "../../include/warp_rnnt_amd_pruned_hat.h"
 #include "../../include/warp_rnnt_amd_pruned_joint.h"
 #include "../../include/warp_rnnt_amd_simple.h"
 #include "../../include/warp_rnnt_amd_tdt.h"
@@ -30,6 +31,7 @@
 #include "philox.h"
 #include "prune_ranges.h"
 #include "pruned.h"
+#include "pruned_hat.h"
 #include "pruned_joint.h"
 #include "simple.h"
 #include "tdt.h"
@@ -389,10 +391,11 @@ rnntStatus_t rnnt_amd_hat_logits_backward(rnntStream_t stream, int dtype, const 
 // standard ones over the (N,T,U) grid; the backward is one streaming launch over the (N,T,S,V) logits.
 // include/warp_rnnt_amd_topology.h: the same with a topology and a delay penalty.  RNNT_TOPOLOGY_REGULAR with
 // delay_penalty == 0 IS the entry without them.
-rnntStatus_t rnnt_amd_pruned_loss_logits_topology(rnntStream_t stream, void* workspace, int dtype, const void* logits,
-                                                  const int* labels, const int* starts, const int* xn, const int* yn,
-                                                  float* costs, float* grads, int N, int T, int U, int S, int V, int blank,
-                                                  float fastemit_lambda, int topology, float delay_penalty) {
+// (hat: HAT's pair in the band's cells, pruned_hat.hip -- include/warp_rnnt_amd_pruned_hat.h; everything else is the same)
+static rnntStatus_t pruned_loss_entry(bool hat, rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                      const int* labels, const int* starts, const int* xn, const int* yn, float* costs,
+                                      float* grads, int N, int T, int U, int S, int V, int blank, float fastemit_lambda,
+                                      int topology, float delay_penalty) {
     if (!topology_ok(topology, delay_penalty) || !dtype_ok(dtype) || !topology_dims_ok(topology, N, T, U) || V < 2 ||
         !vocab_ok(V, blank) || !pruned_band_ok(N, T, U, S))
         return RNNT_STATUS_INVALID_ARGUMENT;
@@ -401,11 +404,28 @@ rnntStatus_t rnnt_amd_pruned_loss_logits_topology(rnntStream_t stream, void* wor
     if (N == 0) return RNNT_STATUS_SUCCESS;
     Carver c(workspace);
     const TopologyWorkspace tw = topology_layout(c, topology, N, T, U);
-    if (launch_pruned_pairs(stream, dtype, logits, labels, starts, xn, yn, tw.w.ws2, N, T, U, S, V, blank, topology,
-                            delay_penalty) != hipSuccess)
+    const auto pairs = hat ? launch_pruned_hat_pairs : launch_pruned_pairs;
+    if (pairs(stream, dtype, logits, labels, starts, xn, yn, tw.w.ws2, N, T, U, S, V, blank, topology, delay_penalty) !=
+        hipSuccess)
         return RNNT_STATUS_PROLOGUE_FAILED;
     return topology_sweeps(stream, tw, topology, xn, yn, costs, grads ? grads : tw.w.ws2, WRITE_SKEWED2, false, N, T, U,
                            fastemit_lambda);
+}
+
+rnntStatus_t rnnt_amd_pruned_loss_logits_topology(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                                  const int* labels, const int* starts, const int* xn, const int* yn,
+                                                  float* costs, float* grads, int N, int T, int U, int S, int V, int blank,
+                                                  float fastemit_lambda, int topology, float delay_penalty) {
+    return pruned_loss_entry(false, stream, workspace, dtype, logits, labels, starts, xn, yn, costs, grads, N, T, U, S, V,
+                             blank, fastemit_lambda, topology, delay_penalty);
+}
+
+rnntStatus_t rnnt_amd_pruned_hat_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                             const int* labels, const int* starts, const int* xn, const int* yn,
+                                             float* costs, float* grads, int N, int T, int U, int S, int V, int blank,
+                                             float fastemit_lambda, int topology, float delay_penalty) {
+    return pruned_loss_entry(true, stream, workspace, dtype, logits, labels, starts, xn, yn, costs, grads, N, T, U, S, V,
+                             blank, fastemit_lambda, topology, delay_penalty);
 }
 
 rnntStatus_t rnnt_amd_pruned_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits,
@@ -416,10 +436,10 @@ rnntStatus_t rnnt_amd_pruned_loss_logits(rnntStream_t stream, void* workspace, i
                                                 U, S, V, blank, fastemit_lambda, RNNT_TOPOLOGY_REGULAR, 0.0f);
 }
 
-rnntStatus_t rnnt_amd_pruned_logits_backward_topology(rnntStream_t stream, int dtype, const void* logits,
-                                                      const int* labels, const int* starts, const int* xn, const int* yn,
-                                                      const float* grads_diagonal, const float* grad_costs, void* dlogits,
-                                                      int N, int T, int U, int S, int V, int blank, int topology) {
+static rnntStatus_t pruned_backward_entry(bool hat, rnntStream_t stream, int dtype, const void* logits, const int* labels,
+                                          const int* starts, const int* xn, const int* yn, const float* grads_diagonal,
+                                          const float* grad_costs, void* dlogits, int N, int T, int U, int S, int V,
+                                          int blank, int topology) {
     if (!topology_ok(topology, 0.0f) || !dtype_ok(dtype) || !topology_dims_ok(topology, N, T, U) || V < 2 ||
         !vocab_ok(V, blank) || !pruned_band_ok(N, T, U, S))
         return RNNT_STATUS_INVALID_ARGUMENT;
@@ -427,10 +447,27 @@ rnntStatus_t rnnt_amd_pruned_logits_backward_topology(rnntStream_t stream, int d
         (topology == RNNT_TOPOLOGY_MODIFIED && (!xn || !yn)))
         return RNNT_STATUS_INVALID_ARGUMENT;
     if (N == 0) return RNNT_STATUS_SUCCESS;
-    if (launch_pruned_logits_backward(stream, dtype, logits, labels, starts, xn, yn, grads_diagonal, grad_costs, dlogits, N,
-                                      T, U, S, V, blank, topology) != hipSuccess)
+    const auto backward = hat ? launch_pruned_hat_logits_backward : launch_pruned_logits_backward;
+    if (backward(stream, dtype, logits, labels, starts, xn, yn, grads_diagonal, grad_costs, dlogits, N, T, U, S, V, blank,
+                 topology) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_pruned_logits_backward_topology(rnntStream_t stream, int dtype, const void* logits,
+                                                      const int* labels, const int* starts, const int* xn, const int* yn,
+                                                      const float* grads_diagonal, const float* grad_costs, void* dlogits,
+                                                      int N, int T, int U, int S, int V, int blank, int topology) {
+    return pruned_backward_entry(false, stream, dtype, logits, labels, starts, xn, yn, grads_diagonal, grad_costs, dlogits,
+                                 N, T, U, S, V, blank, topology);
+}
+
+rnntStatus_t rnnt_amd_pruned_hat_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* labels,
+                                                 const int* starts, const int* xn, const int* yn,
+                                                 const float* grads_diagonal, const float* grad_costs, void* dlogits, int N,
+                                                 int T, int U, int S, int V, int blank, int topology) {
+    return pruned_backward_entry(true, stream, dtype, logits, labels, starts, xn, yn, grads_diagonal, grad_costs, dlogits, N,
+                                 T, U, S, V, blank, topology);
 }
 
 rnntStatus_t rnnt_amd_pruned_logits_backward(rnntStream_t stream, int dtype, const void* logits, const int* labels,

@@ -23,51 +23,6 @@
 namespace rnnt {
 namespace {
 
-// Where row `row` of (N,T,S) lies in the lattice.  live: u in [0,U) -- starts is device data nobody validated, and the sum
-// is formed in 64 bits so that no start wraps into the grid
-//
-// TOPO_MODIFIED (pruned.h): the plane has T + 1 rows per utterance and is frame-major, cell (t,u) at ((n (T+1) + t) U + u) --
-// the diagonal-major address of cell (t' = t - u, u) of the sheared lattice.  live: also t < xn[n], t >= u, u <= yn[n], the
-// cells a path can reach -- row (t = T_n, u = U_n) of a padding frame has the address of the virtual terminal cell.
-struct BandCell {
-    size_t sk;      // float2 index into the diagonal-major plane
-    int label;      // vocabulary index of the label channel (the blank in the last column and for a label outside [0,V))
-    int n;
-    int t;
-    bool live;
-};
-template <int TOPO>
-__device__ __forceinline__ BandCell band_cell(size_t row, const int* __restrict__ labels, const int* __restrict__ starts,
-                                              const int* __restrict__ xn, const int* __restrict__ yn, int T, int U, int S,
-                                              int V, int blank) {
-    // N*T*S < 2^32 is checked by the C ABI, so 32-bit divisions are enough
-    const unsigned r32 = (unsigned)row;
-    const unsigned frame = r32 / (unsigned)S;          // n*T + t
-    const int s = (int)(r32 - frame * (unsigned)S);
-    const unsigned n = frame / (unsigned)T;
-    const int t = (int)(frame - n * (unsigned)T);
-    const long long u64 = (long long)starts[frame] + s;
-    BandCell c;
-    c.n = (int)n;
-    c.t = t;
-    c.live = u64 >= 0 && u64 < (long long)U;
-    c.sk = 0;
-    c.label = blank;
-    if constexpr (TOPO == TOPO_MODIFIED) c.live = c.live && t < xn[n] && (long long)t >= u64 && u64 <= (long long)yn[n];
-    if (c.live) {
-        const int u = (int)u64;
-        if constexpr (TOPO == TOPO_MODIFIED) {
-            c.sk = ((size_t)n * (T + 1) + t) * (size_t)U + u;
-        } else {
-            int r = t + u;
-            r = r >= T ? r % T : r;
-            c.sk = ((size_t)n * T + r) * (size_t)U + u;
-        }
-        if (u < U - 1) c.label = safe_label(labels[(size_t)n * (U - 1) + u], V, blank);
-    }
-    return c;
-}
-
 // PEN: the label channel of frame t gets dp (0.5 (T_n - 1) - t) added, fp32: the bracket, one multiply, one add
 template <typename E, int G, int ACC, int TOPO, bool PEN>
 __global__ void __launch_bounds__(ROW_THREADS)

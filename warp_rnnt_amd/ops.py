@@ -712,17 +712,19 @@ def topology_of(rnnt_type, delay_penalty):
     return RNNT_TYPES[rnnt_type], dp
 
 
-def with_topology_keywords(positional, full):
+def with_topology_keywords(positional, full, **more):
     """``positional`` -- a front end as it is documented and introspected, its positional signature unchanged -- taking
     the keyword-only ``rnnt_type`` and ``delay_penalty`` as well: ``full`` is called with ``positional``'s arguments, bound
-    and with their defaults, and the two keywords behind them."""
+    and with their defaults, and the two keywords behind them.  ``more``: further keyword-only arguments of ``full`` with
+    their defaults (``use_hat_loss=False`` of the pruned loss)."""
     signature = inspect.signature(positional)
 
     @functools.wraps(positional)
     def front(*args, rnnt_type="regular", delay_penalty=0.0, **kwargs):
+        extra = {name: kwargs.pop(name, default) for name, default in more.items()}
         bound = signature.bind(*args, **kwargs)
         bound.apply_defaults()
-        return full(*bound.args, rnnt_type=rnnt_type, delay_penalty=delay_penalty)
+        return full(*bound.args, rnnt_type=rnnt_type, delay_penalty=delay_penalty, **extra)
     return front
 
 
@@ -763,6 +765,47 @@ def pruned_logits_backward_topology(logits, labels, starts, xn, yn, grads, grad_
         if N == 0:
             return out
         _check(L.rnnt_amd_pruned_logits_backward_topology(
+            _stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(), _ptr(labels), starts.data_ptr(), xn.data_ptr(),
+            yn.data_ptr(), grads.data_ptr(), _ptr(grad_costs), out.data_ptr(), N, T, U, S, V, blank, topology))
+    return out
+
+
+def pruned_hat_loss(logits, labels, starts, xn, yn, blank=0, fastemit_lambda=0.0, with_grads=True,
+                    topology=_lib.TOPOLOGY_REGULAR, delay_penalty=0.0):
+    """:func:`pruned_loss_topology` with the factorised-blank (HAT) pair in the band's cells
+    (include/warp_rnnt_amd_pruned_hat.h, csrc/pruned_hat.hip): the same arguments, the same costs and gradient pairs --
+    what :func:`pruned_hat_logits_backward` reads."""
+    L = _lib.load()
+    N, T, S, V = logits.shape
+    U = labels.shape[1] + 1
+    dev = logits.device
+    _pruned_check(S, U, V, blank)
+    _mismatch.poll(dev)
+    frames = T + 1 if topology == _lib.TOPOLOGY_MODIFIED else T
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        grads = torch.empty((N, frames, U, 2), dtype=torch.float32, device=dev) if with_grads else None
+        if N == 0:
+            return costs, grads
+        ws = _workspace(dev, lambda n, t, u: L.rnnt_amd_pruned_topology_workspace_size(topology, n, t, u), "N T U", N, T, U)
+        _check(L.rnnt_amd_pruned_hat_loss_logits(
+            _stream(dev), ws.data_ptr(), LOGITS_DTYPES[logits.dtype], logits.data_ptr(), _ptr(labels), starts.data_ptr(),
+            xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), _ptr(grads), N, T, U, S, V, blank, float(fastemit_lambda),
+            topology, float(delay_penalty)))
+    return costs, grads
+
+
+def pruned_hat_logits_backward(logits, labels, starts, xn, yn, grads, grad_costs, blank=0, topology=_lib.TOPOLOGY_REGULAR):
+    """:func:`pruned_logits_backward_topology` of :func:`pruned_hat_loss`: HAT's chain rule, the same exactly zero rows."""
+    L = _lib.load()
+    N, T, S, V = logits.shape
+    U = labels.shape[1] + 1
+    dev = logits.device
+    with torch.cuda.device(dev):
+        out = torch.empty_like(logits)
+        if N == 0:
+            return out
+        _check(L.rnnt_amd_pruned_hat_logits_backward(
             _stream(dev), LOGITS_DTYPES[logits.dtype], logits.data_ptr(), _ptr(labels), starts.data_ptr(), xn.data_ptr(),
             yn.data_ptr(), grads.data_ptr(), _ptr(grad_costs), out.data_ptr(), N, T, U, S, V, blank, topology))
     return out

@@ -42,7 +42,10 @@ graph over them; the backward's workspace holds one ``(N,T,S,H)`` buffer::
     loss = pruned_rnnt_loss_from_joint(f, g, joiner.output_linear.weight, joiner.output_linear.bias, labels, starts,
                                        xn, yn, s_range=s_range, activation="tanh")
 
-Out of scope: k2's ``constrained`` topology; a pruned form of HAT, TDT, the compact layout or ``rnnt_align``; the gradient
+``use_hat_loss=True`` (k2's argument; icefall's ``zipformer_hat``) puts the factorised-blank (HAT) log-probs of
+``hat_loss_from_logits`` into the band's cells: csrc/pruned_hat.hip, DESIGN.md 3.23.
+
+Out of scope: k2's ``constrained`` topology; a pruned form of TDT, the compact layout or ``rnnt_align``; the gradient
 clamp; a sweep that visits the band's cells only (the sweeps cost what the dense loss's do -- DESIGN.md 3.17 prices the
 alternative).  Of the joint form: the two knobs of the streaming recipes above, dropout.
 """
@@ -104,12 +107,16 @@ class PrunedRNNTLossFromLogits(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, starts, frames_lengths, labels_lengths, blank=0, fastemit_lambda=0.0,
-                topology=ops.RNNT_TYPES["regular"], delay_penalty=0.0):
+                topology=ops.RNNT_TYPES["regular"], delay_penalty=0.0, hat=False):
         check_pruned_inputs(logits, labels, starts, frames_lengths, labels_lengths)
         wants_grad = ctx.needs_input_grad[0]          # (nothing requires grad: no pairs are produced or kept)
         # the defaults are the entries without a topology: the calls, and so the bits, of every earlier version
-        ctx.plain = topology == ops.RNNT_TYPES["regular"] and delay_penalty == 0.0
-        if ctx.plain:
+        ctx.plain = topology == ops.RNNT_TYPES["regular"] and delay_penalty == 0.0 and not hat
+        ctx.hat = hat
+        if hat:                                       # (one pair of entries: the topology and the penalty are arguments)
+            costs, grads = ops.pruned_hat_loss(logits, labels, starts, frames_lengths, labels_lengths, blank,
+                                               fastemit_lambda, wants_grad, topology, delay_penalty)
+        elif ctx.plain:
             costs, grads = ops.pruned_loss(logits, labels, starts, frames_lengths, labels_lengths, blank, fastemit_lambda,
                                            wants_grad)
         else:
@@ -127,9 +134,9 @@ class PrunedRNNTLossFromLogits(torch.autograd.Function):
         go = grads_output.reshape(-1).to(torch.float32)
         go = torch.where(no_path, torch.zeros_like(go), go).contiguous()       # scale 0: exactly zero rows, pairs unread
         if ctx.plain:
-            return (ops.pruned_logits_backward(logits, labels, starts, grads, go, ctx.blank),) + (None,) * 8
-        return (ops.pruned_logits_backward_topology(logits, labels, starts, xn, yn, grads, go, ctx.blank,
-                                                    ctx.topology),) + (None,) * 8
+            return (ops.pruned_logits_backward(logits, labels, starts, grads, go, ctx.blank),) + (None,) * 9
+        backward = ops.pruned_hat_logits_backward if ctx.hat else ops.pruned_logits_backward_topology
+        return (backward(logits, labels, starts, xn, yn, grads, go, ctx.blank, ctx.topology),) + (None,) * 9
 
 
 def pruned_rnnt_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, ranges: torch.Tensor,
@@ -155,31 +162,38 @@ def pruned_rnnt_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, ran
     ``alpha(t,u) = lse(alpha(t-1,u) + lpB(t-1,u), alpha(t-1,u-1) + lpL(t-1,u-1))``; an utterance with ``T_n < U_n`` has
     no path); another string is a ``ValueError`` (``"constrained"`` is not covered).  ``delay_penalty >= 0`` adds
     ``delay_penalty * ((T_n - 1) / 2 - t)`` to the label log-prob of every cell of frame ``t`` (fp32), as k2 does.  With
-    ``"modified"`` rows of frames ``t >= frames_lengths[n]`` are never read, whatever their starts are."""
+    ``"modified"`` rows of frames ``t >= frames_lengths[n]`` are never read, whatever their starts are.
+
+    A third, ``use_hat_loss=False`` (k2's argument of that name; icefall's ``zipformer_hat``): with ``True`` the band's
+    cells hold the factorised-blank (HAT) log-probs of ``hat_loss_from_logits`` -- ``log sigmoid(z[blank])`` for the blank,
+    ``log_softmax`` over the non-blank logits plus ``log(1 - sigmoid(z[blank]))`` for a label -- and the gradient follows
+    HAT's chain rule (csrc/pruned_hat.hip); everything else above holds, both topologies and the delay
+    penalty included.  With ``S = U``, zero starts and ``"regular"`` the costs and gradients are ``hat_loss_from_logits``'
+    bit for bit.  ``False`` makes exactly the calls it made before the argument existed."""
     return _pruned_loss(logits, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank,
                         fastemit_lambda)
 
 
 def _pruned_loss(logits, labels, ranges, frames_lengths, labels_lengths, average_frames, reduction, blank, fastemit_lambda,
-                 rnnt_type="regular", delay_penalty=0.0):
+                 rnnt_type="regular", delay_penalty=0.0, use_hat_loss=False):
     topology, delay_penalty = ops.topology_of(rnnt_type, delay_penalty)
     assert reduction is None or reduction in ("none", "mean", "sum")
     assert isinstance(blank, int)
     starts = band_starts(ranges, logits.shape[2] if logits.dim() == 4 else None)
     costs = PrunedRNNTLossFromLogits.apply(logits, labels, starts, frames_lengths, labels_lengths, blank, fastemit_lambda,
-                                           topology, delay_penalty)
+                                           topology, delay_penalty, bool(use_hat_loss))
     return finish_costs(costs, frames_lengths, average_frames, reduction)
 
 
-pruned_rnnt_loss_from_logits = ops.with_topology_keywords(pruned_rnnt_loss_from_logits, _pruned_loss)
+pruned_rnnt_loss_from_logits = ops.with_topology_keywords(pruned_rnnt_loss_from_logits, _pruned_loss, use_hat_loss=False)
 
 
 class PrunedRNNTLoss(torch.nn.Module):
     """:func:`pruned_rnnt_loss_from_logits` as a module: stores ``blank``, ``fastemit_lambda``, ``reduction``,
-    ``rnnt_type`` and ``delay_penalty``."""
+    ``rnnt_type``, ``delay_penalty`` and ``use_hat_loss``."""
 
     def __init__(self, blank: int = 0, fastemit_lambda: float = 0.0, reduction: Optional[str] = "mean",
-                 rnnt_type: str = "regular", delay_penalty: float = 0.0):
+                 rnnt_type: str = "regular", delay_penalty: float = 0.0, use_hat_loss: bool = False):
         super().__init__()
         ops.topology_of(rnnt_type, delay_penalty)
         self.blank = blank
@@ -187,12 +201,13 @@ class PrunedRNNTLoss(torch.nn.Module):
         self.reduction = reduction
         self.rnnt_type = rnnt_type
         self.delay_penalty = delay_penalty
+        self.use_hat_loss = use_hat_loss
 
     def forward(self, logits, labels, ranges, frames_lengths, labels_lengths):
         return pruned_rnnt_loss_from_logits(logits, labels, ranges, frames_lengths, labels_lengths,
                                             reduction=self.reduction, blank=self.blank,
                                             fastemit_lambda=self.fastemit_lambda, rnnt_type=self.rnnt_type,
-                                            delay_penalty=self.delay_penalty)
+                                            delay_penalty=self.delay_penalty, use_hat_loss=self.use_hat_loss)
 
 
 # ---- the rest of the recipe: plain torch on any device, no Python loop over N or T, no read-back; prune_ranges_hip is the
@@ -397,7 +412,8 @@ def pruned_rnnt_loss_from_joint(f: torch.Tensor, g: torch.Tensor, weight: torch.
     atomics anywhere.
 
     Not covered: ``rnnt_type`` other than ``"regular"`` (a ``ValueError``) and ``delay_penalty``, dropout, the gradient
-    clamp, HAT / TDT band forms, the compact layout."""
+    clamp, the compact layout, TDT band forms, and ``use_hat_loss``: HAT inside the MFMA joiner is out of scope -- form the
+    band's logits and call ``pruned_rnnt_loss_from_logits(..., use_hat_loss=True)``."""
     if rnnt_type != "regular":
         raise ValueError(f"pruned_rnnt_loss_from_joint takes rnnt_type='regular' only, not {rnnt_type!r}: the modified "
                          "topology and the delay penalty are served by pruned_rnnt_loss_from_logits")
