@@ -232,6 +232,18 @@ PRUNED_HAT_SYMBOLS = {
 # behind ADDITIVE_PRUNE_RANGES, under the same contract (tests/test_host_pruned_hat.py holds this one to it); a tuple of
 # its own for the same reason
 ADDITIVE_PRUNED_HAT = ((PRUNED_HAT_SYMBOLS, "warp_rnnt_amd_pruned_hat.h"),)
+# every symbol include/warp_rnnt_amd_pruned_align.h declares (best-path alignments on the pruned band; additive: it did not
+# move the version): the size is a function of (N, T, S, topology); the call is (stream, workspace, input_kind, dtype,
+# inputs, labels, starts, xn, yn, scores, emit_frames, N, T, U, S, V, blank, topology, delay_penalty)
+PRUNED_ALIGN_IN_LOGITS, PRUNED_ALIGN_IN_HAT_LOGITS, PRUNED_ALIGN_IN_PAIRS = 0, 1, 2
+PRUNED_ALIGN_MAX_S = 64
+PRUNED_ALIGN_SYMBOLS = {
+    "rnnt_amd_pruned_align_workspace_size": (_sz, [_i, _i, _i, _i]),
+    "rnnt_amd_pruned_align": (_i, [_vp, _vp, _i, _i] + [_vp] * 7 + [_i] * 7 + [_f]),
+}
+# behind ADDITIVE_PRUNED_HAT, under the same contract (tests/test_host_pruned_align.py holds this one to it); a tuple of
+# its own for the same reason
+ADDITIVE_PRUNED_ALIGN = ((PRUNED_ALIGN_SYMBOLS, "warp_rnnt_amd_pruned_align.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -271,7 +283,7 @@ def load():
     # additive entries do not move the version: a library built before them has to be told apart by its exports
     for table, header in (ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED + ADDITIVE_SIMPLE +
                           ADDITIVE_MULTIBLANK + ADDITIVE_TOPOLOGY + ADDITIVE_PRUNED_JOINT + ADDITIVE_PRUNE_RANGES +
-                          ADDITIVE_PRUNED_HAT):
+                          ADDITIVE_PRUNED_HAT + ADDITIVE_PRUNED_ALIGN):
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

@@ -16,6 +16,7 @@
 #include "../../include/warp_rnnt_amd_multiblank.h"
 #include "../../include/warp_rnnt_amd_prune_ranges.h"
 #include "../../include/warp_rnnt_amd_pruned.h"
+#include "../../include/warp_rnnt_amd_pruned_align.h"
 #include "../../include/warp_rnnt_amd_pruned_hat.h"
 #include "../../include/warp_rnnt_amd_pruned_joint.h"
 #include "../../include/warp_rnnt_amd_simple.h"
@@ -31,6 +32,7 @@
 #include "philox.h"
 #include "prune_ranges.h"
 #include "pruned.h"
+#include "pruned_align.h"
 #include "pruned_hat.h"
 #include "pruned_joint.h"
 #include "simple.h"
@@ -188,6 +190,18 @@ AlignWorkspace align_layout(Carver& c, int N, int T, int U) {
     AlignWorkspace aw;
     aw.words = c.take<unsigned long long>(align_word_count(N, T, U));
     aw.park = c.take<float>(align_park_count(N, T, U));
+    return aw;
+}
+
+// Best-path alignments on the pruned band (pruned_align.hip): the band-compact pairs, then the decision words.
+struct PrunedAlignWorkspace {
+    float* pairs;
+    unsigned long long* words;
+};
+PrunedAlignWorkspace pruned_align_layout(Carver& c, int N, int T, int S, int topology) {
+    PrunedAlignWorkspace aw;
+    aw.pairs = c.take<float>((size_t)N * T * S * 2);
+    aw.words = c.take<unsigned long long>((size_t)N * pruned_align_words(T, topology));
     return aw;
 }
 
@@ -608,6 +622,40 @@ rnntStatus_t rnnt_amd_align(rnntStream_t stream, void* workspace, int input_kind
     if (launch_align_sweep(stream, w.ws2, xn, yn, aw.words, aw.park, scores, N, T, U) != hipSuccess)
         return RNNT_STATUS_WARP_FAILED;
     if (launch_align_trace(stream, aw.words, xn, yn, scores, emit_frames, N, T, U) != hipSuccess)
+        return RNNT_STATUS_WARP_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_pruned_align.h: best-path alignments on the pruned band.  A producer with the pruned loss's row
+// arithmetic fills band-compact pairs -- and leaves them -- and one wave per utterance sweeps the band frame by frame and
+// walks back (pruned_align.hip): no (N,T,U) plane, no floor.
+size_t rnnt_amd_pruned_align_workspace_size(int N, int T, int S, int topology) {
+    if (N < 0 || T < 1 || S < 1 || S > PA_MAX_S || (int64_t)N * T * S >= (int64_t)1 << 32 || !topology_ok(topology, 0.0f))
+        return 0;
+    Carver c(nullptr);
+    pruned_align_layout(c, N, T, S, topology);
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_pruned_align(rnntStream_t stream, void* workspace, int input_kind, int dtype, const void* inputs,
+                                   const int* labels, const int* starts, const int* xn, const int* yn, float* scores,
+                                   int* emit_frames, int N, int T, int U, int S, int V, int blank, int topology,
+                                   float delay_penalty) {
+    const bool logits = input_kind == RNNT_PRUNED_ALIGN_IN_LOGITS || input_kind == RNNT_PRUNED_ALIGN_IN_HAT_LOGITS;
+    if (!logits && input_kind != RNNT_PRUNED_ALIGN_IN_PAIRS) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!topology_ok(topology, delay_penalty) || !dtype_ok(dtype) || (!logits && dtype != RNNT_DTYPE_F32) ||
+        !topology_dims_ok(topology, N, T, U) || V < 2 || !vocab_ok(V, blank) || !pruned_band_ok(N, T, U, S) || S > PA_MAX_S)
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!workspace_ok(workspace) || !inputs || !starts || !xn || !yn || !scores || (U > 1 && !emit_frames) ||
+        (logits && labels_missing(U, labels)))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const PrunedAlignWorkspace aw = pruned_align_layout(c, N, T, S, topology);
+    if (launch_band_pairs(stream, input_kind, dtype, inputs, labels, starts, xn, yn, aw.pairs, N, T, U, S, V, blank,
+                          delay_penalty) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    if (launch_band_sweep(stream, aw.pairs, starts, xn, yn, aw.words, scores, emit_frames, N, T, U, S, topology) != hipSuccess)
         return RNNT_STATUS_WARP_FAILED;
     return RNNT_STATUS_SUCCESS;
 }

@@ -1140,6 +1140,38 @@ def tdt_align(logits, labels, xn, yn, durations, blank=0, sigma=0.0):
     return scores, emit_frames, emit_durations
 
 
+PRUNED_ALIGN_KINDS = {"logits": _lib.PRUNED_ALIGN_IN_LOGITS, "hat_logits": _lib.PRUNED_ALIGN_IN_HAT_LOGITS,
+                      "pairs": _lib.PRUNED_ALIGN_IN_PAIRS}
+
+
+def pruned_align(inputs, labels, starts, xn, yn, input_kind, blank=0, topology=_lib.TOPOLOGY_REGULAR, delay_penalty=0.0):
+    """Best-path alignments on the pruned band (include/warp_rnnt_amd_pruned_align.h, csrc/pruned_align.hip): ``inputs``
+    (N,T,S,V) as :func:`pruned_loss_topology` / :func:`pruned_hat_loss` take them, or (N,T,S,2) fp32 pairs for
+    PRUNED_ALIGN_IN_PAIRS; starts (N,T) int32 contiguous; validated by the caller.  Returns scores (N,) fp32 -- -inf where
+    the band holds no path -- and emit_frames (N,U-1) int32, -1 behind yn[n] and for an utterance without a path."""
+    L = _lib.load()
+    N, T, S, V = inputs.shape
+    U = labels.shape[1] + 1
+    dev = inputs.device
+    if input_kind == _lib.PRUNED_ALIGN_IN_PAIRS:
+        blank = 0          # channel 0 of the 2-channel layout
+    _pruned_check(S, U, V, blank)
+    if S > _lib.PRUNED_ALIGN_MAX_S:
+        raise RuntimeError(f"rnnt_loss status 5 (RNNT_STATUS_INVALID_ARGUMENT): pruned_rnnt_align takes a band of at most "
+                           f"{_lib.PRUNED_ALIGN_MAX_S} positions (S={S})")
+    with torch.cuda.device(dev):
+        scores = torch.empty((N,), dtype=torch.float32, device=dev)
+        emit_frames = torch.empty((N, U - 1), dtype=torch.int32, device=dev)
+        if N == 0:
+            return scores, emit_frames
+        ws = _workspace(dev, lambda n, t, s: L.rnnt_amd_pruned_align_workspace_size(n, t, s, topology), "N T S", N, T, S)
+        _check(L.rnnt_amd_pruned_align(_stream(dev), ws.data_ptr(), input_kind, LOGITS_DTYPES[inputs.dtype],
+                                       inputs.data_ptr(), _ptr(labels), starts.data_ptr(), xn.data_ptr(), yn.data_ptr(),
+                                       scores.data_ptr(), emit_frames.data_ptr() if U > 1 else 0, N, T, U, S, V, blank,
+                                       topology, float(delay_penalty)))
+    return scores, emit_frames
+
+
 ALIGN_IN_HAT_LOGITS = _lib.ALIGN_IN_HAT_LOGITS
 
 

@@ -45,9 +45,14 @@ graph over them; the backward's workspace holds one ``(N,T,S,H)`` buffer::
 ``use_hat_loss=True`` (k2's argument; icefall's ``zipformer_hat``) puts the factorised-blank (HAT) log-probs of
 ``hat_loss_from_logits`` into the band's cells: csrc/pruned_hat.hip, DESIGN.md 3.23.
 
-Out of scope: k2's ``constrained`` topology; a pruned form of TDT, the compact layout or ``rnnt_align``; the gradient
-clamp; a sweep that visits the band's cells only (the sweeps cost what the dense loss's do -- DESIGN.md 3.17 prices the
-alternative).  Of the joint form: the two knobs of the streaming recipes above, dropout.
+:func:`pruned_rnnt_align` is ``rnnt_align`` for this recipe: the best path through the band -- its score and the frame at
+which every label is emitted -- from the band's logits (plain or HAT) or from ready-made pairs, in either topology and
+with the delay penalty it is the measure of; a frame-synchronous sweep, one wave per utterance, that never forms an
+``(N,T,U)`` plane (csrc/pruned_align.hip).
+
+Out of scope: k2's ``constrained`` topology; a pruned form of TDT or the compact layout; the gradient
+clamp; loss sweeps that visit the band's cells only (the loss's alpha/beta sweeps cost what the dense loss's do --
+DESIGN.md 3.17 prices the alternative; the alignment's sweep above is such a sweep).  Of the joint form: the two knobs of the streaming recipes above, dropout.
 """
 import math
 from typing import Optional
@@ -208,6 +213,42 @@ class PrunedRNNTLoss(torch.nn.Module):
                                             reduction=self.reduction, blank=self.blank,
                                             fastemit_lambda=self.fastemit_lambda, rnnt_type=self.rnnt_type,
                                             delay_penalty=self.delay_penalty, use_hat_loss=self.use_hat_loss)
+
+
+PRUNED_ALIGN_KINDS = tuple(ops.PRUNED_ALIGN_KINDS)
+
+
+def pruned_rnnt_align(inputs: torch.Tensor, labels: torch.Tensor, ranges: torch.Tensor, frames_lengths: torch.Tensor,
+                      labels_lengths: torch.Tensor, blank: int = 0, kind: str = "logits", rnnt_type: str = "regular",
+                      delay_penalty: float = 0.0):
+    """The best path of every utterance through the band: ``(scores, emit_frames)``.
+
+    ``kind`` says what ``inputs`` holds: ``"logits"`` (N,T,S,V) in fp32, bf16 or fp16, read as
+    :func:`pruned_rnnt_loss_from_logits` reads them; ``"hat_logits"`` the same, read as it reads them with
+    ``use_hat_loss=True``; ``"pairs"`` (N,T,S,2) fp32, channel 0 the blank's log-probability of row ``(n,t,s)`` and channel 1
+    the label's (``labels`` and ``blank`` are then only checked for their shape).  ``ranges``: k2's ``(N,T,S)`` integer
+    tensor or the ``(N,T)`` starts; ``1 <= S <= min(U, 64)``.  ``rnnt_type`` and ``delay_penalty`` are the loss's, and the
+    penalty is added to the label channel of every kind.
+
+    ``scores`` (N,) fp32 is the log-probability (penalties included) of the best path, ``-inf`` where the band holds none
+    -- and, with ``"modified"``, where ``T_n < U_n``; ``emit_frames`` (N,U-1) int32 holds the frame at which label ``u`` is
+    emitted (``"modified"``: the frame its edge consumes), -1 in the columns from ``labels_lengths[n]`` on and throughout
+    for an utterance without a path.  Lengths outside ``[1,T]`` x ``[0,U-1]`` give a NaN score and a row of -1.  The
+    arithmetic is fp32, one add per edge and one compare per cell, a tie goes to the blank.
+    ``warp_rnnt_amd.align.alignment_mask`` applies unchanged to the regular topology's frames.  Both outputs are detached
+    and computed under ``no_grad``.  Enqueue-only: the call can be captured into a graph."""
+    assert isinstance(blank, int)
+    if kind not in ops.PRUNED_ALIGN_KINDS:
+        raise ValueError(f"kind must be one of {PRUNED_ALIGN_KINDS}, not {kind!r}")
+    topology, delay_penalty = ops.topology_of(rnnt_type, delay_penalty)
+    with torch.no_grad():
+        inputs = inputs.detach()
+        starts = band_starts(ranges, inputs.shape[2] if inputs.dim() == 4 else None)
+        check_pruned_inputs(inputs, labels, starts, frames_lengths, labels_lengths)
+        if kind == "pairs" and (inputs.dtype != torch.float32 or inputs.size(3) != 2):
+            raise RuntimeError("xs must be float32 with values only for blank and label")
+        return ops.pruned_align(inputs, labels, starts, frames_lengths, labels_lengths, ops.PRUNED_ALIGN_KINDS[kind], blank,
+                                topology, delay_penalty)
 
 
 # ---- the rest of the recipe: plain torch on any device, no Python loop over N or T, no read-back; prune_ranges_hip is the
