@@ -244,6 +244,19 @@ PRUNED_ALIGN_SYMBOLS = {
 # behind ADDITIVE_PRUNED_HAT, under the same contract (tests/test_host_pruned_align.py holds this one to it); a tuple of
 # its own for the same reason
 ADDITIVE_PRUNED_ALIGN = ((PRUNED_ALIGN_SYMBOLS, "warp_rnnt_amd_pruned_align.h"),)
+# every symbol include/warp_rnnt_amd_pruned_hidden.h declares (the pruned joiner's act(f + g on the band) and its backward;
+# additive: it did not move the version): the size is a function of (N, T, U, S, H); the forward is (stream, dtype,
+# activation, f, g, starts, xn, h, N, T, U, S, H), the backward (stream, workspace, dtype, activation, dh, h, starts, xn, df,
+# dg, N, T, U, S, H); xn, df and dg may be null
+PRUNED_HIDDEN_MIN_H, PRUNED_HIDDEN_MAX_H = 8, 4096
+PRUNED_HIDDEN_SYMBOLS = {
+    "rnnt_amd_pruned_hidden_workspace_size": (_sz, [_i] * 5),
+    "rnnt_amd_pruned_hidden": (_i, [_vp, _i, _i] + [_vp] * 5 + [_i] * 5),
+    "rnnt_amd_pruned_hidden_backward": (_i, [_vp, _vp, _i, _i] + [_vp] * 6 + [_i] * 5),
+}
+# behind ADDITIVE_PRUNED_ALIGN, under the same contract (tests/test_host_pruned_hidden.py holds this one to it); a tuple of
+# its own for the same reason
+ADDITIVE_PRUNED_HIDDEN = ((PRUNED_HIDDEN_SYMBOLS, "warp_rnnt_amd_pruned_hidden.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -283,7 +296,7 @@ def load():
     # additive entries do not move the version: a library built before them has to be told apart by its exports
     for table, header in (ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED + ADDITIVE_SIMPLE +
                           ADDITIVE_MULTIBLANK + ADDITIVE_TOPOLOGY + ADDITIVE_PRUNED_JOINT + ADDITIVE_PRUNE_RANGES +
-                          ADDITIVE_PRUNED_HAT + ADDITIVE_PRUNED_ALIGN):
+                          ADDITIVE_PRUNED_HAT + ADDITIVE_PRUNED_ALIGN + ADDITIVE_PRUNED_HIDDEN):
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

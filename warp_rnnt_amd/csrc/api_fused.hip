@@ -9,7 +9,8 @@
 // into it (include/warp_rnnt_amd_tdt_joint.h), the multi-blank loss (include/warp_rnnt_amd_multiblank.h: producer, sweeps
 // and gradient kernel all its own), the joint network fused into the pruned loss
 // (include/warp_rnnt_amd_pruned_joint.h), the band selection between the recipe's two passes
-// (include/warp_rnnt_amd_prune_ranges.h).  Host-side orchestration only: argument checks, workspace carving, launches.
+// (include/warp_rnnt_amd_prune_ranges.h) and the joiner's hidden activations on the band behind it
+// (include/warp_rnnt_amd_pruned_hidden.h).  Host-side orchestration only: argument checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd_align.h"
 #include "../../include/warp_rnnt_amd_hat.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
@@ -18,6 +19,7 @@
 #include "../../include/warp_rnnt_amd_pruned.h"
 #include "../../include/warp_rnnt_amd_pruned_align.h"
 #include "../../include/warp_rnnt_amd_pruned_hat.h"
+#include "../../include/warp_rnnt_amd_pruned_hidden.h"
 #include "../../include/warp_rnnt_amd_pruned_joint.h"
 #include "../../include/warp_rnnt_amd_simple.h"
 #include "../../include/warp_rnnt_amd_tdt.h"
@@ -34,6 +36,7 @@
 #include "pruned.h"
 #include "pruned_align.h"
 #include "pruned_hat.h"
+#include "pruned_hidden.h"
 #include "pruned_joint.h"
 #include "simple.h"
 #include "tdt.h"
@@ -203,6 +206,12 @@ PrunedAlignWorkspace pruned_align_layout(Carver& c, int N, int T, int S, int top
     aw.pairs = c.take<float>((size_t)N * T * S * 2);
     aw.words = c.take<unsigned long long>((size_t)N * pruned_align_words(T, topology));
     return aw;
+}
+
+// The pruned joiner's hidden activations (pruned_hidden.hip): a band of any width S >= 1 over g's U rows
+inline bool pruned_hidden_args_ok(int dtype, int activation, int N, int T, int U, int S, int H) {
+    return dtype_ok(dtype) && (activation == RNNT_ACT_TANH || activation == RNNT_ACT_RELU) && dims_ok(N, T, U) &&
+           pruned_hidden_shape_ok(N, T, U, S, H);
 }
 
 // The token-and-duration loss (tdt.hip): the plane of 2 + D channels, alpha, beta, the log-likelihoods.
@@ -933,6 +942,43 @@ rnntStatus_t rnnt_amd_prune_ranges(rnntStream_t stream, const float* pair_grads,
     if (N == 0) return RNNT_STATUS_SUCCESS;
     if (launch_prune_ranges(stream, pair_grads, pitch, xn, yn, starts, N, T, U, S) != hipSuccess)
         return RNNT_STATUS_PROLOGUE_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_pruned_hidden.h: the pruned joiner's act(f + g on the band) and its backward (pruned_hidden.hip).
+// The forward is one launch without a workspace; the backward's workspace is the dg kernel's (lo, hi) table.
+size_t rnnt_amd_pruned_hidden_workspace_size(int N, int T, int U, int S, int H) {
+    if (!pruned_hidden_args_ok(RNNT_DTYPE_F32, RNNT_ACT_TANH, N, T, U, S, H)) return 0;
+    Carver c(nullptr);
+    c.take<int>(pruned_hidden_table_ints(N, U));
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_pruned_hidden(rnntStream_t stream, int dtype, int activation, const void* f, const void* g,
+                                    const int* starts, const int* xn, void* h, int N, int T, int U, int S, int H) {
+    if (!pruned_hidden_args_ok(dtype, activation, N, T, U, S, H)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!f || !g || !starts || !h) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!aligned(f, 16) || !aligned(g, 16) || !aligned(h, 16) || !aligned(starts, 4) || !aligned(xn, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    if (launch_pruned_hidden_fwd(stream, dtype, activation, f, g, starts, xn, h, N, T, U, S, H) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_pruned_hidden_backward(rnntStream_t stream, void* workspace, int dtype, int activation, const void* dh,
+                                             const void* h, const int* starts, const int* xn, void* df, void* dg, int N,
+                                             int T, int U, int S, int H) {
+    if (!pruned_hidden_args_ok(dtype, activation, N, T, U, S, H)) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!dh || !h || !starts || (dg && !workspace_ok(workspace))) return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!aligned(dh, 16) || !aligned(h, 16) || !aligned(df, 16) || !aligned(dg, 16) || !aligned(starts, 4) ||
+        !aligned(xn, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0 || (!df && !dg)) return RNNT_STATUS_SUCCESS;
+    Carver c(dg ? workspace : nullptr);
+    int* table = c.take<int>(pruned_hidden_table_ints(N, U));
+    if (launch_pruned_hidden_bwd(stream, dtype, activation, dh, h, starts, xn, table, df, dg, N, T, U, S, H) != hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
 

@@ -1172,6 +1172,49 @@ def pruned_align(inputs, labels, starts, xn, yn, input_kind, blank=0, topology=_
     return scores, emit_frames
 
 
+def _pruned_hidden_check(T, U, S, H):
+    lo, hi = _lib.PRUNED_HIDDEN_MIN_H, _lib.PRUNED_HIDDEN_MAX_H
+    if H % 8 or not lo <= H <= hi or S < 1 or U < 1 or T < 1:
+        raise ValueError(f"pruned_joint_hidden takes H % 8 == 0, {lo} <= H <= {hi}, S >= 1, U >= 1 and T >= 1 "
+                         f"(H={H}, S={S}, U={U}, T={T})")
+
+
+def pruned_hidden(f, g, starts, xn, S, activation="tanh"):
+    """The pruned joiner's hidden activations (include/warp_rnnt_amd_pruned_hidden.h, csrc/pruned_hidden.hip): f (N,T,H)
+    and g (N,U,H) of one dtype (fp32 / bf16 / fp16), contiguous at 16-byte aligned addresses, starts (N,T) int32 contiguous,
+    xn (N,) int32 contiguous or None (every frame is live); validated by the caller.  Returns h (N,T,S,H) in that dtype."""
+    L = _lib.load()
+    N, T, H = f.shape
+    U = g.shape[1]
+    dev = f.device
+    _pruned_hidden_check(T, U, S, H)
+    with torch.cuda.device(dev):
+        h = torch.empty((N, T, S, H), dtype=f.dtype, device=dev)
+        if N == 0:
+            return h
+        _check(L.rnnt_amd_pruned_hidden(_stream(dev), LOGITS_DTYPES[f.dtype], ACTIVATIONS[activation], f.data_ptr(),
+                                        g.data_ptr(), starts.data_ptr(), _ptr(xn), h.data_ptr(), N, T, U, S, H))
+    return h
+
+
+def pruned_hidden_backward(dh, h, starts, xn, U, activation="tanh", need_f=True, need_g=True):
+    """d/d(f, g) of :func:`pruned_hidden` from dh and the h it returned, both (N,T,S,H) contiguous at 16-byte aligned
+    addresses: df (N,T,H) and dg (N,U,H) in their dtype, None for what is not asked for (and not computed)."""
+    L = _lib.load()
+    N, T, S, H = h.shape
+    dev = h.device
+    with torch.cuda.device(dev):
+        df = torch.empty((N, T, H), dtype=h.dtype, device=dev) if need_f else None
+        dg = torch.empty((N, U, H), dtype=h.dtype, device=dev) if need_g else None
+        if N == 0 or not (need_f or need_g):
+            return df, dg
+        ws = _workspace(dev, L.rnnt_amd_pruned_hidden_workspace_size, "N T U S H", N, T, U, S, H) if need_g else None
+        _check(L.rnnt_amd_pruned_hidden_backward(_stream(dev), _ptr(ws), LOGITS_DTYPES[h.dtype], ACTIVATIONS[activation],
+                                                 dh.data_ptr(), h.data_ptr(), starts.data_ptr(), _ptr(xn), _ptr(df),
+                                                 _ptr(dg), N, T, U, S, H))
+    return df, dg
+
+
 ALIGN_IN_HAT_LOGITS = _lib.ALIGN_IN_HAT_LOGITS
 
 

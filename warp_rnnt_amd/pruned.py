@@ -21,6 +21,16 @@ The recipe, in three steps (tests/test_gpu_simple.py runs it end to end)::
     loss   = pruned_rnnt_loss_from_logits(joiner(fp, gp), labels, starts, xn, yn)
     (simple_loss_scale * simple.sum() + loss.sum()).backward()
 
+:func:`pruned_joint_hidden` is the third step and the joiner's activation as one HIP unit (csrc/pruned_hidden.hip,
+DESIGN.md 3.25): ``h = act(f + g on the band)`` written once, a backward that reads ``dh`` and ``h`` and writes ``df`` and
+``dg`` -- no ``(N,T,S,H)`` copy of ``g``, no atomics, nothing saved but ``h``; the output projection stays the vendor's
+GEMM.  The recipe is then four calls in a row::
+
+    simple, pair_grads = simple_rnnt_loss(am, lm, labels, xn, yn, lm_only_scale=0.25, return_grad=True)
+    starts = prune_ranges_hip(pair_grads, xn, yn, s_range)
+    h      = pruned_joint_hidden(f, g, starts, xn, s_range=s_range, activation="tanh")     # (N,T,S,H), once
+    loss   = pruned_rnnt_loss_from_logits(joiner.output_linear(h), labels, starts, xn, yn)
+
 ``simple_rnnt_loss`` (simple.py, csrc/simple.hip) is k2's ``rnnt_loss_smoothed`` on the fused path: its forward already
 holds the gradient pairs and hands them back with ``return_grad=True`` -- no ``requires_grad_`` on an intermediate tensor,
 no ``autograd.grad(..., retain_graph=True)``.  The plain-torch form of its pairs without the smoothing scales,
@@ -387,6 +397,78 @@ def prune_joint_inputs(f: torch.Tensor, g: torch.Tensor, ranges: torch.Tensor, s
     idx = (starts.long()[..., None] + torch.arange(S, device=starts.device)).clamp(0, U - 1)          # (N,T,S)
     gp = g.gather(1, idx.reshape(N, T * S, 1).expand(N, T * S, H)).reshape(N, T, S, H)
     return f[:, :, None, :].expand(N, T, S, H), gp
+
+
+# ---- the joiner's hidden activations on the band (csrc/pruned_hidden.hip) ----
+
+class PrunedJointHidden(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, f, g, starts, xn, S, activation):
+        h = ops.pruned_hidden(_aligned(f.detach()), _aligned(g.detach()), starts, xn, S, activation)
+        ctx.save_for_backward(h, starts, xn)          # h is the output: the Linear behind it keeps it anyway
+        ctx.U, ctx.activation = g.shape[1], activation
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        h, starts, xn = ctx.saved_tensors
+        df, dg = ops.pruned_hidden_backward(_aligned(dh), h, starts, xn, ctx.U, ctx.activation, ctx.needs_input_grad[0],
+                                            ctx.needs_input_grad[1])
+        return df, dg, None, None, None, None
+
+
+def pruned_joint_hidden(f: torch.Tensor, g: torch.Tensor, ranges: torch.Tensor,
+                        frames_lengths: Optional[torch.Tensor] = None, *, s_range: Optional[int] = None,
+                        activation: str = "tanh") -> torch.Tensor:
+    """``act(fp + gp)`` on ``fp, gp = prune_joint_inputs(f, g, ranges, s_range)`` as one HIP launch: f ``(N,T,H)``, g
+    ``(N,U,H)`` of one dtype (fp32, bf16 or fp16), ``ranges`` k2's ``(N,T,S)`` integer tensor (only ``[..., 0]`` is used) or
+    the ``(N,T)`` starts with ``s_range=S``, ``activation`` one of ``ops.ACTIVATIONS``.  Returns ``h`` ``(N,T,S,H)``,
+    contiguous, in that dtype::
+
+        h[n,t,s,:] = act(float(f[n,t,:]) + float(g[n, clamp(starts[n,t] + s, 0, U-1), :]))
+
+    the sum and the activation in fp32, rounded once.  Served: ``H % 8 == 0``, ``8 <= H <= 4096``, ``S >= 1``, ``U >= 1``,
+    ``T >= 1``; another shape is a ``ValueError``.  With ``frames_lengths`` (N,) int32, frames ``t >= frames_lengths[n]`` are
+    not read: their rows of ``h`` are exactly zero, they add exactly nothing to the gradients and their rows of ``df`` are
+    zero.  ``None``: all ``T`` frames are live.
+
+    Gradients go to f and g only, and only where they are needed: with ``p = dh * act'(h)`` (``act'`` from the rounded
+    ``h``, the product in fp32) ``df`` is the sum of ``p`` over ``s`` and ``dg[n,u]`` the sum over the live ``(t,s)`` whose
+    clamped index is ``u`` -- fp32 sums in ascending ``t``, then ``s``, rounded once; a ``u`` no live row maps to gets an
+    exactly zero row.  No atomics and no ``(N,T,S,H)`` temporary: nothing is saved but ``h``, two runs give the same bits.
+    Enqueue-only: nothing is read back, the call and its backward can be captured into a graph."""
+    if activation not in ops.ACTIVATIONS:
+        raise ValueError(f"activation must be one of {tuple(ops.ACTIVATIONS)}, not {activation!r}")
+    if not isinstance(f, torch.Tensor) or not isinstance(g, torch.Tensor) or f.dim() != 3 or g.dim() != 3:
+        raise RuntimeError("f must be (N,T,H) and g (N,U,H)")
+    if f.dtype not in ops.LOGITS_DTYPES or g.dtype != f.dtype:
+        raise RuntimeError(f"f and g must share one dtype of float32, bfloat16 and float16 (f is {f.dtype}, g is {g.dtype})")
+    if ranges.dim() == 3:
+        S = ranges.shape[2] if s_range is None else int(s_range)
+    elif s_range is None:
+        raise ValueError("pruned_joint_hidden needs s_range with ranges of shape (N,T)")
+    else:
+        S = int(s_range)
+    N, T, H = f.shape
+    if g.shape[0] != N or g.shape[2] != H:
+        raise RuntimeError(f"g must be (N,U,H) = ({N},U,{H}), not {tuple(g.shape)}")
+    ops._pruned_hidden_check(T, g.shape[1], S, H)
+    starts = band_starts(ranges, S)
+    if tuple(starts.shape) != (N, T):
+        raise RuntimeError(f"ranges must be (N,T,S) or (N,T) for f (N,T,H) = {tuple(f.shape)}")
+    xn = frames_lengths
+    if xn is not None:
+        _core._check_int(xn, "frames_lengths")
+        if xn.numel() != N:
+            raise RuntimeError("frames_lengths shape must be equal (N,)")
+        xn = xn.contiguous()
+    for x, name in ((f, "f"), (g, "g"), (starts, "ranges"), (xn, "frames_lengths")):
+        if x is not None:
+            _core._check_cuda(x, name)
+            if x.device != f.device:
+                raise RuntimeError(f"{name} must be on the device of f ({f.device}), not {x.device}")
+    return PrunedJointHidden.apply(f, g, starts, xn, S, activation)
 
 
 # ---- the joiner fused into the loss (csrc/pruned_joint.hip) ----
