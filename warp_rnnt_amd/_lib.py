@@ -257,6 +257,19 @@ PRUNED_HIDDEN_SYMBOLS = {
 # behind ADDITIVE_PRUNED_ALIGN, under the same contract (tests/test_host_pruned_hidden.py holds this one to it); a tuple of
 # its own for the same reason
 ADDITIVE_PRUNED_HIDDEN = ((PRUNED_HIDDEN_SYMBOLS, "warp_rnnt_amd_pruned_hidden.h"),)
+# every symbol include/warp_rnnt_amd_ctc.h declares (the CTC loss from logits; additive: it did not move the version): the
+# size is a function of (N, T, L, V); the forward is (stream, workspace, dtype, logits, labels, xn, yn, costs, N, T, L, V,
+# blank), the backward (stream, workspace, dtype, logits, labels, xn, yn, dcosts, dlogits, N, T, L, V, blank) on the
+# workspace the forward left; dcosts may be null
+CTC_MAX_L, CTC_MIN_V, CTC_MAX_V = 1023, 2, 16384
+CTC_SYMBOLS = {
+    "rnnt_amd_ctc_workspace_size": (_sz, [_i] * 4),
+    "rnnt_amd_ctc_loss_logits": (_i, [_vp, _vp, _i] + [_vp] * 5 + [_i] * 5),
+    "rnnt_amd_ctc_logits_backward": (_i, [_vp, _vp, _i] + [_vp] * 6 + [_i] * 5),
+}
+# behind ADDITIVE_PRUNED_HIDDEN, under the same contract (tests/test_host_ctc.py holds this one to it); a tuple of its own
+# for the same reason
+ADDITIVE_CTC = ((CTC_SYMBOLS, "warp_rnnt_amd_ctc.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -296,7 +309,7 @@ def load():
     # additive entries do not move the version: a library built before them has to be told apart by its exports
     for table, header in (ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED + ADDITIVE_SIMPLE +
                           ADDITIVE_MULTIBLANK + ADDITIVE_TOPOLOGY + ADDITIVE_PRUNED_JOINT + ADDITIVE_PRUNE_RANGES +
-                          ADDITIVE_PRUNED_HAT + ADDITIVE_PRUNED_ALIGN + ADDITIVE_PRUNED_HIDDEN):
+                          ADDITIVE_PRUNED_HAT + ADDITIVE_PRUNED_ALIGN + ADDITIVE_PRUNED_HIDDEN + ADDITIVE_CTC):
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

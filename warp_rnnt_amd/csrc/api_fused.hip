@@ -10,8 +10,11 @@
 // and gradient kernel all its own), the joint network fused into the pruned loss
 // (include/warp_rnnt_amd_pruned_joint.h), the band selection between the recipe's two passes
 // (include/warp_rnnt_amd_prune_ranges.h) and the joiner's hidden activations on the band behind it
-// (include/warp_rnnt_amd_pruned_hidden.h).  Host-side orchestration only: argument checks, workspace carving, launches.
+// (include/warp_rnnt_amd_pruned_hidden.h), and the CTC loss the recipes train beside the transducer
+// (include/warp_rnnt_amd_ctc.h: producer, sweeps and gradient kernel all its own).  Host-side orchestration only: argument
+// checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd_align.h"
+#include "../../include/warp_rnnt_amd_ctc.h"
 #include "../../include/warp_rnnt_amd_hat.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
 #include "../../include/warp_rnnt_amd_multiblank.h"
@@ -29,6 +32,7 @@
 
 #include "align.h"
 #include "api_common.h"
+#include "ctc.h"
 #include "hat.h"
 #include "multiblank.h"
 #include "philox.h"
@@ -212,6 +216,27 @@ PrunedAlignWorkspace pruned_align_layout(Carver& c, int N, int T, int S, int top
 inline bool pruned_hidden_args_ok(int dtype, int activation, int N, int T, int U, int S, int H) {
     return dtype_ok(dtype) && (activation == RNNT_ACT_TANH || activation == RNNT_ACT_RELU) && dims_ok(N, T, U) &&
            pruned_hidden_shape_ok(N, T, U, S, H);
+}
+
+// The CTC loss (ctc.hip): the rows' (max, log sum), the emissions, alpha and beta with their two channels, the
+// log-likelihoods, the label order.
+CtcWorkspace ctc_layout(Carver& c, int N, int T, int L) {
+    const size_t rows = (size_t)N * T, cells = rows * ((size_t)L + 1);
+    CtcWorkspace w;
+    w.stats = c.take<float2>(rows);
+    w.E = c.take<float>(cells);
+    w.alpha = c.take<float>(cells * 2);
+    w.beta = c.take<float>(cells * 2);
+    w.ll = c.take<float>((size_t)N);
+    w.order = c.take<int>((size_t)N * L);
+    return w;
+}
+// what both CTC entries refuse: the shape, the dtype, the blank, a missing or misplaced tensor
+inline bool ctc_args_ok(const void* workspace, int dtype, const void* logits, const int* labels, const int* xn,
+                        const int* yn, int N, int T, int L, int V, int blank) {
+    return dtype_ok(dtype) && ctc_shape_ok(N, T, L, V) && vocab_ok(V, blank) && workspace_ok(workspace) && logits &&
+           labels && xn && yn && aligned(logits, dtype == RNNT_DTYPE_F32 ? 4 : 2) && aligned(labels, 4) && aligned(xn, 4) &&
+           aligned(yn, 4);
 }
 
 // The token-and-duration loss (tdt.hip): the plane of 2 + D channels, alpha, beta, the log-likelihoods.
@@ -978,6 +1003,41 @@ rnntStatus_t rnnt_amd_pruned_hidden_backward(rnntStream_t stream, void* workspac
     Carver c(dg ? workspace : nullptr);
     int* table = c.take<int>(pruned_hidden_table_ints(N, U));
     if (launch_pruned_hidden_bwd(stream, dtype, activation, dh, h, starts, xn, table, df, dg, N, T, U, S, H) != hipSuccess)
+        return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_ctc.h: the CTC loss from logits (ctc.hip).  The forward leaves emissions, alpha and the
+// log-likelihoods in the workspace; the backward adds beta and the label order and writes d/d logits.
+size_t rnnt_amd_ctc_workspace_size(int N, int T, int L, int V) {
+    if (!ctc_shape_ok(N, T, L, V)) return 0;
+    Carver c(nullptr);
+    ctc_layout(c, N, T, L);
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_ctc_loss_logits(rnntStream_t stream, void* workspace, int dtype, const void* logits, const int* labels,
+                                      const int* xn, const int* yn, float* costs, int N, int T, int L, int V, int blank) {
+    if (!ctc_args_ok(workspace, dtype, logits, labels, xn, yn, N, T, L, V, blank) || !costs || !aligned(costs, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const CtcWorkspace w = ctc_layout(c, N, T, L);
+    if (launch_ctc_forward(stream, dtype, logits, labels, xn, yn, w, costs, N, T, L, V, blank) != hipSuccess)
+        return RNNT_STATUS_PROLOGUE_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t rnnt_amd_ctc_logits_backward(rnntStream_t stream, void* workspace, int dtype, const void* logits,
+                                          const int* labels, const int* xn, const int* yn, const float* dcosts,
+                                          void* dlogits, int N, int T, int L, int V, int blank) {
+    if (!ctc_args_ok(workspace, dtype, logits, labels, xn, yn, N, T, L, V, blank) || !dlogits ||
+        !aligned(dlogits, dtype == RNNT_DTYPE_F32 ? 4 : 2) || !aligned(dcosts, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const CtcWorkspace w = ctc_layout(c, N, T, L);
+    if (launch_ctc_backward(stream, dtype, logits, labels, xn, yn, w, dcosts, dlogits, N, T, L, V, blank) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
     return RNNT_STATUS_SUCCESS;
 }

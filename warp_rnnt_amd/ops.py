@@ -1215,6 +1215,48 @@ def pruned_hidden_backward(dh, h, starts, xn, U, activation="tanh", need_f=True,
     return df, dg
 
 
+def _ctc_check(N, T, L, V, blank):
+    if not 1 <= L <= _lib.CTC_MAX_L or not _lib.CTC_MIN_V <= V <= _lib.CTC_MAX_V or T < 1 or N * T * (L + 1) >= 1 << 31:
+        raise ValueError(f"ctc_loss_from_logits takes 1 <= L <= {_lib.CTC_MAX_L}, {_lib.CTC_MIN_V} <= V <= "
+                         f"{_lib.CTC_MAX_V}, T >= 1 and N*T*(L+1) < 2^31 (N={N}, T={T}, L={L}, V={V})")
+    if not 0 <= blank < V:
+        raise ValueError(f"blank={blank} is not a vocabulary index of logits (V={V})")
+
+
+def ctc_loss(logits, labels, xn, yn, blank=0):
+    """The CTC costs (N,) fp32 of logits (N,T,V) and the workspace the forward left for :func:`ctc_logits_backward`
+    (include/warp_rnnt_amd_ctc.h, csrc/ctc.hip): emissions and the alpha sweep.  Tensors validated by the caller."""
+    L = _lib.load()
+    N, T, V = logits.shape
+    dev = logits.device
+    _ctc_check(N, T, labels.shape[1], V, blank)
+    with torch.cuda.device(dev):
+        costs = torch.empty((N,), dtype=torch.float32, device=dev)
+        if N == 0:
+            return costs, None
+        ws = _workspace(dev, L.rnnt_amd_ctc_workspace_size, "N T L V", N, T, labels.shape[1], V)
+        _check(L.rnnt_amd_ctc_loss_logits(_stream(dev), ws.data_ptr(), LOGITS_DTYPES[logits.dtype], logits.data_ptr(),
+                                          labels.data_ptr(), xn.data_ptr(), yn.data_ptr(), costs.data_ptr(), N, T,
+                                          labels.shape[1], V, blank))
+    return costs, ws
+
+
+def ctc_logits_backward(logits, labels, xn, yn, workspace, grad_costs, blank=0):
+    """d/d logits (N,T,V) in the logits' dtype from the workspace :func:`ctc_loss` returned for the same arguments: the beta
+    sweep, the label order, the gradient kernel.  grad_costs (N,) fp32 or None for ones."""
+    L = _lib.load()
+    N, T, V = logits.shape
+    dev = logits.device
+    with torch.cuda.device(dev):
+        out = torch.empty_like(logits)
+        if N == 0:
+            return out
+        _check(L.rnnt_amd_ctc_logits_backward(_stream(dev), workspace.data_ptr(), LOGITS_DTYPES[logits.dtype],
+                                              logits.data_ptr(), labels.data_ptr(), xn.data_ptr(), yn.data_ptr(),
+                                              _ptr(grad_costs), out.data_ptr(), N, T, labels.shape[1], V, blank))
+    return out
+
+
 ALIGN_IN_HAT_LOGITS = _lib.ALIGN_IN_HAT_LOGITS
 
 
