@@ -17,11 +17,12 @@ SOURCES = ["api_loss.hip", "api_compact.hip", "api_reference.hip", "api_fused.hi
            "lattice_wd.hip", "grads.hip", "lsm_f32.hip", "lsm_bf16.hip", "lsm_f16.hip", "lsm_backward.hip", "to_diagonal.hip",
            "compact.hip", "expand.hip", "joint.hip", "hat.hip", "align.hip", "tdt.hip", "tdt_align.hip",
            "tdt_joint.hip", "pruned.hip", "simple.hip", "multiblank.hip", "pruned_joint.hip", "prune_ranges.hip",
-           "pruned_hat.hip", "pruned_align.hip", "pruned_hidden.hip", "ctc.hip"]
+           "pruned_hat.hip", "pruned_align.hip", "pruned_hidden.hip", "ctc.hip", "ctc_align.hip"]
 HEADERS = ["api_common.h", "common.h", "kernels.h", "lattice_plan.h", "lattice_launch.h", "lattice_step.h", "lattice_wd_body.h",
            "lattice_single.h", "grads_cell.h", "streaming.h", "lsm_plan.h", "lsm.h", "philox.h", "hat.h", "align.h", "row_chunks.h", "tdt.h", "tdt_align.h",
            "joint_tile.h", "tdt_joint.h", "pruned.h", "simple.h", "multiblank.h", "pruned_joint.h", "prune_ranges.h", "pruned_hat.h",
            "pruned_align.h", "pruned_hidden.h", "ctc.h", os.path.join("..", "..", "include", "warp_rnnt_amd_ctc.h"),
+           "ctc_align.h", os.path.join("..", "..", "include", "warp_rnnt_amd_ctc_align.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_pruned_hidden.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_pruned_align.h"),
            os.path.join("..", "..", "include", "warp_rnnt_amd_pruned_hat.h"),

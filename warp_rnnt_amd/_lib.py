@@ -270,6 +270,17 @@ CTC_SYMBOLS = {
 # behind ADDITIVE_PRUNED_HIDDEN, under the same contract (tests/test_host_ctc.py holds this one to it); a tuple of its own
 # for the same reason
 ADDITIVE_CTC = ((CTC_SYMBOLS, "warp_rnnt_amd_ctc.h"),)
+# every symbol include/warp_rnnt_amd_ctc_align.h declares (best-path alignments of the CTC lattice; additive: it did not
+# move the version): the size is a function of (N, T, L, V); the call is (stream, workspace, input_kind, dtype, inputs,
+# labels, xn, yn, scores, frame_tokens, emit_frames, N, T, L, V, blank)
+CTC_ALIGN_IN_LOGITS, CTC_ALIGN_IN_LOG_PROBS = 0, 1
+CTC_ALIGN_SYMBOLS = {
+    "rnnt_amd_ctc_align_workspace_size": (_sz, [_i] * 4),
+    "rnnt_amd_ctc_align": (_i, [_vp, _vp, _i, _i] + [_vp] * 7 + [_i] * 5),
+}
+# behind ADDITIVE_CTC, under the same contract (tests/test_host_ctc_align.py holds this one to it); a tuple of its own for
+# the same reason
+ADDITIVE_CTC_ALIGN = ((CTC_ALIGN_SYMBOLS, "warp_rnnt_amd_ctc_align.h"),)
 
 
 ABI_VERSION = 110   # rnnt_amd_version() of the library these argument lists belong to
@@ -309,7 +320,8 @@ def load():
     # additive entries do not move the version: a library built before them has to be told apart by its exports
     for table, header in (ADDITIVE + ADDITIVE_NEXT + ADDITIVE_TDT_JOINT + ADDITIVE_PRUNED + ADDITIVE_SIMPLE +
                           ADDITIVE_MULTIBLANK + ADDITIVE_TOPOLOGY + ADDITIVE_PRUNED_JOINT + ADDITIVE_PRUNE_RANGES +
-                          ADDITIVE_PRUNED_HAT + ADDITIVE_PRUNED_ALIGN + ADDITIVE_PRUNED_HIDDEN + ADDITIVE_CTC):
+                          ADDITIVE_PRUNED_HAT + ADDITIVE_PRUNED_ALIGN + ADDITIVE_PRUNED_HIDDEN + ADDITIVE_CTC +
+                          ADDITIVE_CTC_ALIGN):
         for name, (res, args) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

@@ -11,10 +11,11 @@
 // (include/warp_rnnt_amd_pruned_joint.h), the band selection between the recipe's two passes
 // (include/warp_rnnt_amd_prune_ranges.h) and the joiner's hidden activations on the band behind it
 // (include/warp_rnnt_amd_pruned_hidden.h), and the CTC loss the recipes train beside the transducer
-// (include/warp_rnnt_amd_ctc.h: producer, sweeps and gradient kernel all its own).  Host-side orchestration only: argument
-// checks, workspace carving, launches.
+// (include/warp_rnnt_amd_ctc.h: producer, sweeps and gradient kernel all its own) with its best-path alignment
+// (include/warp_rnnt_amd_ctc_align.h).  Host-side orchestration only: argument checks, workspace carving, launches.
 #include "../../include/warp_rnnt_amd_align.h"
 #include "../../include/warp_rnnt_amd_ctc.h"
+#include "../../include/warp_rnnt_amd_ctc_align.h"
 #include "../../include/warp_rnnt_amd_hat.h"
 #include "../../include/warp_rnnt_amd_joint_dropout.h"
 #include "../../include/warp_rnnt_amd_multiblank.h"
@@ -33,6 +34,7 @@
 #include "align.h"
 #include "api_common.h"
 #include "ctc.h"
+#include "ctc_align.h"
 #include "hat.h"
 #include "multiblank.h"
 #include "philox.h"
@@ -237,6 +239,21 @@ inline bool ctc_args_ok(const void* workspace, int dtype, const void* logits, co
     return dtype_ok(dtype) && ctc_shape_ok(N, T, L, V) && vocab_ok(V, blank) && workspace_ok(workspace) && logits &&
            labels && xn && yn && aligned(logits, dtype == RNNT_DTYPE_F32 ? 4 : 2) && aligned(labels, 4) && aligned(xn, 4) &&
            aligned(yn, 4);
+}
+
+// The CTC best-path alignment (ctc_align.hip): the rows' (max, log sum) k_ctc_emit writes, the emissions, the decision words.
+struct CtcAlignWorkspace {
+    float2* stats;
+    float* E;
+    void* decisions;
+};
+CtcAlignWorkspace ctc_align_layout(Carver& c, int N, int T, int L) {
+    const size_t rows = (size_t)N * T;
+    CtcAlignWorkspace w;
+    w.stats = c.take<float2>(rows);
+    w.E = c.take<float>(rows * ((size_t)L + 1));
+    w.decisions = c.take<char>(ctc_align_decision_bytes(N, T, L));
+    return w;
 }
 
 // The token-and-duration loss (tdt.hip): the plane of 2 + D channels, alpha, beta, the log-likelihoods.
@@ -1039,6 +1056,36 @@ rnntStatus_t rnnt_amd_ctc_logits_backward(rnntStream_t stream, void* workspace, 
     const CtcWorkspace w = ctc_layout(c, N, T, L);
     if (launch_ctc_backward(stream, dtype, logits, labels, xn, yn, w, dcosts, dlogits, N, T, L, V, blank) != hipSuccess)
         return RNNT_STATUS_EXPAND_FAILED;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// include/warp_rnnt_amd_ctc_align.h: best-path alignments of the CTC lattice (ctc_align.hip): the emissions -- k_ctc_emit's
+// for logits, a gather for log-probs -- then the sweep and the walk back in one launch.
+size_t rnnt_amd_ctc_align_workspace_size(int N, int T, int L, int V) {
+    if (!ctc_shape_ok(N, T, L, V)) return 0;
+    Carver c(nullptr);
+    ctc_align_layout(c, N, T, L);
+    return c.off;
+}
+
+rnntStatus_t rnnt_amd_ctc_align(rnntStream_t stream, void* workspace, int input_kind, int dtype, const void* inputs,
+                                const int* labels, const int* xn, const int* yn, float* scores, int* frame_tokens,
+                                int* emit_frames, int N, int T, int L, int V, int blank) {
+    if (input_kind != RNNT_CTC_ALIGN_IN_LOGITS && input_kind != RNNT_CTC_ALIGN_IN_LOG_PROBS)
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (!ctc_args_ok(workspace, dtype, inputs, labels, xn, yn, N, T, L, V, blank) || !scores || !frame_tokens ||
+        !emit_frames || !aligned(scores, 4) || !aligned(frame_tokens, 4) || !aligned(emit_frames, 4))
+        return RNNT_STATUS_INVALID_ARGUMENT;
+    if (N == 0) return RNNT_STATUS_SUCCESS;
+    Carver c(workspace);
+    const CtcAlignWorkspace w = ctc_align_layout(c, N, T, L);
+    const hipError_t e = input_kind == RNNT_CTC_ALIGN_IN_LOGITS
+                             ? launch_ctc_emit(stream, dtype, inputs, labels, xn, yn, w.stats, w.E, N, T, L, V, blank)
+                             : launch_ctc_align_gather(stream, dtype, inputs, labels, xn, yn, w.E, N, T, L, V, blank);
+    if (e != hipSuccess) return RNNT_STATUS_PROLOGUE_FAILED;
+    if (launch_ctc_align_sweep(stream, w.E, labels, xn, yn, w.decisions, scores, frame_tokens, emit_frames, N, T, L, V,
+                               blank) != hipSuccess)
+        return RNNT_STATUS_WARP_FAILED;
     return RNNT_STATUS_SUCCESS;
 }
 

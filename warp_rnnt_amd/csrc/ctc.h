@@ -16,6 +16,20 @@ inline bool ctc_shape_ok(int N, int T, int L, int V) {
     return (long long)N * T * (L + 1) < 1ll << 31;
 }
 
+// The lengths of utterance n as the kernels use them; outside 1 <= xn <= T, 0 <= yn <= L nothing of it is read
+struct CtcLens {
+    int Tn, Ln;
+    bool ok;
+};
+__device__ __forceinline__ CtcLens ctc_lens(const int* __restrict__ xn, const int* __restrict__ yn, int n, int T, int L) {
+    const int x = xn[n], y = yn[n];
+    CtcLens l;
+    l.ok = x >= 1 && x <= T && y >= 0 && y <= L;
+    l.Tn = l.ok ? x : 0;
+    l.Ln = l.ok ? y : 0;
+    return l;
+}
+
 // The workspace, carved by the C entry.  stats: (m, ls) per row; E: (N,T,L+1); alpha, beta: (N,T,2,L+1), channel 0 the
 // blank in front of label l (l = L_n: the final blank), channel 1 label l; ll: the log-likelihoods (CTC_FLOOR or below:
 // no path; NaN: lengths out of range); order: (N,L), position | CTC_ORDER_HEAD on the first position of a token
@@ -28,6 +42,11 @@ struct CtcWorkspace {
     int* order;
 };
 constexpr int CTC_ORDER_HEAD = 1 << 16;
+
+// The emissions alone (k_ctc_emit): stats (N,T) and E (N,T,L+1), rows t >= T_n untouched.  What launch_ctc_forward runs
+// first, and what the best-path alignment (ctc_align.hip) runs on logits: the same bits
+hipError_t launch_ctc_emit(hipStream_t stream, int dtype, const void* logits, const int* labels, const int* xn,
+                           const int* yn, float2* stats, float* E, int N, int T, int L, int V, int blank);
 
 // Emissions, then the alpha sweep: stats, E, alpha, ll and costs (N,)
 hipError_t launch_ctc_forward(hipStream_t stream, int dtype, const void* logits, const int* labels, const int* xn,

@@ -34,20 +34,6 @@ namespace {
 constexpr int CTC_LDS_FLOATS = 16384;    // a workgroup's LDS: rows of ceil8(V) floats, as many as fit (at least one)
 constexpr int CTC_ORDER_THREADS = 256;
 
-// The lengths of utterance n as the kernels use them; outside 1 <= xn <= T, 0 <= yn <= L nothing of it is read
-struct CtcLens {
-    int Tn, Ln;
-    bool ok;
-};
-__device__ __forceinline__ CtcLens ctc_lens(const int* __restrict__ xn, const int* __restrict__ yn, int n, int T, int L) {
-    const int x = xn[n], y = yn[n];
-    CtcLens l;
-    l.ok = x >= 1 && x <= T && y >= 0 && y <= L;
-    l.Tn = l.ok ? x : 0;
-    l.Ln = l.ok ? y : 0;
-    return l;
-}
-
 // M + log(exp(a-M) + exp(b-M) + exp(c-M)), the sum from the left; finite arguments (>= about 2 CTC_FLOOR) give a finite
 // result: exp of a difference that large is +0, and three floors give the floor (log 3 is absorbed)
 __device__ __forceinline__ float ctc_lse3(float a, float b, float c) {
@@ -292,20 +278,27 @@ hipError_t ctc_sweep(hipStream_t stream, const int* labels, const int* xn, const
 
 }  // namespace
 
-hipError_t launch_ctc_forward(hipStream_t stream, int dtype, const void* logits, const int* labels, const int* xn,
-                              const int* yn, const CtcWorkspace& w, float* costs, int N, int T, int L, int V, int blank) {
+hipError_t launch_ctc_emit(hipStream_t stream, int dtype, const void* logits, const int* labels, const int* xn,
+                           const int* yn, float2* stats, float* em, int N, int T, int L, int V, int blank) {
     if (!ctc_shape_ok(N, T, L, V) || blank < 0 || blank >= V) return hipErrorInvalidValue;
     if (N == 0) return hipSuccess;
     const unsigned rows = (unsigned)N * T;
-    const hipError_t e = row_typed(dtype, logits, nullptr, [&](auto* x, auto*) {
+    return row_typed(dtype, logits, nullptr, [&](auto* x, auto*) {
         using E = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
         const int G = row_group(V), R = ctc_rows_per_group(G, V), Vp = (V + ROW_CHUNK - 1) & ~(ROW_CHUNK - 1);
         return row_dispatch<E>(G, row_access<E>(V, x, nullptr), [&](auto g, auto acc) {
             k_ctc_emit<E, decltype(g)::value, decltype(acc)::value>
-                <<<(rows + R - 1) / R, R * G, (size_t)R * Vp * sizeof(float), stream>>>(x, labels, xn, yn, w.stats, w.E,
-                                                                                      rows, T, L, V, blank);
+                <<<(rows + R - 1) / R, R * G, (size_t)R * Vp * sizeof(float), stream>>>(x, labels, xn, yn, stats, em, rows,
+                                                                                      T, L, V, blank);
         });
     });
+}
+
+hipError_t launch_ctc_forward(hipStream_t stream, int dtype, const void* logits, const int* labels, const int* xn,
+                              const int* yn, const CtcWorkspace& w, float* costs, int N, int T, int L, int V, int blank) {
+    if (!ctc_shape_ok(N, T, L, V) || blank < 0 || blank >= V) return hipErrorInvalidValue;
+    if (N == 0) return hipSuccess;
+    const hipError_t e = launch_ctc_emit(stream, dtype, logits, labels, xn, yn, w.stats, w.E, N, T, L, V, blank);
     if (e != hipSuccess) return e;
     return ctc_sweep(stream, labels, xn, yn, w, costs, N, T, L, V, blank, 0);
 }

@@ -8,8 +8,13 @@ logits are read once for the emissions of the ``L_n + 1`` columns the lattice us
 and the backward reads the logits once more and writes d/d logits in their dtype.  No atomics: the same bits every run, and
 an utterance's bits do not depend on the batch it is in.
 
-Out of scope: torch's ``(T,N,V)`` layout, a ``log_probs`` entry, the CR-CTC consistency term, label priors, the compact
-layout, a gradient clamp, the mismatch guard, a joint / MFMA form.
+:func:`ctc_align` is the head's other use: the best path through the same lattice (csrc/ctc_align.hip,
+include/warp_rnnt_amd_ctc_align.h) -- its score, the token of every frame and the frame every label starts at -- for a whole
+batch in two launches, from logits (the loss's emissions, bit for bit) or from log-probs taken as they are.
+
+Out of scope: torch's ``(T,N,V)`` layout, a ``log_probs`` entry of the loss, the CR-CTC consistency term, label priors, the
+compact layout, a gradient clamp, the mismatch guard, a joint / MFMA form; of the alignment: per-frame scores, word-level
+merging.
 """
 from typing import Optional
 
@@ -57,6 +62,15 @@ def ctc_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, frames_leng
     grad only the forward kernels run."""
     if reduction not in REDUCTIONS:
         raise ValueError(f"reduction must be one of {REDUCTIONS}, not {reduction!r}")
+    blank = _checked(logits, labels, frames_lengths, labels_lengths, blank)
+    costs = CTCLossFromLogits.apply(logits, labels, frames_lengths, labels_lengths, blank)
+    if reduction == "none":
+        return costs
+    return costs.sum() if reduction == "sum" else costs.mean()
+
+
+def _checked(logits, labels, frames_lengths, labels_lengths, blank):
+    """The argument checks of both entries; returns the blank as a column of ``[0, V)``."""
     if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
         raise RuntimeError("logits must be (N,T,V)")
     if logits.dtype not in ops.LOGITS_DTYPES:
@@ -78,10 +92,29 @@ def ctc_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, frames_leng
         _core._check_cuda(x, name)
         if x.device != logits.device:
             raise RuntimeError(f"{name} must be on the device of logits ({logits.device}), not {x.device}")
-    costs = CTCLossFromLogits.apply(logits, labels, frames_lengths, labels_lengths, resolve_blank(blank, V))
-    if reduction == "none":
-        return costs
-    return costs.sum() if reduction == "sum" else costs.mean()
+    return resolve_blank(blank, V)
+
+
+def ctc_align(inputs: torch.Tensor, labels: torch.Tensor, frames_lengths: torch.Tensor, labels_lengths: torch.Tensor,
+              blank: int = 0, kind: str = "logits"):
+    """The best path through the CTC lattice of every utterance (forced alignment): ``(scores, frame_tokens, emit_frames)``.
+
+    ``inputs`` ``(N,T,V)``, batch-major and contiguous, fp32, bf16 or fp16: logits (``kind="logits"``: the emissions are the
+    log-softmax bits :func:`ctc_loss_from_logits` uses) or log-probs taken as they are, not normalised
+    (``kind="log_probs"``: what ``torchaudio.functional.forced_align`` takes, here for a whole ragged batch).  The other
+    arguments are :func:`ctc_loss_from_logits`'s, with its checks.
+
+    ``scores`` ``(N,)`` fp32: the log-probability of the best path; ``frame_tokens`` ``(N,T)`` int32: the token of every
+    frame on it (``blank`` between labels), -1 from ``frames_lengths[n]`` on; ``emit_frames`` ``(N,L)`` int32: the first
+    frame of every label, -1 from ``labels_lengths[n]`` on.  Of equal paths the one that stays in the higher state wins
+    (include/warp_rnnt_amd_ctc_align.h has the rule).  An utterance without any path gets ``-inf`` and rows of -1; lengths
+    outside ``1 <= T_n <= T``, ``0 <= L_n <= L`` give a NaN score and rows of -1.  Nothing is differentiable: the results are
+    detached.  Enqueue-only: the call can be captured into a graph."""
+    if kind not in ops.CTC_ALIGN_KINDS:
+        raise ValueError(f"kind must be one of {tuple(ops.CTC_ALIGN_KINDS)}, not {kind!r}")
+    blank = _checked(inputs, labels, frames_lengths, labels_lengths, blank)
+    with torch.no_grad():
+        return ops.ctc_align(inputs.detach(), labels, frames_lengths, labels_lengths, ops.CTC_ALIGN_KINDS[kind], blank)[:3]
 
 
 class CTCLoss(torch.nn.Module):

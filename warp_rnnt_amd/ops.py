@@ -1257,6 +1257,37 @@ def ctc_logits_backward(logits, labels, xn, yn, workspace, grad_costs, blank=0):
     return out
 
 
+CTC_ALIGN_KINDS = {"logits": _lib.CTC_ALIGN_IN_LOGITS, "log_probs": _lib.CTC_ALIGN_IN_LOG_PROBS}
+
+
+def ctc_align(inputs, labels, xn, yn, input_kind, blank=0):
+    """Best-path alignments of the CTC lattice (include/warp_rnnt_amd_ctc_align.h, csrc/ctc_align.hip): inputs (N,T,V) logits
+    or log-probs, by input_kind; tensors validated by the caller.  Returns scores (N,) fp32 -- -inf where there is no path --
+    frame_tokens (N,T) and emit_frames (N,L) int32, and the workspace, whose emission plane (N,T,L+1) fp32 lies at byte
+    :func:`ctc_align_emissions_offset`."""
+    L = _lib.load()
+    N, T, V = inputs.shape
+    dev = inputs.device
+    _ctc_check(N, T, labels.shape[1], V, blank)
+    with torch.cuda.device(dev):
+        scores = torch.empty((N,), dtype=torch.float32, device=dev)
+        frame_tokens = torch.empty((N, T), dtype=torch.int32, device=dev)
+        emit_frames = torch.empty((N, labels.shape[1]), dtype=torch.int32, device=dev)
+        if N == 0:
+            return scores, frame_tokens, emit_frames, None
+        ws = _workspace(dev, L.rnnt_amd_ctc_align_workspace_size, "N T L V", N, T, labels.shape[1], V)
+        _check(L.rnnt_amd_ctc_align(_stream(dev), ws.data_ptr(), input_kind, LOGITS_DTYPES[inputs.dtype], inputs.data_ptr(),
+                                    labels.data_ptr(), xn.data_ptr(), yn.data_ptr(), scores.data_ptr(),
+                                    frame_tokens.data_ptr(), emit_frames.data_ptr(), N, T, labels.shape[1], V, blank))
+    return scores, frame_tokens, emit_frames, ws
+
+
+def ctc_align_emissions_offset(N, T):
+    """Byte offset of the emission plane in :func:`ctc_align`'s workspace: behind the (N,T,2) fp32 row statistics, on a
+    multiple of 256."""
+    return -(-8 * N * T // 256) * 256
+
+
 ALIGN_IN_HAT_LOGITS = _lib.ALIGN_IN_HAT_LOGITS
 
 
